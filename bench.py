@@ -2,7 +2,7 @@
 """
 bench.py — real-time audio streams (xRT) at 48 kHz on MI355X: BASELINE.json's metric on its configs.
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--dump-outputs DIR] [--full]
 
   --config 2 (default)  wavenet_a1_standard.nam, 256 concurrent streams per GPU, buffer = 64   (BASELINE configs[1], headline)
   --config 3            lstm.nam, 1,024 concurrent streams per GPU                             (configs[2])
@@ -12,10 +12,10 @@ bench.py — real-time audio streams (xRT) at 48 kHz on MI355X: BASELINE.json's 
 A "step" is one pass of the hot path over one batch: every stream of the batch advances by one 64-frame buffer
 (`DSP::process(in, out, 64)` for all streams at once). Inputs are resident in HBM before the timed region. After W
 untimed warm-up steps a timed region is EXACTLY K steps between barrier + torch.cuda.synchronize() pairs, MAX over
-ranks; the region is repeated --reps times (default 11, protocol of the reference's benchmark_wavenet_a1.sh:10) and
-`value` is the MEDIAN region (every region's time is in the line). Weak scaling: every GPU owns `--streams`
-independent streams, sharded per width class (no data-path collective; RCCL only broadcasts the model text once,
-scatters the input bank before and gathers the rendered tail after the timed regions).
+ranks; the region is repeated --reps times (default 1: a plain run times exactly K steps; with --full 11, protocol of
+the reference's benchmark_wavenet_a1.sh:10) and `value` is the MEDIAN region (every region's time is in the line).
+Weak scaling: every GPU owns `--streams` independent streams, sharded per width class (no data-path collective; RCCL
+only broadcasts the model text once, scatters the input bank before and gathers the rendered tail after the timed regions).
 
 Launch modes (the kernel is the same):
   --launch block     one kernel launch per 64-frame step, K launches enqueued back to back
@@ -24,8 +24,17 @@ Launch modes (the kernel is the same):
 
 Prints ONE JSON line (rank 0): contract keys + `roofline` (algorithmic bytes of SURVEY.md §8d against the 8 TB/s HBM
 peak, with the fp32 fraction, the PMC-measured HBM bytes and the LDS counters of the dominant kernel from
-profiles/traffic.json) + `cpu_baseline` (the CPU oracle on the box's host cores) + `latency_us` (per-launch
-min / p50 / p99 / p99.9, as tools/bench_a2_fast.cpp:274-296 prints them) + `fast_tanh_off` and `zeros_input` side runs.
+profiles/traffic.json). A plain run does nothing else: set-up, warm-up, the timed steps, the line.
+
+--full adds what takes runs of its own: the parity check against the CPU oracle, `cpu_baseline` (the CPU oracle on the
+box's host cores), the resident-launch comparison, `latency_us` (per-launch min / p50 / p99 / p99.9, as
+tools/bench_a2_fast.cpp:274-296 prints them), the `fast_tanh_off`, `zeros_input` and `wav_input` side runs and, for the
+default configuration on one GPU, brief runs of the other configurations and `host_io`; the timed region is repeated 11
+times or more unless --reps says otherwise.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path returned in its last step: DIR/output_last_step.npy,
+float32 [streams, output channels, block] (every rank's streams, in global order). The input bank is seeded, so the same
+arguments give the same inputs from run to run and two builds can be compared output for output.
 
 --dry-run executes the same scatter -> steps -> gather -> all_reduce(MAX) code on CPU tensors over gloo with a stub
 in place of the kernels (tests/test_bench_dry_run.py): the distributed branch is exercised without GPUs.
@@ -299,7 +308,7 @@ def run_other_configs(args):
                else ["--config", "2" if c == "2_steady" else str(c)])
         steps, warm = ("64", "64") if c == "3_long" else ("500", "50")
         cmd = [sys.executable, os.path.abspath(__file__)] + sel + ["--gpus", "1", "--steps", steps, "--warmup", warm,
-               "--brief", "--full-line", "--persistent", str(args.persistent), "--fast-tanh", str(args.fast_tanh)]
+               "--brief", "--full", "--full-line", "--persistent", str(args.persistent), "--fast-tanh", str(args.fast_tanh)]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         t0 = time.perf_counter()
@@ -319,6 +328,24 @@ def run_other_configs(args):
         except Exception as e:  # noqa: BLE001
             res[str(c)] = {"error": str(e)[:400]}
     return res
+
+
+WINDOW_BYTES = 32 << 20  # a plain run's input bank at most (beyond it the steps cycle through the window)
+
+
+def window_segments(first, count, n_blocks):
+    """Steps first .. first + count - 1 on a window of n_blocks blocks: step s renders block s % n_blocks. (start block, count)
+    pieces that do not wrap; one piece, (first, count), whenever the steps fit the window."""
+    if first + count <= n_blocks:
+        return [(first, count)]
+    out = []
+    while count > 0:
+        start = first % n_blocks
+        n = min(count, n_blocks - start)
+        out.append((start, n))
+        first += n
+        count -= n
+    return out
 
 
 class HipEngine:
@@ -349,11 +376,12 @@ class HipEngine:
 
     def run_steps(self, first, count, launch):
         sh, b = self.stream.cuda_stream, self.block
-        if launch == "block":
-            for s in range(first, first + count):
-                self.batch.process_device(self.xp + s * b * 4, self.yp + s * b * 4, b, self.T, sh)
-        else:
-            self.batch.process_device(self.xp + first * b * 4, self.yp + first * b * 4, count * b, self.T, sh)
+        for first, count in window_segments(first, count, self.T // b):
+            if launch == "block":
+                for s in range(first, first + count):
+                    self.batch.process_device(self.xp + s * b * 4, self.yp + s * b * 4, b, self.T, sh)
+            else:
+                self.batch.process_device(self.xp + first * b * 4, self.yp + first * b * 4, count * b, self.T, sh)
 
     def event(self):
         e = self.torch.cuda.Event(enable_timing=True)
@@ -400,8 +428,9 @@ class StubEngine:
         self.x, self.y = x, y
 
     def run_steps(self, first, count, launch):
-        a, b = first * self.block, (first + count) * self.block
-        self.y[:, :, a:b] = 0.5 * self.x[:, :1, a:b]
+        for first, count in window_segments(first, count, self.x.shape[2] // self.block):
+            a, b = first * self.block, (first + count) * self.block
+            self.y[:, :, a:b] = 0.5 * self.x[:, :1, a:b]
 
     def event(self):
         return time.perf_counter()
@@ -623,6 +652,25 @@ def wav_fidelity_run(fresh_engine, model, n_streams, block, dev, oracle_err, fas
                     "0.35 peak), median of the passes; a fidelity run beside `value`, not `value`"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, arrays: dict):
+    """--dump-outputs: each array as DIR/<name>.npy in float32 (float64 stays float64). Should the whole exceed 64 MB, a fixed,
+    seeded sample of the leading axis (the streams) is kept, in order, so that two runs keep the same rows."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.size * (8 if a.dtype == np.float64 else 4) for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":
         return cpu_worker(sys.argv[2:])
@@ -632,7 +680,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--reps", type=int, default=None,
                     help="timed regions of exactly --steps steps, each behind its own --warmup untimed steps; value = the "
-                         "median region. Default: 11, more for short regions (about 30 ms of timed work, at most 101)")
+                         "median region. Default: 1; with --full 11, more for short regions (about 30 ms of timed work, at most 101)")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json config (see the module docstring)")
     ap.add_argument("--streams", type=int, default=None, help="streams per GPU (weak scaling); default from --config")
     ap.add_argument("--block", type=int, default=64)
@@ -649,7 +697,8 @@ def main():
     ap.add_argument("--spinup-ms", type=float, default=150.0,
                     help="untimed GPU work on a scratch batch before the warm-up steps (brings the clocks up; the measured "
                          "batch's state is not touched)")
-    ap.add_argument("--check", type=int, default=1, help="verify stream 0 of rank 0 against the oracle after timing")
+    ap.add_argument("--check", type=int, default=None,
+                    help="verify the first and last stream of every rank against the oracle after timing (default: 1 with --full, else 0)")
     ap.add_argument("--persistent", type=int, default=1,
                     help="--launch block: use the persistent block mode when the batch is eligible (one resident launch, one "
                          "doorbell per step); 0 = one kernel launch per step")
@@ -664,8 +713,17 @@ def main():
                     help="print the whole record as the line (default: a compact line of at most 6 KB, the whole record goes to "
                          "gpurun_out/bench_full.json)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default invocation (config 2, one GPU): do not append brief runs of configs 3, 4 and 5")
+                    help="default invocation (config 2, one GPU) with --full: do not append brief runs of configs 3, 4 and 5")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity check, CPU baseline, resident-launch comparison, latency pass, "
+                         "side runs, other configurations, host_io, 11+ timed regions (the --no-* options still turn parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returned in its last step to DIR/output_last_step.npy")
     args = ap.parse_args()
+    if args.check is None:
+        args.check = 1 if args.full else 0
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_side_runs = args.no_cpu_baseline = args.no_other_configs = True
     if args.brief:
         args.no_side_runs = True
     cfg = CONFIGS[args.config]
@@ -702,8 +760,16 @@ def main():
     model_path = os.path.join(ROOT, "tests", "golden", "models", model_name + ".nam")
     block, K, W = args.block, args.steps, args.warmup
     # repetitions: an odd count; short regions (the driver's --steps 20 is 0.3 ms) get more of them
-    R = max(1, args.reps) if args.reps is not None else min(101, max(11, int(30e-3 / max(K * 15e-6, 1e-9)) | 1))
-    T = (W + K) * block
+    R = (max(1, args.reps) if args.reps is not None else
+         min(101, max(11, int(30e-3 / max(K * 15e-6, 1e-9)) | 1)) if args.full else 1)
+    # the input window: one block per warm-up and timed step. A plain run without the check caps it at WINDOW_BYTES of input
+    # and lets the steps cycle through it (step s renders block s % n_blocks: the same work per step), so that set-up does
+    # not grow with --steps; the parity check needs the first pass unwrapped
+    n_blocks = W + K
+    if not args.full and not args.check:
+        n_blocks = min(n_blocks, max(64, WINDOW_BYTES // (n_streams * world * block * 4)))
+    last_block = (W + K - 1) % n_blocks  # where the last timed step's output lands
+    T = n_blocks * block
 
     # ---- one-time weight broadcast: rank 0 reads the file, the text travels once over RCCL ----
     model_text = None
@@ -829,6 +895,13 @@ def main():
             got_dev = y[chk_rows, 0, :n_chk].clone()  # parity sample: blocks 0..W+K of the FIRST pass over the window
             if not args.dry_run:
                 torch.cuda.synchronize(dev)  # (see above: the copy must not race the next repetition)
+    # --dump-outputs: the last timed step's output buffers, copied before anything else writes into the window (the
+    # latency pass and the side runs of --full do); waited for, so that the copy cannot race a later launch
+    last_dev = None
+    if args.dump_outputs:
+        last_dev = y[:, :, last_block * block:(last_block + 1) * block].clone()
+        if not args.dry_run:
+            torch.cuda.synchronize(dev)
     red = reduce_max([v for r_ in raw for v in r_[:2]])
     regions = [{"wall_s": red[2 * i], "gpu_s": red[2 * i + 1], "enqueue_s": raw[i][2],
                 "flushed_s": raw[i][1] if pers else None} for i in range(R)]
@@ -842,7 +915,7 @@ def main():
     # alongside (not `value`): the same K blocks as ONE resident launch — the offline re-amp shape, no per-block kernel
     # boundary — timed the same way
     other = None
-    if args.launch == "block" and not args.brief:
+    if args.launch == "block" and not args.brief and args.full:
         fence(engine)
         t1 = time.perf_counter()
         engine.run_steps(W, K, "resident")
@@ -886,15 +959,19 @@ def main():
         dist.barrier()
 
     # after the timed regions: gather the last rendered block of every stream back to rank 0 over RCCL
-    tail = y[:, :, (W + K - 1) * block:].contiguous()
+    tail = y[:, :, last_block * block:(last_block + 1) * block].contiguous()
     gathered = sharding.gather_rows(tail, owners, n_total, dst=0) if distributed else tail
     finite = bool(torch.isfinite(y).all()) and (gathered is None or bool(torch.isfinite(gathered).all()))
     gathered_ok = gathered is None or tuple(gathered.shape) == (n_total, oc, block)
+    if last_dev is not None:
+        last_all = sharding.gather_rows(last_dev, owners, n_total, dst=0) if distributed else last_dev
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"output_last_step": last_all.cpu().numpy()})
 
     parity = None
     parity_detail = None
     parity_per_rank = None
-    parity_streams = [int(mine[i]) for i in chk_rows]  # (global stream numbers this rank checked)
+    parity_streams = [int(mine[i]) for i in chk_rows] if args.check else []  # (global stream numbers this rank checked)
     if args.check and chk_rows:
         if args.dry_run:
             parity = float(torch.max(torch.abs(got_dev - 0.5 * x[chk_rows, 0, :n_chk])))
@@ -1184,7 +1261,7 @@ def main():
         if args.full_line:
             print(json.dumps(out), flush=True)
         else:
-            full_path = write_full_record(out) if world == 1 or rank == 0 else None
+            full_path = write_full_record(out) if args.full else None
             print(json.dumps(compact_line(out, full_path)), flush=True)
     if engine is not None:
         engine.close()

@@ -10,7 +10,7 @@ import sys, json
 j = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('  ', '$1', j['config']['kernel'], round(j['ms_per_step']*1e3,3), 'us/step', j['value'], 'err', j['max_abs_err_vs_oracle'])
 "; }
-B="python3 bench.py --gpus 1 --steps 500 --warmup 50 --brief --no-cpu-baseline"
+B="python3 bench.py --gpus 1 --steps 500 --warmup 50 --brief --full --no-cpu-baseline"
 for c in 4 5; do
   NAM_HIP_SESSION_STATS=1 $B --config $c 2>&1 | grep "nam_wn_reg_kernel:" | sort | uniq -c
 done

@@ -4,10 +4,10 @@
 #   gpurun --timeout 1500 -- 'bash scripts/gpu_round_check.sh'
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export NAM_HIP_PERSIST_TIMEOUT_MS=8000
 ( timeout 900 python -m pytest tests -m gpu -x -q --durations=8 2>&1 | tail -16 ) > gpurun_out/check_pytest.txt; tail -3 gpurun_out/check_pytest.txt
-timeout 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/check_bench_default.out 2> gpurun_out/check_bench_default.err
-tail -1 gpurun_out/check_bench_default.out | wc -c; tail -1 gpurun_out/check_bench_default.out
+timeout 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > /tmp/check_bench_default.out 2> /tmp/check_bench_default.err
+tail -1 /tmp/check_bench_default.out | wc -c; tail -1 /tmp/check_bench_default.out
 cp gpurun_out/bench_full.json gpurun_out/check_bench_default_full.json
-grep PARITY gpurun_out/check_bench_default.err
+grep PARITY /tmp/check_bench_default.err
 for p in valu_rate sync_tail; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -o /tmp/$p tools/src/$p.hip 2>/dev/null && /tmp/$p > gpurun_out/check_$p.txt
 done

@@ -12,9 +12,9 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 for C in 2 4; do
   if [ "$N" -gt 1 ]; then
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port ${MASTER_PORT:-29517} \
-      bench.py --gpus "$N" --config $C --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-other-configs | grep '^{' > "$OUT/bench_config${C}_n${N}.json"
+      bench.py --gpus "$N" --config $C --steps ${STEPS:-20} --warmup ${WARMUP:-5} --full --no-other-configs | grep '^{' > "$OUT/bench_config${C}_n${N}.json"
   else
-    python bench.py --gpus 1 --config $C --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-other-configs | grep '^{' > "$OUT/bench_config${C}_n${N}.json"
+    python bench.py --gpus 1 --config $C --steps ${STEPS:-20} --warmup ${WARMUP:-5} --full --no-other-configs | grep '^{' > "$OUT/bench_config${C}_n${N}.json"
   fi
   python - "$OUT/bench_config${C}_n${N}.json" <<'PY'
 import json, sys

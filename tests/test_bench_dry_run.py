@@ -53,7 +53,7 @@ def test_bench_distributed_branch_world2_gloo(config, streams):
                    MASTER_PORT=str(port))
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "2",
-             "--reps", "3", "--config", str(config), "--streams", str(streams)],
+             "--reps", "3", "--config", str(config), "--streams", str(streams), "--full"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT))
     outs = [p.communicate(timeout=150) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]
@@ -104,6 +104,33 @@ def test_bench_line_stays_under_the_drivers_tail():
     assert len(json.dumps(bench.compact_line(big, None)).encode()) < bench.LINE_LIMIT
 
 
+@pytest.mark.timeout(180)
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full): ONE timed region of exactly --steps steps, the contract's keys, no check or side figure;
+    --dump-outputs writes what the timed path returned in its last step, the same from run to run (seeded inputs)."""
+    import numpy as np
+    from signals import stream_bank
+    steps, warmup = 7, 3
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run", "--steps", str(steps),
+                            "--warmup", str(warmup), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=150, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == steps and line["warmup"] == warmup and line["repetitions"]["n"] == 1 and line["ms_per_step"] > 0
+        assert line["max_abs_err_vs_oracle"] is None and line["parity_streams_checked"] == []
+        assert not {"cpu_baseline", "other_configs", "latency_us", "resident_launch", "zeros_input", "host_io"} & set(line)
+        dumps.append(np.load(d / "output_last_step.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (256, 1, 64)
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    # the stub renders y = 0.5 x: the dump is the last timed block of the seeded input bank
+    bank = stream_bank(256, (warmup + steps) * 64, seed=0)
+    np.testing.assert_array_equal(dumps[0][:, 0, :], 0.5 * bank[:, (warmup + steps - 1) * 64:].astype(np.float32))
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("config,streams", [(2, 64), (5, 96)])
@@ -118,7 +145,7 @@ def test_bench_distributed_branch_on_rccl_one_rank(config, streams):
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-distributed", "--steps", "20",
-         "--warmup", "5", "--reps", "3", "--config", str(config), "--streams", str(streams), "--no-cpu-baseline",
+         "--warmup", "5", "--reps", "3", "--config", str(config), "--streams", str(streams), "--full", "--no-cpu-baseline",
          "--no-side-runs", "--spinup-ms", "0"],
         env=env, capture_output=True, text=True, timeout=550, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]

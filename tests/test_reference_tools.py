@@ -1,8 +1,8 @@
 """The drop-in boundary proven on the reference's OWN callers: /root/reference/tools/{benchmodel,
 benchmodel_bufsize,loadmodel,render}.cpp compile UNMODIFIED against cpp/NAM/*.h (+ cpp/tools/wav.h for the AudioDSPTools
 header render.cpp names) and link against libnam_hip.so (cpp/Makefile: ref_tools; the sources are compiled where they lie,
-never copied). The CPU test does the compile here, where /root/reference exists; the binaries (cpp/ref_tools/, git-ignored)
-travel to the GPU box with the snapshot, where the -m gpu tests run them on the reference's example models
+never copied). The CPU test does the compile where the reference tree exists; the binaries (oracle/_ref/tools/, git-ignored,
+with the other reference builds) travel with the built tree to the GPU machine, where the -m gpu tests run them on the example models
 (tools/benchmodel.cpp:9-11, 83-131; NAM/slimmable.h:13-29)."""
 import os
 import re
@@ -15,7 +15,7 @@ from conftest import ROOT, model_path
 
 REF = "/root/reference"
 TOOLS = ("benchmodel", "benchmodel_bufsize", "loadmodel", "render")
-OUT = os.path.join(ROOT, "cpp", "ref_tools")
+OUT = os.path.join(ROOT, "oracle", "_ref", "tools")
 
 
 def test_reference_tools_compile_unmodified_against_the_adapter(nam_lib):
@@ -27,7 +27,7 @@ def test_reference_tools_compile_unmodified_against_the_adapter(nam_lib):
     assert r.returncode == 0, r.stderr[-3000:]
     for t in TOOLS:
         # every compile line names the reference's own source file, not a copy
-        assert re.search(rf"-o ref_tools/{t} {REF}/tools/{t}\.cpp ", r.stdout), r.stdout
+        assert re.search(rf"-o \.\./oracle/_ref/tools/{t} {REF}/tools/{t}\.cpp ", r.stdout), r.stdout
         assert os.access(os.path.join(OUT, t), os.X_OK)
     # the headers the tools include beyond the standard library all resolve inside cpp/ (no reference header is on the path)
     assert "-I/root/reference" not in r.stdout and "-I" + REF not in r.stdout
@@ -40,7 +40,7 @@ def test_reference_tools_compile_unmodified_against_the_adapter(nam_lib):
 def _tool(name):
     p = os.path.join(OUT, name)
     if not os.access(p, os.X_OK):
-        pytest.skip("cpp/ref_tools was not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/tools was not built (needs the reference tree at build time)")
     return p
 
 
