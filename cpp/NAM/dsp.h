@@ -68,6 +68,10 @@ struct BatchDeleter
 {
   void operator()(nam_hip_batch* b) const { nam_hip_batch_destroy(b); }
 };
+struct BankDeleter
+{
+  void operator()(nam_hip_bank* b) const { nam_hip_bank_free(b); }
+};
 } // namespace detail
 
 namespace detail
@@ -201,7 +205,7 @@ protected:
     if (mBatch && maxBufferSize == mMaxBufferSize)
       return;
     nam_hip_batch* b = nullptr;
-    detail::check(nam_hip_batch_create(mModel.get(), mDevice, NumStreams(), maxBufferSize, &b));
+    detail::check(CreateBatch(maxBufferSize, &b));
     mBatch.reset(b);
     // persistent block mode where the model's kernel has one (include/nam_hip.h): process() then costs a command and a
     // wait on host-mapped buffers instead of two copies, a launch and a stream synchronise per buffer (buffers of a
@@ -212,6 +216,10 @@ protected:
     mOut.assign((size_t)NumOutputChannels() * NumStreams() * maxBufferSize, NAM_SAMPLE(0));
   }
   virtual int NumStreams() const { return 1; }
+  virtual int CreateBatch(const int maxBufferSize, nam_hip_batch** b)
+  {
+    return nam_hip_batch_create(mModel.get(), mDevice, NumStreams(), maxBufferSize, b);
+  }
 
   std::shared_ptr<nam_hip_model> mModel;
   std::unique_ptr<nam_hip_batch, detail::BatchDeleter> mBatch;
@@ -255,6 +263,44 @@ protected:
   double mRatio = 1.0;
 };
 
+// A model bank (not in the reference; include/nam_hip.h: nam_hip_bank_create): loaded models that ONE BatchDSP runs side by
+// side, each stream bound to one member — a host that serves many captures of the official WaveNet topology (standard, lite,
+// feather; all loaded with the same fast tanh setting). A value type: copies share the immutable bank. Construction throws
+// std::runtime_error (naming the member) when the models cannot share a launch.
+class ModelBank
+{
+public:
+  explicit ModelBank(std::vector<std::shared_ptr<nam_hip_model>> models)
+  : mModels(std::move(models))
+  {
+    std::vector<const nam_hip_model*> raw;
+    for (const auto& m : mModels)
+      raw.push_back(m.get());
+    nam_hip_bank* b = nullptr;
+    detail::check(nam_hip_bank_create(raw.data(), (int)raw.size(), &b));
+    mBank.reset(b, detail::BankDeleter());
+  }
+  // from .nam files, loaded with the current Activation::using_fast_tanh (as nam::get_dsp(path) does)
+  static ModelBank FromFiles(const std::vector<std::string>& paths)
+  {
+    std::vector<std::shared_ptr<nam_hip_model>> models;
+    for (const std::string& p : paths)
+    {
+      nam_hip_model* m = nullptr;
+      detail::check(nam_hip_model_load(p.c_str(), activations::Activation::using_fast_tanh ? 1 : 0, &m));
+      models.emplace_back(m, detail::ModelDeleter());
+    }
+    return ModelBank(std::move(models));
+  }
+  int size() const { return nam_hip_bank_n_models(mBank.get()); }
+  const nam_hip_bank* handle() const { return mBank.get(); }
+  const std::shared_ptr<nam_hip_model>& model(const int member) const { return mModels.at((size_t)member); }
+
+private:
+  std::vector<std::shared_ptr<nam_hip_model>> mModels; // (the getters of a BatchDSP answer from member 0)
+  std::shared_ptr<nam_hip_bank> mBank;
+};
+
 // The many-stream form of the same object (not in the reference): N independent streams, planar
 // float32 host buffers [stream][channel][frame].
 class BatchDSP : public DSP
@@ -265,6 +311,32 @@ public:
   , mStreams(n_streams)
   {
   }
+  // One stream per entry of `members`: stream s runs bank member members[s].
+  BatchDSP(const ModelBank& bank, std::vector<int> members, int device = 0)
+  : DSP(bank.model(0), device)
+  , mStreams((int)members.size())
+  , mBank(std::make_shared<ModelBank>(bank))
+  , mMembers(std::move(members))
+  {
+  }
+  // Binds the listed streams (nullptr: all) to bank member `member`: they start from that member's freshly reset (and, after a
+  // Reset with prewarm, prewarmed) state; every other stream is untouched (nam_hip_batch_set_stream_model).
+  void SetStreamModel(const int* stream_ids, int n, int member)
+  {
+    if (!mBank)
+      throw std::runtime_error("SetStreamModel: this BatchDSP was not built from a ModelBank");
+    if (mBatch)
+      detail::check(nam_hip_batch_set_stream_model(mBatch.get(), stream_ids, n, member));
+    else if (member < 0 || member >= mBank->size())
+      throw std::runtime_error("SetStreamModel: member out of range");
+    for (int i = 0; i < (stream_ids ? n : mStreams); i++) // (kept for the next SetMaxBufferSize, which builds a new batch)
+    {
+      const int s = stream_ids ? stream_ids[i] : i;
+      if (s >= 0 && s < mStreams)
+        mMembers[(size_t)s] = member;
+    }
+  }
+  int GetStreamModel(int stream) const { return mBank ? mMembers.at((size_t)stream) : 0; }
   void process_batch(const float* in, float* out, const int num_frames)
   {
     detail::check(nam_hip_batch_process_f32(mBatch.get(), in, out, num_frames));
@@ -301,7 +373,15 @@ public:
 
 protected:
   int NumStreams() const override { return mStreams; }
+  int CreateBatch(const int maxBufferSize, nam_hip_batch** b) override
+  {
+    if (!mBank)
+      return DSP::CreateBatch(maxBufferSize, b);
+    return nam_hip_batch_create_bank(mBank->handle(), mDevice, mStreams, maxBufferSize, mMembers.data(), b);
+  }
   int mStreams;
+  std::shared_ptr<ModelBank> mBank; // nullptr: one model
+  std::vector<int> mMembers;
 };
 
 } // namespace nam

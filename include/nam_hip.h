@@ -20,6 +20,7 @@
  *   - a `nam_hip_model` is immutable host data (parsed file + device plans); a `nam_hip_batch`
  *     owns the GPU memory (weights, per-stream history) for N streams of one model on one device
  *     and must be used from one host thread at a time, like a reference `nam::DSP` instance.
+ *     A `nam_hip_bank` is an immutable set of models one batch runs side by side (nam_hip_batch_create_bank).
  */
 #ifndef NAM_HIP_H
 #define NAM_HIP_H
@@ -71,6 +72,7 @@ extern "C" {
 
 typedef struct nam_hip_model nam_hip_model;
 typedef struct nam_hip_batch nam_hip_batch;
+typedef struct nam_hip_bank nam_hip_bank;
 
 /* What nam::DSP's getters report — NAM/dsp.h:100-149,153, NAM/slimmable.h:23-29. */
 typedef struct nam_hip_model_info
@@ -186,6 +188,42 @@ NAM_HIP_API int nam_hip_model_slimmable_breakpoints(const nam_hip_model* model, 
 NAM_HIP_API int nam_hip_batch_create(const nam_hip_model* model, int device, int n_streams, int max_frames,
                          nam_hip_batch** out_batch);
 NAM_HIP_API void nam_hip_batch_destroy(nam_hip_batch* batch);
+
+/* ---- model banks: one batch whose streams each run their own model ("captures") ----
+ * A host that serves captures runs one architecture with many weight sets. A bank is an immutable set of loaded models that
+ * ONE batch runs side by side — one launch, one session, one ticket queue — each stream bound to one member.
+ * nam_hip_bank_create is host-only (no device call). It accepts a set when every member plans onto the same instantiation of
+ * the interleaved-frame kernels with the same blob and state layout: the official WaveNet topology (two arrays of ten layers,
+ * kernel size 3, dilations 1 .. 512) at 16 / 8 channels — the lite 12 / 6 and feather 8 / 4 sizes are zero-padded to it at plan
+ * time —, all members Tanh or all Fasttanh (so: loaded with the same fast_tanh), no lookup tables. The plans are compared field
+ * by field; the first difference — or a member of another kind: LSTM, nano, A2, FiLM / gated models, another activation, a
+ * slimmable model — is refused with NAM_HIP_ERR_UNSUPPORTED and a message naming the member index and the field. n_models <= 0
+ * or a NULL member: NAM_HIP_ERR_INVALID_ARGUMENT. A bank of one model is legal. The bank copies what it needs: the models may
+ * be freed right after, and the bank may be freed while batches created from it live. */
+NAM_HIP_API int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hip_bank** out_bank);
+NAM_HIP_API void nam_hip_bank_free(nam_hip_bank* bank);
+/* Number of members (>= 1), or NAM_HIP_ERR_INVALID_ARGUMENT for a NULL bank. */
+NAM_HIP_API int nam_hip_bank_n_models(const nam_hip_bank* bank);
+/* nam_hip_batch_create for a bank: stream s runs member stream_model[s] (NULL: every stream member 0; an index outside
+ * [0, n_models) is NAM_HIP_ERR_INVALID_ARGUMENT). The result is an ordinary batch: reset, process_*, render, set_persistent,
+ * flush, submit / wait, synchronize, kernel_name* and n_streams work as for one model; set_slimmable_size returns what it
+ * returns for a non-slimmable model. The members' weights live in one device allocation [member][blob]; a workgroup resolves
+ * its stream's member once, in the kernel's prologue. Kernels: the NAM_HIP_KERNEL_A1_IL family for every launch shape —
+ * nam_a1_q_kernel in sessions and launches of several buffers, nam_a1_p4_kernel for short bursts and short blocking calls,
+ * nam_a1_p2_kernel for a lone buffer (where a one-model batch under AUTO runs nam_a1_mfma_kernel, which knows no banks);
+ * nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_A1_IL, anything else is NAM_HIP_ERR_UNSUPPORTED.
+ * Reset with prewarm runs the silence through every stream with its own member's weights (no cached image: it depends on the
+ * weights); the state equals, bit for bit, what a one-model batch of that member holds after the same Reset. */
+NAM_HIP_API int nam_hip_batch_create_bank(const nam_hip_bank* bank, int device, int n_streams, int max_frames,
+                                          const int* stream_model, nam_hip_batch** out_batch);
+/* Binds the listed streams (NULL: all) to `member`, following nam_hip_batch_set_slimmable_size's contract: a running session's
+ * launch ends first (the kernels load weights in their prologue), the streams that change member start from a freshly reset
+ * (and, if the batch was last reset with prewarm, prewarmed) state of the new member; every other stream's state and output
+ * are untouched; a stream already bound to `member` is left alone. A stream or member out of range — or a batch that was not
+ * created from a bank — is NAM_HIP_ERR_INVALID_ARGUMENT and changes nothing. */
+NAM_HIP_API int nam_hip_batch_set_stream_model(nam_hip_batch* batch, const int* stream_ids, int n_ids, int member);
+/* The member `stream` is bound to (0 for every stream of a one-model batch), or NAM_HIP_ERR_INVALID_ARGUMENT. */
+NAM_HIP_API int nam_hip_batch_get_stream_model(const nam_hip_batch* batch, int stream);
 
 /* DSP::Reset (NAM/dsp.cpp:130-140): WaveNet history is zeroed; if `prewarm` != 0 the model then
  * processes ceil(prewarm_samples / max_frames) * max_frames frames of silence (DSP::prewarm,

@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "NamHipError", "NamFileValidationError", "Model", "Batch", "get_dsp", "get_dsp_json", "get_dsp_data", "get_sample_rate_from_nam_file", "lib_path", "load_library",
-    "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_A1", "KERNEL_A1_MFMA", "KERNEL_A1_IL", "KERNEL_WN_REG", "ABI_SYMBOLS",
+    "KERNEL_AUTO", "KERNEL_GENERIC", "KERNEL_A1", "KERNEL_A1_MFMA", "KERNEL_A1_IL", "KERNEL_WN_REG", "ABI_SYMBOLS", "ModelBank",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "nam_hip_batch_debug_timeline",
     "nam_hip_model_load_parts", "nam_hip_model_get_string", "nam_hip_model_get_weights", "nam_hip_sample_rate_from_nam",
     "nam_hip_batch_kernel_name_for", "nam_hip_version_support", "nam_hip_device_count",
+    "nam_hip_bank_create", "nam_hip_bank_free", "nam_hip_bank_n_models", "nam_hip_batch_create_bank",
+    "nam_hip_batch_set_stream_model", "nam_hip_batch_get_stream_model",
 ]
 
 
@@ -159,6 +161,13 @@ def load_library():
     L.nam_hip_model_get_weights.restype = ctypes.c_int64
     L.nam_hip_version_support.argtypes = [ctypes.c_char_p]
     L.nam_hip_sample_rate_from_nam.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(cd)]
+    L.nam_hip_bank_create.argtypes = [ctypes.POINTER(vp), ci, ctypes.POINTER(vp)]
+    L.nam_hip_bank_free.argtypes = [vp]
+    L.nam_hip_bank_free.restype = None
+    L.nam_hip_bank_n_models.argtypes = [vp]
+    L.nam_hip_batch_create_bank.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
+    L.nam_hip_batch_set_stream_model.argtypes = [vp, ctypes.POINTER(ci), ci, ci]
+    L.nam_hip_batch_get_stream_model.argtypes = [vp, ci]
     _lib = L
     return L
 
@@ -277,17 +286,54 @@ class Model:
         return Batch(self, n_streams, max_frames, device)
 
 
+class ModelBank:
+    """An immutable set of loaded models one batch runs side by side, each stream bound to one member (include/nam_hip.h:
+    nam_hip_bank_create). Members must plan onto the same kernel instantiation: the official WaveNet topology (standard, lite,
+    feather), all loaded with the same ``fast_tanh``; anything else raises NamHipError(ERR_UNSUPPORTED) naming the member."""
+
+    def __init__(self, models: Sequence[Model]):
+        self._L = load_library()
+        self._h = None
+        self.models = list(models)
+        arr = (ctypes.c_void_p * max(len(self.models), 1))(*[m._h.value for m in self.models])
+        h = ctypes.c_void_p()
+        _check(self._L.nam_hip_bank_create(arr, len(self.models), ctypes.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.nam_hip_bank_free(self._h)
+            self._h = None
+
+    def __len__(self) -> int:
+        return _check(self._L.nam_hip_bank_n_models(self._h))
+
+    def batch(self, n_streams: int, max_frames: int = 64, device: int = 0, stream_model: Optional[Sequence[int]] = None) -> "Batch":
+        """A batch whose stream s runs member stream_model[s] (None: every stream member 0)."""
+        return Batch(self.models[0], n_streams, max_frames, device, bank=self, stream_model=stream_model)
+
+
 class Batch:
     """N independent streams of one model on one GPU (replaces N ``nam::DSP`` instances)."""
 
-    def __init__(self, model: Model, n_streams: int, max_frames: int, device: int = 0):
+    def __init__(self, model: Model, n_streams: int, max_frames: int, device: int = 0, bank: Optional["ModelBank"] = None,
+                 stream_model: Optional[Sequence[int]] = None):
         self._L = load_library()
-        self.model = model
+        self.model = model  # (a bank batch: member 0 — channel counts and the other getters are the same for every member)
+        self.bank = bank
         self.n_streams = int(n_streams)
         self.max_frames = int(max_frames)
         self.device = int(device)
         h = ctypes.c_void_p()
-        _check(self._L.nam_hip_batch_create(model._h, device, n_streams, max_frames, ctypes.byref(h)))
+        if bank is None:
+            _check(self._L.nam_hip_batch_create(model._h, device, n_streams, max_frames, ctypes.byref(h)))
+        else:
+            arr = None
+            if stream_model is not None:
+                if len(stream_model) != self.n_streams:
+                    raise ValueError(f"stream_model needs one member index per stream ({self.n_streams}), got {len(stream_model)}")
+                arr = (ctypes.c_int * self.n_streams)(*[int(m) for m in stream_model])
+            _check(self._L.nam_hip_batch_create_bank(bank._h, device, n_streams, max_frames, arr, ctypes.byref(h)))
         self._h = h
         self._ticket_frames = {}  # ticket -> n_frames of the buffers in flight (submit / wait)
 
@@ -311,6 +357,19 @@ class Batch:
         else:
             arr = (ctypes.c_int * len(stream_ids))(*[int(s) for s in stream_ids])
             _check(self._L.nam_hip_batch_set_slimmable_size(self._h, arr, len(stream_ids), float(ratio)))
+
+    def set_stream_model(self, member: int, stream_ids: Optional[Sequence[int]] = None):
+        """Bank batches: bind the listed streams (None: all) to bank member ``member``; they start from a freshly reset (and, if
+        the batch was last reset with prewarm, prewarmed) state of that member, every other stream is untouched."""
+        if stream_ids is None:
+            _check(self._L.nam_hip_batch_set_stream_model(self._h, None, 0, int(member)))
+        else:
+            arr = (ctypes.c_int * len(stream_ids))(*[int(s) for s in stream_ids])
+            _check(self._L.nam_hip_batch_set_stream_model(self._h, arr, len(stream_ids), int(member)))
+
+    def stream_model(self, stream: int) -> int:
+        """The bank member ``stream`` runs (0 for a one-model batch)."""
+        return _check(self._L.nam_hip_batch_get_stream_model(self._h, int(stream)))
 
     def set_kernel(self, kernel: int):
         _check(self._L.nam_hip_batch_set_kernel(self._h, int(kernel)))

@@ -1,0 +1,224 @@
+// api_bank.cpp — model banks (include/nam_hip.h: nam_hip_bank_create, nam_hip_batch_create_bank): which models may share a
+// batch, the bank's host image, a bank batch's device image and the per-stream member binding. See api_internal.h.
+//
+// What a bank holds per member is the part of the plan's blob the interleaved-frame kernels read — from A1Plan::ws_tiles_off to
+// the end: tiles | extra tiles | constants | rechannel column | nam_a1_q_kernel's weight block — and the two scalars they take
+// by value (head_scale, act_p0). In front of that region a plan keeps the op program's weights in the model's OWN channel
+// counts, so the region starts at another offset in a lite or feather model than in a standard one; inside it the layout is
+// the padded 16 / 8 topology's and the same for every member. The launch arguments of a bank batch are therefore offsets from
+// the region's start (launch_group), and the comparison below is made on those.
+#include "api_internal.h"
+
+namespace namhip
+{
+namespace api
+{
+namespace
+{
+// Why `p` cannot be a bank member at all ("" = it can): the family is nam_a1_q_kernel's — the official topology at 16 / 8
+// (padded) channels with Tanh or Fasttanh — and its siblings' instantiations for that shape.
+std::string member_refusal(const nam_hip_model& m)
+{
+  const ModelSpec& s = *m.spec;
+  if (s.arch == ARCH_LSTM)
+    return "an LSTM (banks hold WaveNets of the official topology)";
+  if (s.arch == ARCH_CONTAINER)
+    return "a SlimmableContainer (banks hold plain WaveNets of the official topology)";
+  if (m.slimmable())
+    return "a slimmable WaveNet (its widths are separate plans; banks hold one plan per member)";
+  const Plan& p = m.plans[m.full_width];
+  const A1Plan& a = p.a1;
+  if (!a.valid)
+    return "outside the A1 kernel family (FiLM / gating / groups / a lookup-table or per-channel activation / a post-stack head ...)";
+  if (!(a.il_ok && a.p2_ok && a.q_ok && a.p2_c0 == 16 && a.p2_c1 == 8))
+    return "not the official WaveNet topology at (padded) 16 / 8 channels with Tanh or Fasttanh: no nam_a1_q_kernel plan (q_ok / p2_c0 / "
+           "p2_c1)";
+  if (!a1_q_takes(a.arr[0].act))
+    return "an activation nam_a1_q_kernel is not compiled for (arr[0].act)";
+  if (a.ws_tiles_off % 4 != 0 || a.ws_consts_off < a.ws_tiles_off || a.ws_xt_off < a.ws_tiles_off || a.q_w_off < a.ws_tiles_off
+      || (size_t)a.ws_tiles_off >= p.blob.size())
+    return "a blob layout whose kernel region does not start at its tile area (ws_tiles_off)";
+  return "";
+}
+
+// The first field in which member `p` differs from member 0 (`q`), "" when the two run as one launch.
+std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m)
+{
+  const Plan& q = m0.plans[m0.full_width];
+  const Plan& p = m.plans[m.full_width];
+  const A1Plan& a = p.a1;
+  const A1Plan& b = q.a1;
+  std::string out;
+  auto cmp = [&](const char* field, long long x, long long y) {
+    if (out.empty() && x != y)
+      out = std::string(field) + " (" + std::to_string(x) + " vs " + std::to_string(y) + ")";
+  };
+  cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
+  cmp("in_channels", p.in_channels, q.in_channels);
+  cmp("out_channels", p.out_channels, q.out_channels);
+  cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples);
+  cmp("state_floats", p.state_floats, q.state_floats);
+  cmp("a1.n_arrays", a.n_arrays, b.n_arrays);
+  cmp("a1.n_rings", a.n_rings, b.n_rings);
+  for (int r = 0; r < 64 && r < a.n_rings; r++)
+    cmp("a1.ring_len_by_id", a.ring_len_by_id[r], b.ring_len_by_id[r]);
+  for (int i = 0; i < a.n_arrays && i < kA1MaxArrays; i++)
+  {
+    const A1Array &x = a.arr[i], &y = b.arr[i];
+    cmp("a1.arr.act (ACT_T)", x.act, y.act);
+    cmp("a1.arr.channels", x.channels, y.channels);
+    cmp("a1.arr.kernel", x.kernel, y.kernel);
+    cmp("a1.arr.n_layers", x.n_layers, y.n_layers);
+    cmp("a1.arr.head_size", x.head_size, y.head_size);
+    for (int l = 0; l < x.n_layers && l < kA1MaxLayers; l++)
+    {
+      cmp("a1.arr.dil", x.dil[l], y.dil[l]);
+      cmp("a1.arr.ring_off", x.ring_off[l], y.ring_off[l]);
+      cmp("a1.arr.ring_len", x.ring_len[l], y.ring_len[l]);
+      cmp("a1.arr.ring_id", x.ring_id[l], y.ring_id[l]);
+    }
+  }
+  cmp("a1.p2_c0", a.p2_c0, b.p2_c0);
+  cmp("a1.p2_c1", a.p2_c1, b.p2_c1);
+  // the launch arguments, as offsets from the kernel region's start (see the head of this file)
+  cmp("blob floats behind ws_tiles_off", (long long)p.blob.size() - a.ws_tiles_off, (long long)q.blob.size() - b.ws_tiles_off);
+  cmp("consts_off (ws_consts_off - ws_tiles_off)", a.ws_consts_off - a.ws_tiles_off, b.ws_consts_off - b.ws_tiles_off);
+  cmp("xt_off (ws_xt_off - ws_tiles_off)", a.ws_xt_off - a.ws_tiles_off, b.ws_xt_off - b.ws_tiles_off);
+  cmp("n_xt (ws_n_xt)", a.ws_n_xt, b.ws_n_xt);
+  cmp("q_w_off - ws_tiles_off", a.q_w_off - a.ws_tiles_off, b.q_w_off - b.ws_tiles_off);
+  cmp("il_jobs", a.il_jobs, b.il_jobs);
+  cmp("il_real_jobs", a.il_real_jobs, b.il_real_jobs);
+  cmp("il_depth", a.il_depth, b.il_depth);
+  cmp("il_exch", a.il_exch, b.il_exch);
+  cmp("il_consts_b", a.il_consts_b, b.il_consts_b);
+  cmp("il_xt_b", a.il_xt_b, b.il_xt_b);
+  cmp("il_tiles_b", a.il_tiles_b, b.il_tiles_b);
+  cmp("il_flag_b", a.il_flag_b, b.il_flag_b);
+  cmp("il_lds_bytes", a.il_lds_bytes, b.il_lds_bytes);
+  return out;
+}
+} // namespace
+
+// The device image of a bank batch's one group (instead of upload_group): every member's kernel region in ONE allocation, the
+// per-member scalars, the per-stream member index.
+int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
+{
+  const nam_hip_bank_data& bank = *b->bank;
+  const Plan& p = *g.plan;
+  NAM_HIP_CHECK(hipMalloc(&g.d_blob, bank.blobs.size() * sizeof(float)));
+  NAM_HIP_CHECK(hipMemcpy(g.d_blob, bank.blobs.data(), bank.blobs.size() * sizeof(float), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(hipMalloc(&g.d_a1, sizeof(A1Plan)));
+  NAM_HIP_CHECK(hipMemcpy(g.d_a1, &p.a1, sizeof(A1Plan), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(hipMalloc(&g.d_bank_scal, bank.scal.size() * sizeof(float)));
+  NAM_HIP_CHECK(hipMemcpy(g.d_bank_scal, bank.scal.data(), bank.scal.size() * sizeof(float), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(hipMalloc(&g.d_bank_member, (size_t)b->n_streams * sizeof(int)));
+  NAM_HIP_CHECK(hipMemcpy(g.d_bank_member, b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
+  g.bank_stride = bank.blob_stride;
+  g.state_stride = p.state_floats;
+  return NAM_HIP_OK;
+}
+
+// nam_hip_batch_set_stream_model behind its argument checks; the order of operations is nam_hip_batch_set_slimmable_size's.
+int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, int member)
+{
+  std::vector<int> ids;
+  if (!stream_ids)
+  {
+    ids.resize(b->n_streams);
+    for (int i = 0; i < b->n_streams; i++)
+      ids[i] = i;
+  }
+  else
+    for (int i = 0; i < n_ids; i++)
+    {
+      if (stream_ids[i] < 0 || stream_ids[i] >= b->n_streams)
+        return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_model: stream id out of range");
+      ids.push_back(stream_ids[i]);
+    }
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  std::vector<int> moved;
+  for (int s : ids)
+    if (b->stream_member[s] != member)
+      moved.push_back(s);
+  if (moved.empty())
+    return NAM_HIP_OK;
+  NAM_HIP_CHECK(quiesce(b)); // (a resident launch holds its members' weights since its prologue: it ends here)
+  WidthGroup& g = b->groups[b->model->full_width];
+  for (int s : moved)
+    b->stream_member[s] = member;
+  NAM_HIP_CHECK(hipMemcpy(g.d_bank_member, b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
+  // fresh state of the new member for the streams that moved: Reset (+ prewarm), every other stream untouched
+  int* d_moved = nullptr;
+  NAM_HIP_CHECK(hipMalloc(&d_moved, moved.size() * sizeof(int)));
+  NAM_HIP_CHECK(hipMemcpy(d_moved, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice));
+  const int rc = reset_streams(b, g, d_moved, (int)moved.size(), b->was_reset && b->reset_with_prewarm, -1);
+  const hipError_t e = hipStreamSynchronize(b->stream);
+  (void)hipFree(d_moved);
+  if (rc != NAM_HIP_OK)
+    return rc;
+  NAM_HIP_CHECK(e);
+  return NAM_HIP_OK;
+}
+
+} // namespace api
+} // namespace namhip
+
+extern "C" {
+
+int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hip_bank** out_bank)
+{
+  if (!models || !out_bank || n_models <= 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_bank_create: bad argument (models, out_bank, n_models >= 1)");
+  *out_bank = nullptr;
+  for (int i = 0; i < n_models; i++)
+    if (!models[i])
+      return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_bank_create: member " + std::to_string(i) + " is NULL");
+  return guarded([&]() -> int {
+    for (int i = 0; i < n_models; i++)
+    {
+      const std::string why = member_refusal(*models[i]);
+      if (!why.empty())
+        return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_bank_create: member " + std::to_string(i) + " is " + why);
+      const std::string diff = i ? first_difference(*models[0], *models[i]) : std::string();
+      if (!diff.empty())
+        return fail(NAM_HIP_ERR_UNSUPPORTED,
+                    "nam_hip_bank_create: member " + std::to_string(i) + " differs from member 0 in " + diff);
+    }
+    auto data = std::make_shared<nam_hip_bank_data>();
+    const nam_hip_model& m0 = *models[0];
+    data->proto.spec = m0.spec;
+    data->proto.plans.push_back(m0.plans[m0.full_width]);
+    data->proto.width_channels.push_back({});
+    data->proto.full_width = 0;
+    data->n_members = n_models;
+    const Plan& p0 = m0.plans[m0.full_width];
+    const size_t region = p0.blob.size() - (size_t)p0.a1.ws_tiles_off;
+    data->blob_stride = (long)((region + 3) / 4 * 4);
+    data->blobs.assign((size_t)n_models * (size_t)data->blob_stride, 0.f);
+    data->scal.resize((size_t)n_models * 2);
+    for (int i = 0; i < n_models; i++)
+    {
+      const Plan& p = models[i]->plans[models[i]->full_width];
+      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + p.a1.ws_tiles_off, region * sizeof(float));
+      data->scal[2 * (size_t)i] = p.blob[(size_t)p.a1.head_scale_off];
+      data->scal[2 * (size_t)i + 1] = p.a1.arr[0].act_p0;
+    }
+    nam_hip_bank* bank = new nam_hip_bank();
+    bank->data = std::move(data);
+    *out_bank = bank;
+    return NAM_HIP_OK;
+  });
+}
+
+void nam_hip_bank_free(nam_hip_bank* bank)
+{
+  delete bank;
+}
+
+int nam_hip_bank_n_models(const nam_hip_bank* bank)
+{
+  return bank ? bank->data->n_members : NAM_HIP_ERR_INVALID_ARGUMENT;
+}
+
+} // extern "C"

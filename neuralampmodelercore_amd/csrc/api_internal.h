@@ -4,6 +4,7 @@
 //   api_launch.cpp    model -> plans -> device blobs; which kernel a launch runs and its arguments; Reset / prewarm
 //   api_session.cpp   persistent block mode: the resident launch, its command ring, completion, the watchdog
 //   api_host_io.cpp   host buffers: the windows both sides can reach, blocking calls through a session, tickets
+//   api_bank.cpp      model banks: which models may share a batch, the bank's device image, per-stream member binding
 // No exception leaves these files (guarded); errors are codes + nam_hip_last_error.
 #pragma once
 #include "../../include/nam_hip.h"
@@ -91,6 +92,23 @@ struct nam_hip_model
   }
 };
 
+// A model bank (nam_hip_bank_create): models that plan onto ONE instantiation of the interleaved-frame kernels (nam_a1_q_kernel
+// and its siblings) with the same blob layout, so that one launch can run them side by side, each workgroup on its stream's
+// member. Immutable host data, self-contained (nothing of the member models is referenced after creation); a batch created
+// from it shares ownership of `data`, so the handle may be freed while batches live.
+struct nam_hip_bank_data
+{
+  nam_hip_model proto; // member 0's spec and full-size plan: everything a batch asks its model that is not a weight
+  int n_members = 0;
+  long blob_stride = 0; // floats per member in `blobs`: the plan's blob size rounded up to a multiple of four (16-byte records)
+  std::vector<float> blobs; // [n_members][blob_stride]
+  std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal)
+};
+struct nam_hip_bank
+{
+  std::shared_ptr<const nam_hip_bank_data> data;
+};
+
 namespace namhip
 {
 namespace api
@@ -119,6 +137,12 @@ struct WidthGroup
   // the silence again.
   float* d_prewarm = nullptr;
   int prewarm_kernel = -1, prewarm_len = 0;
+  // a bank batch's one group (api_bank.cpp): d_blob holds [members][bank_stride] floats, and the kernels pick a stream's member
+  // through d_bank_member[stream] (indexed by STREAM, not by launch position) and its scalars from d_bank_scal[2 member].
+  // No prewarm cache: a member's prewarmed state depends on its weights, so a Reset runs the silence for every stream.
+  int* d_bank_member = nullptr;
+  float* d_bank_scal = nullptr;
+  long bank_stride = 0;
 };
 
 // Persistent block mode (nam_hip_batch_set_persistent): one resident launch of nam_a1_p2_kernel per session, fed one
@@ -212,7 +236,9 @@ struct PipeSlot
 
 struct nam_hip_batch
 {
-  const nam_hip_model* model = nullptr;
+  const nam_hip_model* model = nullptr; // (a bank batch: &bank->proto)
+  std::shared_ptr<const nam_hip_bank_data> bank; // nam_hip_batch_create_bank; nullptr = one model
+  std::vector<int> stream_member; // bank batches: member of every stream
   int device = 0;
   int n_streams = 0;
   int max_frames = 0;
@@ -332,6 +358,9 @@ void persist_free(nam_hip_batch* b);
 // api_launch.cpp
 void free_group(WidthGroup& g);
 int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out);
+// api_bank.cpp
+int upload_bank_group(nam_hip_batch* b, WidthGroup& g);
+int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, int member);
 // api_host_io.cpp
 bool host_windows(nam_hip_batch* b, int slots, float*& in_bar, float*& h_out_map, float*& d_out_map, bool& failed, bool prealloc = false);
 bool host_mapped_applies(nam_hip_batch* b, int n_frames);

@@ -97,6 +97,8 @@ constexpr size_t kKtAutoMaxStreams = 1024;
 
 int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
 {
+  if (g.d_bank_member) // a model bank: the interleaved-frame family for every launch shape (the other kernels know no banks)
+    return NAM_HIP_KERNEL_A1_IL;
   const bool a1 = g.plan->a1.valid && g.d_a1;
   const bool mfma = a1 && (g.plan->a1.ws_ok || g.plan->a1.kt_ok);
   const bool il = a1 && g.plan->a1.il_ok && g.plan->a1.p2_ok; // the interleaved-frame kernels: the official topologies (compile-time job tables)
@@ -507,15 +509,22 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
       a.p_cmd_count = a.p_cmd_done = nullptr;
       a.p_seq0 = -1;
       a.p_cmd0 = 0;
+      a.bank_member = g.d_bank_member;
+      a.bank_scal = g.d_bank_scal;
+      a.bank_stride = g.bank_stride;
+      if (g.d_bank_member && kernel != NAM_HIP_KERNEL_A1_IL)
+        return fail(NAM_HIP_ERR_UNSUPPORTED, "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank");
       if (kernel == NAM_HIP_KERNEL_A1_IL)
       {
         int act = p.a1.arr[0].act;
         for (int i = 1; i < p.a1.n_arrays; i++)
           if (p.a1.arr[i].act != act)
             act = -1;
-        a.tiles_off = p.a1.ws_tiles_off;
-        a.consts_off = p.a1.ws_consts_off;
-        a.xt_off = p.a1.ws_xt_off;
+        // a bank's rows start at the kernels' region of the blob (api_bank.cpp): offsets from there
+        const int base = g.d_bank_member ? p.a1.ws_tiles_off : 0;
+        a.tiles_off = p.a1.ws_tiles_off - base;
+        a.consts_off = p.a1.ws_consts_off - base;
+        a.xt_off = p.a1.ws_xt_off - base;
         a.n_xt = p.a1.ws_n_xt;
         a.il_jobs = p.a1.il_jobs;
         a.il_real_jobs = p.a1.il_real_jobs;
@@ -548,8 +557,8 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
         {
           // the 16 / 8 topology as twelve one-wave stages, most rings resident in LDS (kernel_a1_q.hip): its own weight block
           // + the FULL-layout tiles of array 0 (kept in registers)
-          a.consts_off = p.a1.ws_tiles_off;
-          a.tiles_off = p.a1.q_w_off;
+          a.consts_off = p.a1.ws_tiles_off - base;
+          a.tiles_off = p.a1.q_w_off - base;
           NAM_HIP_CHECK(launch_a1_q(a, n, act, s));
         }
         else if (use_pipeline(b, n_frames))
@@ -755,7 +764,7 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
     const int rc = launch_group(b, g, d_map, n, nullptr, nullptr, frames, 0, b->stream);
     if (rc != NAM_HIP_OK)
       return rc;
-    if (p.arch == ARCH_WAVENET && first_stream >= 0)
+    if (p.arch == ARCH_WAVENET && first_stream >= 0 && !g.d_bank_member) // (a bank's prewarmed state depends on the member: no cache)
     {
       if (!g.d_prewarm)
         NAM_HIP_CHECK(hipMalloc(&g.d_prewarm, (size_t)p.state_floats * sizeof(float)));
@@ -789,6 +798,10 @@ void free_group(WidthGroup& g)
     (void)hipFree(g.d_map);
   if (g.d_prewarm)
     (void)hipFree(g.d_prewarm);
+  if (g.d_bank_member)
+    (void)hipFree(g.d_bank_member);
+  if (g.d_bank_scal)
+    (void)hipFree(g.d_bank_scal);
   g = WidthGroup();
 }
 

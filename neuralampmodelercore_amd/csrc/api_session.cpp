@@ -393,7 +393,7 @@ static int persist_prepare_alloc(nam_hip_batch* b)
     const WidthGroup& g0 = b->groups[b->model->full_width];
     if (g0.plan->arch == ARCH_WAVENET && g0.plan->a1.valid && g0.plan->a1.p2_ok && q_runs(b, *g0.plan))
       for (int oh = 0; oh < 2; oh++)
-        NAM_HIP_CHECK(preload_a1_p4_session(g0.plan->a1.p2_c0, g0.plan->a1.p2_c1, g0.plan->a1.arr[0].act, oh != 0));
+        NAM_HIP_CHECK(preload_a1_p4_session(g0.plan->a1.p2_c0, g0.plan->a1.p2_c1, g0.plan->a1.arr[0].act, oh != 0, g0.d_bank_member != nullptr));
   }
   return NAM_HIP_OK;
 }

@@ -57,6 +57,28 @@ __device__ __forceinline__ void for_each_index(F&& f, std::integer_sequence<int,
 {
   (f(std::integral_constant<int, I>{}), ...);
 }
+
+// What a workgroup reads its weights and per-model scalars from. BANK (a model bank: A1Args::bank_member): the stream's member is
+// resolved once, wave-uniformly (scalar loads), right after the stream itself; nothing behind the prologue depends on it.
+// !BANK: the launch's one model, straight from the kernel arguments — the code of those instantiations does not change.
+struct Weights
+{
+  const float* blob;
+  float head_scale, act_p0;
+};
+template <bool BANK>
+__device__ __forceinline__ Weights weights_of(const float* __restrict__ blob, const A1Args& a, int stream)
+{
+  if constexpr (BANK)
+  {
+    const int m = uni(a.bank_member[stream]);
+    const float* sc = a.bank_scal + 2 * m;
+    return Weights{blob + (size_t)m * (size_t)a.bank_stride, __builtin_bit_cast(float, uni(__builtin_bit_cast(int, sc[0]))),
+                   __builtin_bit_cast(float, uni(__builtin_bit_cast(int, sc[1])))};
+  }
+  else
+    return Weights{blob, a.head_scale, a.act_p0};
+}
 } // namespace il
 
 // A session launch waits for command `tag` (ring slot of sequence number tag - 1; `v` = what the slot held at the last look) for

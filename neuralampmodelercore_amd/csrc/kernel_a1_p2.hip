@@ -29,8 +29,9 @@ namespace namhip
 // buffers rung so far are done; the host starts the next launch with the next doorbell. While doorbells arrive faster
 // than blocks are computed (3-6 us vs 10 us) a whole run of buffers is one launch: dispatch, kernarg and
 // write-position round trips, weights into LDS and the write-through drain are paid once per run, not per buffer.
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST>
-__global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict__ blob, const A1Args a)
+// BANK: the streams run the members of a model bank (il_common.h: weights_of).
+template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, bool BANK = false>
+__global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict__ blob0, const A1Args a)
 {
   using namespace mf;
   using il::kOob;
@@ -42,6 +43,8 @@ __global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict_
   const int lane = tid & 63;
   const int w = uni(tid >> 6);
   const int stream = a.stream_map ? a.stream_map[blockIdx.x] : (int)blockIdx.x;
+  const il::Weights wsrc = il::weights_of<BANK>(blob0, a, stream);
+  const float* __restrict__ blob = wsrc.blob;
   float* st = a.state + (size_t)stream * a.state_stride;
   const int n_blocks = PERSIST ? (1 << 30) : (a.n_frames + kBlock - 1) / kBlock;
 
@@ -50,8 +53,8 @@ __global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict_
   const int t = 4 * j + w; // this lane's frame inside the block
   const float* in = a.in ? a.in + (size_t)stream * a.io_stride : nullptr;
   float* out = a.out ? a.out + (size_t)stream * a.io_stride : nullptr;
-  const float head_scale = a.head_scale;
-  const float act_p0 = a.act_p0;
+  const float head_scale = wsrc.head_scale;
+  const float act_p0 = wsrc.act_p0;
   const unsigned v_g16 = (unsigned)g * 16u;
   const unsigned v_gh8 = (unsigned)(g & 1) * 16u + (unsigned)(g >> 1) * 8u;
   const unsigned v_lane16 = (unsigned)lane * 16u;
@@ -478,15 +481,24 @@ __global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict_
 
 namespace
 {
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST = false>
+template <int C0, int C1, int ACT_T, bool WT, bool PERSIST = false, bool BANK = false>
 hipError_t launch_p2_inst(const A1Args& a, int n_blocks, hipStream_t stream)
 {
   static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST>), p2::kLdsBytes);
+  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST, BANK>), p2::kLdsBytes);
   if (e != hipSuccess)
     return e;
-  nam_launch((nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST>), dim3(n_blocks), dim3(256), p2::kLdsBytes, stream, a.blob, a);
+  nam_launch((nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST, BANK>), dim3(n_blocks), dim3(256), p2::kLdsBytes, stream, a.blob, a);
   return hipGetLastError();
+}
+// a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
+template <int ACT_T>
+hipError_t launch_p2_bank(const A1Args& a, int n_blocks, hipStream_t stream)
+{
+  if (a.p_ring)
+    return launch_p2_inst<16, 8, ACT_T, false, true, true>(a, n_blocks, stream);
+  const bool wt = a.n_frames <= 2 * kBlock;
+  return wt ? launch_p2_inst<16, 8, ACT_T, true, false, true>(a, n_blocks, stream) : launch_p2_inst<16, 8, ACT_T, false, false, true>(a, n_blocks, stream);
 }
 template <int C0, int C1>
 hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, hipStream_t stream)
@@ -512,6 +524,12 @@ hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, hipStream_t s
 
 hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream)
 {
+  if (a.bank_member)
+  {
+    if (c0 != 16 || c1 != 8 || (act != ACT_FASTTANH && act != ACT_TANH))
+      return hipErrorInvalidValue;
+    return act == ACT_FASTTANH ? launch_p2_bank<ACT_FASTTANH>(a, n_blocks, stream) : launch_p2_bank<ACT_TANH>(a, n_blocks, stream);
+  }
   if (c0 == 16 && c1 == 8)
     return launch_p2_shape<16, 8>(a, n_blocks, act, stream);
   if (c0 == 12 && c1 == 8)

@@ -103,8 +103,9 @@ constexpr bool exchange_pairs_ok(int nst)
 }
 } // namespace p4
 
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, int NST>
-__global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __restrict__ blob, const A1Args a)
+// BANK: the streams run the members of a model bank (il_common.h: weights_of).
+template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, int NST, bool BANK = false>
+__global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __restrict__ blob0, const A1Args a)
 {
   using namespace mf;
   using il::kOob;
@@ -119,6 +120,8 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
   const int S = wall >> 2; // stage
   const int w = wall & 3;
   const int stream = a.stream_map ? a.stream_map[blockIdx.x] : (int)blockIdx.x;
+  const il::Weights wsrc = il::weights_of<BANK>(blob0, a, stream);
+  const float* __restrict__ blob = wsrc.blob;
   float* st = a.state + (size_t)stream * a.state_stride;
   const int n_blocks = PERSIST ? (1 << 30) : (a.n_frames + kBlock - 1) / kBlock;
 
@@ -127,8 +130,8 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
   const int t = 4 * j + w; // this lane's frame inside the block
   const float* in = a.in ? a.in + (size_t)stream * a.io_stride : nullptr;
   float* out = a.out ? a.out + (size_t)stream * a.io_stride : nullptr;
-  const float head_scale = a.head_scale;
-  const float act_p0 = a.act_p0;
+  const float head_scale = wsrc.head_scale;
+  const float act_p0 = wsrc.act_p0;
   const unsigned v_g16 = (unsigned)g * 16u;
   const unsigned v_gh8 = (unsigned)(g & 1) * 16u + (unsigned)(g >> 1) * 8u;
   const unsigned v_lane16 = (unsigned)lane * 16u;
@@ -752,22 +755,31 @@ namespace
 constexpr int kP4Stages = NAM_P4_STAGES;
 
 // the instantiation's code object on the device and its dynamic-LDS limit raised (what the first launch would otherwise pay: ~1.6 ms)
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST>
+template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, bool BANK = false>
 hipError_t p4_ready()
 {
   static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  return lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_p4_kernel<C0, C1, ACT_T, WT, PERSIST, kP4Stages>), p4::lds_bytes(kP4Stages));
+  return lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_p4_kernel<C0, C1, ACT_T, WT, PERSIST, kP4Stages, BANK>), p4::lds_bytes(kP4Stages));
 }
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST = false>
+template <int C0, int C1, int ACT_T, bool WT, bool PERSIST = false, bool BANK = false>
 hipError_t launch_p4_inst(const A1Args& a, int n_blocks, hipStream_t stream)
 {
   constexpr int lds_bytes = p4::lds_bytes(kP4Stages);
-  const hipError_t e = p4_ready<C0, C1, ACT_T, WT, PERSIST>();
+  const hipError_t e = p4_ready<C0, C1, ACT_T, WT, PERSIST, BANK>();
   if (e != hipSuccess)
     return e;
-  nam_launch((nam_a1_p4_kernel<C0, C1, ACT_T, WT, PERSIST, kP4Stages>), dim3(n_blocks), dim3(kP4Stages * 256), lds_bytes, stream,
+  nam_launch((nam_a1_p4_kernel<C0, C1, ACT_T, WT, PERSIST, kP4Stages, BANK>), dim3(n_blocks), dim3(kP4Stages * 256), lds_bytes, stream,
                      a.blob, a);
   return hipGetLastError();
+}
+// a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
+template <int ACT_T>
+hipError_t launch_p4_bank(const A1Args& a, int n_blocks, hipStream_t stream)
+{
+  if (a.p_ring)
+    return a.p_out_host != 0 ? launch_p4_inst<16, 8, ACT_T, true, true, true>(a, n_blocks, stream) : launch_p4_inst<16, 8, ACT_T, false, true, true>(a, n_blocks, stream);
+  const bool wt = a.n_frames <= 2 * kBlock;
+  return wt ? launch_p4_inst<16, 8, ACT_T, true, false, true>(a, n_blocks, stream) : launch_p4_inst<16, 8, ACT_T, false, false, true>(a, n_blocks, stream);
 }
 template <int C0, int C1>
 hipError_t launch_p4_shape(const A1Args& a, int n_blocks, int act, hipStream_t stream)
@@ -792,10 +804,14 @@ hipError_t launch_p4_shape(const A1Args& a, int n_blocks, int act, hipStream_t s
 
 // A session of the 16 / 8 topology may switch to this kernel in the middle of a caller's real-time loop (api_launch.cpp:
 // PersistSession::short_bursts): its session instantiation is made ready when the session starts, not at the switch.
-hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host)
+hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host, bool bank)
 {
   if (c0 != 16 || c1 != 8)
     return hipSuccess;
+  if (bank && act == ACT_FASTTANH)
+    return out_host ? p4_ready<16, 8, ACT_FASTTANH, true, true, true>() : p4_ready<16, 8, ACT_FASTTANH, false, true, true>();
+  if (bank && act == ACT_TANH)
+    return out_host ? p4_ready<16, 8, ACT_TANH, true, true, true>() : p4_ready<16, 8, ACT_TANH, false, true, true>();
   if (act == ACT_FASTTANH)
     return out_host ? p4_ready<16, 8, ACT_FASTTANH, true, true>() : p4_ready<16, 8, ACT_FASTTANH, false, true>();
   if (act == ACT_TANH)
@@ -805,6 +821,12 @@ hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host)
 
 hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream)
 {
+  if (a.bank_member)
+  {
+    if (c0 != 16 || c1 != 8 || (act != ACT_FASTTANH && act != ACT_TANH))
+      return hipErrorInvalidValue;
+    return act == ACT_FASTTANH ? launch_p4_bank<ACT_FASTTANH>(a, n_blocks, stream) : launch_p4_bank<ACT_TANH>(a, n_blocks, stream);
+  }
   if (c0 == 16 && c1 == 8)
     return launch_p4_shape<16, 8>(a, n_blocks, act, stream);
   if (c0 == 12 && c1 == 8)

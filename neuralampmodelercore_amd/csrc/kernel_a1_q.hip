@@ -148,8 +148,9 @@ constexpr int max_far_small()
 // DBG: the profiling instantiation (A1Args::dbg, nam_hip_batch_debug_timeline): workgroup 0's stage s writes row s of the
 // buffer — shader-clock stamps at kernel entry, behind the prologue's barrier, at its first and last hand-over, behind its
 // write-back; the cycles it spent waiting for input and for its output slot; the buffers it processed.
-template <int ACT_T, bool WT, bool PERSIST, bool DBG = false>
-__global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __restrict__ blob, const A1Args a)
+// BANK: the streams run the members of a model bank (il_common.h: weights_of).
+template <int ACT_T, bool WT, bool PERSIST, bool DBG = false, bool BANK = false>
+__global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __restrict__ blob0, const A1Args a)
 {
   long long dbg_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if constexpr (DBG)
@@ -179,6 +180,8 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
   else if (wall >= 4)
     __builtin_amdgcn_s_setprio((short)1);
   const int stream = a.stream_map ? a.stream_map[blockIdx.x] : (int)blockIdx.x;
+  const il::Weights wsrc = il::weights_of<BANK>(blob0, a, stream);
+  const float* __restrict__ blob = wsrc.blob;
   float* st = a.state + (size_t)stream * a.state_stride;
   const int n_blocks = PERSIST ? (1 << 30) : (a.n_frames + kBlock - 1) / kBlock;
 
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
   const unsigned cls128 = (unsigned)(lane & 3) * 128u; // ... inside a 16 -> 8 tile
   const float* in = a.in ? a.in + (size_t)stream * a.io_stride : nullptr;
   float* out = a.out ? a.out + (size_t)stream * a.io_stride : nullptr;
-  const float head_scale = a.head_scale;
+  const float head_scale = wsrc.head_scale;
   const int io_bytes = PERSIST ? 0x7ffffff0 : a.n_frames * 4;
   const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc((void*)(in ? in : st), 0, in ? io_bytes : 0, 0x00020000);
   const auto rsrc_out = __builtin_amdgcn_make_buffer_rsrc((void*)(out ? out : st), 0, out ? io_bytes : 0, 0x00020000);
@@ -1107,23 +1110,29 @@ template __global__ void nam_a1_q_kernel<ACT_FASTTANH, false, true>(const float*
 #else
 namespace
 {
-template <int ACT_T, bool WT, bool PERSIST = false>
+template <int ACT_T, bool BANK, bool WT, bool PERSIST = false>
 hipError_t launch_q_inst(const A1Args& a, int n_blocks, hipStream_t stream)
 {
   static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_q_kernel<ACT_T, WT, PERSIST>), aq::kLdsBytes);
+  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_q_kernel<ACT_T, WT, PERSIST, false, BANK>), aq::kLdsBytes);
   if (e != hipSuccess)
     return e;
-  nam_launch((nam_a1_q_kernel<ACT_T, WT, PERSIST>), dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
+  nam_launch((nam_a1_q_kernel<ACT_T, WT, PERSIST, false, BANK>), dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
   return hipGetLastError();
+}
+template <int ACT_T, bool BANK>
+hipError_t launch_q_bank(const A1Args& a, int n_blocks, hipStream_t stream)
+{
+  if (a.p_ring) // persistent session (kernel_a1_p4.hip: launch_p4_shape)
+    return a.p_out_host != 0 ? launch_q_inst<ACT_T, BANK, true, true>(a, n_blocks, stream) : launch_q_inst<ACT_T, BANK, false, true>(a, n_blocks, stream);
+  const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through
+  return wt ? launch_q_inst<ACT_T, BANK, true>(a, n_blocks, stream) : launch_q_inst<ACT_T, BANK, false>(a, n_blocks, stream);
 }
 template <int ACT_T>
 hipError_t launch_q_act(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  if (a.p_ring) // persistent session (kernel_a1_p4.hip: launch_p4_shape)
-    return a.p_out_host != 0 ? launch_q_inst<ACT_T, true, true>(a, n_blocks, stream) : launch_q_inst<ACT_T, false, true>(a, n_blocks, stream);
-  const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through
-  return wt ? launch_q_inst<ACT_T, true>(a, n_blocks, stream) : launch_q_inst<ACT_T, false>(a, n_blocks, stream);
+  // a model bank (A1Args::bank_member) runs the BANK instantiations; one model keeps its own
+  return a.bank_member ? launch_q_bank<ACT_T, true>(a, n_blocks, stream) : launch_q_bank<ACT_T, false>(a, n_blocks, stream);
 }
 } // namespace
 
@@ -1135,7 +1144,7 @@ bool a1_q_takes(int act)
 }
 hipError_t launch_a1_q(const A1Args& a, int n_blocks, int act, hipStream_t stream)
 {
-  if (a.dbg && !a.p_ring) // developer tool (nam_hip_batch_debug_timeline): the stamped instantiation
+  if (a.dbg && !a.p_ring && !a.bank_member) // developer tool (nam_hip_batch_debug_timeline): the stamped instantiation
   {
     static DynamicLdsLimit lds_limit;
     const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_q_kernel<ACT_FASTTANH, false, false, true>), aq::kLdsBytes);

@@ -132,6 +132,13 @@ struct A1Args
   unsigned* p_cmd_count;
   unsigned* p_cmd_done;
   long long* dbg; // optional: per-job phase timestamps of workgroup 0 (profiling builds / tools only), else nullptr
+  // model bank (nam_hip_batch_create_bank; nam_a1_q_kernel, nam_a1_p4_kernel, nam_a1_p2_kernel — their BANK instantiations;
+  // nullptr = one model, the fields above): stream s runs member m = bank_member[s] of `blob` = [members][bank_stride] floats
+  // (a multiple of four: the kernels read 16-byte records), with head_scale = bank_scal[2 m] and act_p0 = bank_scal[2 m + 1].
+  // The offsets above are the same for every member (api_bank.cpp compares the plans). Read once, in the prologue.
+  const int* bank_member;
+  const float* bank_scal;
+  long bank_stride;
 };
 
 struct LSTMArgs
@@ -198,7 +205,7 @@ hipError_t launch_a1_mfma(const A1Args& a, int n_blocks, int act, hipStream_t st
 hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream);
 // nam_a1_p4_kernel: the same models as a pipeline of wave sets decoupled through LDS (kernel_a1_p4.hip)
 hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream);
-hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host); // (kernel_a1_p4.hip)
+hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host, bool bank = false); // (kernel_a1_p4.hip)
 // nam_a1_q_kernel (kernel_a1_q.hip): the 16 / 8 official topology (aq_table.h) as twelve one-wave stages with LDS-resident
 // rings; a.tiles_off = the plan's q weight block (A1Plan::q_w_off), a.consts_off = the FULL-layout tile area (ws_tiles_off)
 bool a1_q_takes(int act); // the activations it is compiled for (Fasttanh, Tanh)

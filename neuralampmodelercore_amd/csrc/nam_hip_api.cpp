@@ -49,7 +49,7 @@ int nam_hip_version_support(const char* nam_file_version)
 
 const char* nam_hip_version(void)
 {
-  return "nam_hip 0.2.1 gfx950"; // 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
+  return "nam_hip 0.2.2 gfx950"; // 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
 }
 
 int nam_hip_model_load(const char* nam_path, int fast_tanh, nam_hip_model** out_model)
@@ -293,12 +293,11 @@ int nam_hip_model_slimmable_breakpoints(const nam_hip_model* model, double* out,
   return (int)bp.size();
 }
 
-int nam_hip_batch_create(const nam_hip_model* model, int device, int n_streams, int max_frames,
-                         nam_hip_batch** out_batch)
+// nam_hip_batch_create and nam_hip_batch_create_bank (`bank` != nullptr: `model` is its proto, stream s runs member
+// stream_model[s], nullptr = member 0)
+static int create_batch(const nam_hip_model* model, std::shared_ptr<const nam_hip_bank_data> bank, const int* stream_model, int device,
+                        int n_streams, int max_frames, nam_hip_batch** out_batch)
 {
-  if (!model || !out_batch || n_streams <= 0 || max_frames <= 0)
-    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_create: bad argument");
-  *out_batch = nullptr;
   int count = 0;
   NAM_HIP_CHECK(hipGetDeviceCount(&count));
   if (device < 0 || device >= count)
@@ -308,6 +307,13 @@ int nam_hip_batch_create(const nam_hip_model* model, int device, int n_streams, 
   if (!b)
     return fail(NAM_HIP_ERR_DEVICE, "nam_hip_batch_create: out of host memory");
   b->model = model;
+  if (bank)
+  {
+    b->stream_member.assign((size_t)n_streams, 0);
+    for (int i = 0; stream_model && i < n_streams; i++)
+      b->stream_member[(size_t)i] = stream_model[i];
+    b->bank = std::move(bank);
+  }
   b->device = device;
   (void)hipDeviceGetAttribute(&b->n_cus, hipDeviceAttributeMultiprocessorCount, device);
   {
@@ -334,7 +340,7 @@ int nam_hip_batch_create(const nam_hip_model* model, int device, int n_streams, 
     for (size_t i = 0; i < model->plans.size(); i++)
     {
       b->groups[i].plan = &model->plans[i];
-      const int r = upload_group(b, b->groups[i]);
+      const int r = b->bank ? upload_bank_group(b, b->groups[i]) : upload_group(b, b->groups[i]);
       if (r != NAM_HIP_OK)
         return r;
     }
@@ -364,6 +370,50 @@ int nam_hip_batch_create(const nam_hip_model* model, int device, int n_streams, 
   }
   *out_batch = b;
   return NAM_HIP_OK;
+}
+
+int nam_hip_batch_create(const nam_hip_model* model, int device, int n_streams, int max_frames,
+                         nam_hip_batch** out_batch)
+{
+  if (!model || !out_batch || n_streams <= 0 || max_frames <= 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_create: bad argument");
+  *out_batch = nullptr;
+  return create_batch(model, nullptr, nullptr, device, n_streams, max_frames, out_batch);
+}
+
+int nam_hip_batch_create_bank(const nam_hip_bank* bank, int device, int n_streams, int max_frames, const int* stream_model,
+                              nam_hip_batch** out_batch)
+{
+  if (!bank || !out_batch || n_streams <= 0 || max_frames <= 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_create_bank: bad argument");
+  *out_batch = nullptr;
+  for (int i = 0; stream_model && i < n_streams; i++)
+    if (stream_model[i] < 0 || stream_model[i] >= bank->data->n_members)
+      return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_create_bank: stream " + std::to_string(i) + " names member "
+                                                  + std::to_string(stream_model[i]) + " of " + std::to_string(bank->data->n_members));
+  return guarded([&]() { return create_batch(&bank->data->proto, bank->data, stream_model, device, n_streams, max_frames, out_batch); });
+}
+
+int nam_hip_batch_set_stream_model(nam_hip_batch* batch, const int* stream_ids, int n_ids, int member)
+{
+  if (!batch || n_ids < 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_model: bad argument");
+  if (!batch->bank)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_model: the batch was not created from a bank");
+  if (member < 0 || member >= batch->bank->n_members)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_model: member " + std::to_string(member) + " out of range (the bank has "
+                                                + std::to_string(batch->bank->n_members) + ")");
+  return guarded([&]() -> int {
+    NAM_HIP_CHECK(hipSetDevice(batch->device));
+    return bank_set_stream_model(batch, stream_ids, n_ids, member);
+  });
+}
+
+int nam_hip_batch_get_stream_model(const nam_hip_batch* batch, int stream)
+{
+  if (!batch || stream < 0 || stream >= batch->n_streams)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_get_stream_model: bad argument");
+  return batch->bank ? batch->stream_member[(size_t)stream] : 0;
 }
 
 void nam_hip_batch_destroy(nam_hip_batch* batch)
@@ -800,6 +850,8 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
 {
   if (!batch || kernel < NAM_HIP_KERNEL_AUTO || kernel > NAM_HIP_KERNEL_WN_REG)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_kernel: bad argument");
+  if (batch->bank && kernel != NAM_HIP_KERNEL_AUTO && kernel != NAM_HIP_KERNEL_A1_IL)
+    return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)");
   NAM_HIP_CHECK(hipSetDevice(batch->device)); // (ending a session may relaunch: the launchers configure the current device)
   if (batch->ps.active)
   {
