@@ -325,6 +325,23 @@ struct WrGroupList
   int n = 0;
 };
 
+// Every __global__ function a group's launch can run. The public NAM_HIP_KERNEL_* values (include/nam_hip.h) name what a caller
+// may force, and pick_kernel / kernel_for_launch the family a group runs (the prewarm cache and the state layout key on those);
+// which function of the family a launch runs also depends on the launch: select_kernel.
+enum KernelFn : int
+{
+  FN_GENERIC, FN_WN_REG, FN_A1, FN_A1_MFMA, FN_KT_MFMA, FN_KQ, FN_A1_P2, FN_A1_P4, FN_A1_Q, // WaveNets
+  FN_LSTM, FN_LSTM_MFMA, FN_LSTM_MFMA_REG, FN_LSTM_ROW, FN_LSTM_WIDE,
+  KERNEL_FN_COUNT
+};
+// What select_kernel needs to know about a launch besides the batch and the group
+struct LaunchQuestion
+{
+  int n_frames; // the launch length
+  int session_kind; // PersistKind of the session whose resident launch this is; PERSIST_NONE: an ordinary launch
+  bool short_blocking_call; // a blocking host call of up to four buffers is being served (nam_hip_batch::short_blocking_call)
+};
+
 // api_launch.cpp
 int upload_group(nam_hip_batch* b, WidthGroup& g);
 int ensure_state(nam_hip_batch* b, WidthGroup& g);
@@ -371,14 +388,6 @@ int pipe_wait(nam_hip_batch* b, PipeSlot& sl, int slot, float* out);
 inline bool persist_eligible(const nam_hip_batch* b)
 {
   return persist_kind(b) != PERSIST_NONE;
-}
-
-// nam_a1_p4_kernel (the official topology as a pipeline of wave sets, consecutive buffers in flight at once) instead of
-// nam_a1_p2_kernel: whenever a launch holds more than one buffer — a persistent session, an offline render, a prewarm. A
-// launch of one block has nothing to overlap (every stage waits for the one before) and keeps the four-wave kernel.
-inline bool use_pipeline(const nam_hip_batch* b, int n_frames)
-{
-  return !b->no_pipe && (b->ps_launching || n_frames > kBlock);
 }
 
 // the official 16 / 8 topology's pipeline: nam_a1_q_kernel (one-wave stages, LDS-resident rings) for the activations it is compiled

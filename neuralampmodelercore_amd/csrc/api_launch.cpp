@@ -140,50 +140,6 @@ int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
   }
 }
 
-// Name of the __global__ function launch_group runs for this group (what rocprofv3 --kernel-trace reports, without
-// template arguments): lets callers attribute measurements to the right kernel.
-// `n_frames`: the launch length the question is about (under AUTO a launch of four or more blocks runs another kernel
-// of the family than a one-block launch); 64 in persistent mode means "a command of the session"
-const char* group_kernel_name(const nam_hip_batch* b, const WidthGroup& g, int n_frames)
-{
-  const Plan& p = *g.plan;
-  if (b->ps.enabled && n_frames == kBlock)
-    switch (persist_kind(b)) // persistent block mode
-    {
-      case PERSIST_A1_P2: // (what the NEXT launch of the session starts: PersistSession::short_bursts)
-        return b->no_pipe ? "nam_a1_p2_kernel" : (q_runs(b, p) && !(!b->pipe_session && b->ps.short_bursts())) ? "nam_a1_q_kernel" : "nam_a1_p4_kernel"; // (launch_group's own predicate: the burst history outlives a session)
-      case PERSIST_KQ: return "nam_kq_kernel";
-      case PERSIST_WN_REG: return "nam_wn_reg_kernel";
-      case PERSIST_LSTM_ROW: return "nam_lstm_row_kernel";
-      case PERSIST_LSTM_WIDE: return "nam_lstm_wide_kernel";
-      default: break;
-    }
-  if (p.arch == ARCH_WAVENET)
-  {
-    switch (kernel_for_launch(b, g, n_frames))
-    {
-      case NAM_HIP_KERNEL_GENERIC: return "nam_generic_kernel";
-      case NAM_HIP_KERNEL_WN_REG: return "nam_wn_reg_kernel";
-      case NAM_HIP_KERNEL_A1: return "nam_a1_kernel";
-      case NAM_HIP_KERNEL_A1_IL:
-        return (!b->no_pipe && n_frames > kBlock) ? (q_runs(b, p) ? "nam_a1_q_kernel" : "nam_a1_p4_kernel") : "nam_a1_p2_kernel";
-      default:
-        return p.a1.ws_ok ? "nam_a1_mfma_kernel" : (kq_runs(b, p) && !b->no_pipe && n_frames > kBlock) ? "nam_kq_kernel" : "nam_kt_mfma_kernel";
-    }
-  }
-  const LSTMPlan& L = p.lstm;
-  if (b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA && L.hidden >= 1 && L.hidden <= 4
-      && L.n_layers <= 2 && L.input_size >= 1 && L.input_size <= 2 && L.in_ch == L.input_size && L.out_ch <= 16)
-    return "nam_lstm_row_kernel";
-  if (b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA && L.hidden >= 5 && L.hidden <= 32
-      && L.n_layers <= 2 && L.input_size >= 1 && L.input_size <= 2 && L.in_ch == L.input_size && L.out_ch <= 16)
-    return "nam_lstm_wide_kernel";
-  if (L.mf_ok && b->kernel != NAM_HIP_KERNEL_GENERIC)
-    return (L.input_size <= 4 && L.n_layers <= 2 && L.mf_nt <= 6) ? "nam_lstm_mfma_reg_kernel" : "nam_lstm_mfma_kernel";
-  return "nam_lstm_kernel";
-}
-
-
 // the session's side of a persistent launch of a one-wavefront-per-workgroup kernel (kernels.h: PersistArgs)
 PersistArgs persist_args(const nam_hip_batch* b)
 {
@@ -199,6 +155,27 @@ PersistArgs persist_args(const nam_hip_batch* b)
   pa.cmd0 = b->ps.cmd0;
   pa.grace = b->ps.grace;
   return pa;
+}
+
+// ... and of the workgroup-per-stream kernels (nam_a1_q_kernel, nam_a1_p4_kernel, nam_a1_p2_kernel, nam_kq_kernel), which carry the
+// same words as A1Args::p_* plus where the results go and how long the launch lingers
+static void session_args(const nam_hip_batch* b, A1Args& a)
+{
+  if (!b->ps_launching)
+    return;
+  const PersistArgs pa = persist_args(b);
+  a.p_ring = pa.ring;
+  a.p_ring_mask = pa.ring_mask;
+  a.p_cons = pa.cons;
+  a.p_prog = pa.prog;
+  a.p_done = pa.done;
+  a.p_seq0 = pa.seq0;
+  a.p_cmd0 = pa.cmd0;
+  a.p_grace = pa.grace;
+  a.p_out_host = b->ps.out_is_host ? (b->ps.cmd_done_published ? 2 : 1) : 0;
+  a.p_linger = (b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus) ? session_linger_ticks(b) : 0; // (more workgroups than CUs take turns: the ones on the chip must leave when the ring is empty)
+  a.p_cmd_count = b->ps.d_cmd_count;
+  a.p_cmd_done = b->ps.d_cmd_done;
 }
 
 // The function of a per-model code object on the current device (hipModuleLoad is per device: cached per path and
@@ -453,6 +430,239 @@ int kernel_for_launch(const nam_hip_batch* b, const WidthGroup& g, int n_frames)
   return kernel;
 }
 
+// ... and of a launch in general: the resident launch of a session of the interleaved-frame family runs that family whatever a
+// one-buffer launch of the batch would (persist_kind: PERSIST_A1_P2 needs no more than AUTO and a model the family takes)
+static int family_for_launch(const nam_hip_batch* b, const WidthGroup& g, const LaunchQuestion& q)
+{
+  return q.session_kind == PERSIST_A1_P2 ? NAM_HIP_KERNEL_A1_IL : kernel_for_launch(b, g, q.n_frames);
+}
+
+// the functions as rocprofv3 --kernel-trace shows them, without template arguments (in KernelFn's order)
+static const char* const kKernelFnName[KERNEL_FN_COUNT] = {
+  "nam_generic_kernel", "nam_wn_reg_kernel", "nam_a1_kernel", "nam_a1_mfma_kernel", "nam_kt_mfma_kernel", "nam_kq_kernel",
+  "nam_a1_p2_kernel", "nam_a1_p4_kernel", "nam_a1_q_kernel", // WaveNets
+  "nam_lstm_kernel", "nam_lstm_mfma_kernel", "nam_lstm_mfma_reg_kernel", "nam_lstm_row_kernel", "nam_lstm_wide_kernel"};
+
+// Which __global__ function the group runs for the launch `q` describes: what launch_group launches and what
+// nam_hip_batch_kernel_name reports.
+static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const LaunchQuestion& q)
+{
+  const Plan& p = *g.plan;
+  const bool session = q.session_kind != PERSIST_NONE;
+  if (p.arch != ARCH_WAVENET)
+  {
+    // AUTO: small cells (hidden <= 4) one gate row per lane and four streams per wavefront, cells of 5 .. 32 units two
+    // gate rows per lane and one stream per wavefront, else the matrix-core kernel (16 streams per wavefront);
+    // NAM_HIP_KERNEL_A1_MFMA forces the matrix-core kernel; NAM_HIP_KERNEL_GENERIC: lanes = streams
+    const bool small = b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA;
+    if (small && lstm_row_eligible(p.lstm))
+      return FN_LSTM_ROW;
+    if (small && lstm_wide_eligible(p.lstm))
+      return FN_LSTM_WIDE;
+    if (p.lstm.mf_ok && b->kernel != NAM_HIP_KERNEL_GENERIC)
+      return lstm_mfma_in_registers(p.lstm) ? FN_LSTM_MFMA_REG : FN_LSTM_MFMA;
+    return FN_LSTM;
+  }
+  if (q.session_kind == PERSIST_WN_REG) // (one launch for every width group: launch_wr_all)
+    return FN_WN_REG;
+  // nam_a1_p4_kernel / nam_a1_q_kernel / nam_kq_kernel (pipelines, consecutive buffers in flight at once) instead of the
+  // one-buffer kernels: whenever a launch holds more than one buffer — a persistent session, an offline render, a prewarm. A
+  // launch of one block has nothing to overlap (every stage waits for the one before).
+  const bool pipeline = !b->no_pipe && (session || q.n_frames > kBlock);
+  switch (family_for_launch(b, g, q))
+  {
+    case NAM_HIP_KERNEL_GENERIC: return FN_GENERIC;
+    case NAM_HIP_KERNEL_WN_REG: return FN_WN_REG;
+    case NAM_HIP_KERNEL_A1: return FN_A1;
+    case NAM_HIP_KERNEL_A1_IL:
+      if (!pipeline) // one buffer: the four-wave kernel, job table compiled in
+        return FN_A1_P2;
+      // the 16 / 8 topology as twelve one-wave stages, most rings resident in LDS (kernel_a1_q.hip) — unless the caller waits for
+      // the FIRST buffer (nam_hip_batch::short_blocking_call; PersistSession::short_bursts, which ticket sessions never follow) —
+      // else as a pipeline of wave sets (three wavefronts per SIMD) across consecutive buffers
+      if (q_runs(b, p) && !q.short_blocking_call && !(session && !b->pipe_session && b->ps.short_bursts()))
+        return FN_A1_Q;
+      return FN_A1_P4;
+    default: // NAM_HIP_KERNEL_A1_MFMA
+      if (p.a1.ws_ok)
+        return FN_A1_MFMA;
+      // the K-tap kernel addresses the launch's input through a 32-bit buffer descriptor (1 GiB of float32 audio per
+      // stream and launch): longer launches take the VALU kernel, same state layout
+      if (q.n_frames > (1 << 28))
+        return FN_A1;
+      // the A2 topology with more than one buffer in the launch (a session, a render, a prewarm): the pipeline of one-wave
+      // stages compiled for it (kernel_kq.hip); same state as the K-tap kernel
+      if (kq_runs(b, p) && pipeline)
+        return FN_KQ;
+      return FN_KT_MFMA; // single-array models with other kernel sizes than 3 (A2): the K-tap MFMA kernel
+  }
+}
+
+// Name of the __global__ function launch_group runs for this group (what rocprofv3 --kernel-trace reports, without
+// template arguments): lets callers attribute measurements to the right kernel.
+// `n_frames`: the launch length the question is about (under AUTO a launch of four or more blocks runs another kernel
+// of the family than a one-block launch); 64 in persistent mode means "a command of the session" — answered for what the
+// NEXT launch of the session starts (PersistSession::short_bursts: the burst history outlives a session), outside any host call
+const char* group_kernel_name(const nam_hip_batch* b, const WidthGroup& g, int n_frames)
+{
+  const bool session_command = b->ps.enabled && n_frames == kBlock;
+  return kKernelFnName[select_kernel(b, g, LaunchQuestion{n_frames, session_command ? persist_kind(b) : (int)PERSIST_NONE, false})];
+}
+
+// what every kernel's argument block starts with (kernels.h): the group's weights and state, the launch's streams and audio
+template <typename Args>
+static void common_args(Args& a, const WidthGroup& g, const int* d_map, const float* d_in, float* d_out, int n_frames, long io_stride)
+{
+  a.blob = g.d_blob;
+  a.state = g.d_state;
+  a.state_stride = g.state_stride;
+  a.stream_map = d_map;
+  a.in = d_in;
+  a.out = d_out;
+  a.io_stride = io_stride;
+  a.n_frames = n_frames;
+}
+
+// the arrays' activation when it is uniform (a compile-time specialised kernel), else -1 (run-time dispatch)
+static int uniform_act(const A1Plan& a1)
+{
+  for (int i = 1; i < a1.n_arrays; i++)
+    if (a1.arr[i].act != a1.arr[0].act)
+      return -1;
+  return a1.arr[0].act;
+}
+
+static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args& a, int n, hipStream_t s)
+{
+  const Plan& p = *g.plan;
+  a.plan = g.d_a1;
+  a.act_p0 = p.a1.arr[0].act_p0; // uniform across arrays and layers for the A1 kernels (plan.cpp)
+  a.dbg = b->dbg;
+  if (b->ps_launching && b->ps.h_why)
+    a.dbg = b->ps.d_why; // (NAM_HIP_SESSION_STATS: why a lingering workgroup left — il_common.h: session_wait_command)
+  a.n_rings = p.a1.n_rings;
+  a.head_scale = p.blob[(size_t)p.a1.head_scale_off];
+  a.bank_member = g.d_bank_member;
+  a.bank_scal = g.d_bank_scal;
+  a.bank_stride = g.bank_stride;
+  const bool il = fn == FN_A1_P2 || fn == FN_A1_P4 || fn == FN_A1_Q;
+  if (g.d_bank_member && !il)
+    return fail(NAM_HIP_ERR_UNSUPPORTED, "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank");
+  if (il)
+  {
+    const int act = uniform_act(p.a1);
+    // a bank's rows start at the kernels' region of the blob (api_bank.cpp): offsets from there
+    const int base = g.d_bank_member ? p.a1.ws_tiles_off : 0;
+    a.tiles_off = p.a1.ws_tiles_off - base;
+    a.consts_off = p.a1.ws_consts_off - base;
+    a.xt_off = p.a1.ws_xt_off - base;
+    a.n_xt = p.a1.ws_n_xt;
+    a.il_jobs = p.a1.il_jobs;
+    a.il_real_jobs = p.a1.il_real_jobs;
+    a.il_depth = p.a1.il_depth;
+    a.il_exch = p.a1.il_exch;
+    a.il_consts_b = p.a1.il_consts_b;
+    a.il_xt_b = p.a1.il_xt_b;
+    a.il_tiles_b = p.a1.il_tiles_b;
+    a.il_flag_b = p.a1.il_flag_b;
+    a.il_lds_bytes = p.a1.il_lds_bytes;
+    a.act = act;
+    session_args(b, a);
+    if (!p.a1.p2_ok) // (pick_kernel: the interleaved-frame kernels exist for the official topologies' compile-time tables only)
+      return fail(NAM_HIP_ERR_UNSUPPORTED, "NAM_HIP_KERNEL_A1_IL: not one of the official topologies");
+    if (fn == FN_A1_Q)
+    {
+      // its own weight block + the FULL-layout tiles of array 0 (kept in registers)
+      a.consts_off = p.a1.ws_tiles_off - base;
+      a.tiles_off = p.a1.q_w_off - base;
+      NAM_HIP_CHECK(launch_a1_q(a, n, act, s));
+    }
+    else if (fn == FN_A1_P4)
+      NAM_HIP_CHECK(launch_a1_p4(a, n, p.a1.p2_c0, p.a1.p2_c1, act, s));
+    else
+      NAM_HIP_CHECK(launch_a1_p2(a, n, p.a1.p2_c0, p.a1.p2_c1, act, s));
+  }
+  else if (fn == FN_KQ)
+  {
+    a.tiles_off = p.a1.kq_w_off;
+    a.consts_off = p.a1.kt_lds_src_off;
+    a.r1_off = p.a1.kt_rech_off;
+    a.act = p.a1.arr[0].act;
+    session_args(b, a);
+    NAM_HIP_CHECK(launch_kq(a, n, p.a1.arr[0].act, s));
+  }
+  else if (fn == FN_KT_MFMA)
+    NAM_HIP_CHECK(launch_kt_mfma(a, n, p.a1.kt_nk, p.a1.arr[0].channels, p.a1.kt_lds_floats, p.a1.arr[0].act, s));
+  else if (fn == FN_A1_MFMA)
+  {
+    a.n_mjobs = p.a1.ws_jobs;
+    a.tiles_off = p.a1.ws_tiles_off;
+    a.consts_off = p.a1.ws_consts_off;
+    a.r1_off = p.a1.ws_r1_off;
+    a.xt_off = p.a1.ws_xt_off;
+    a.n_xt = p.a1.ws_n_xt;
+    a.lds_tiles_b = p.a1.ws_lds_tiles_b;
+    a.lds_xt_b = p.a1.ws_lds_xt_b;
+    a.lds_cond_b = p.a1.ws_lds_cond_b;
+    a.lds_bytes = p.a1.ws_lds_bytes;
+    a.prefetch = p.a1.ws_prefetch;
+    NAM_HIP_CHECK(launch_a1_mfma(a, n, uniform_act(p.a1), s));
+  }
+  else
+    NAM_HIP_CHECK(launch_a1(a, n, s));
+  return NAM_HIP_OK;
+}
+
+static int launch_generic_program(const WidthGroup& g, GenericArgs& a, int n, hipStream_t s)
+{
+  const Plan& p = *g.plan;
+  a.ops = g.d_ops;
+  a.in_ch = p.in_channels;
+  a.out_ch = p.out_channels;
+  // conv weights from LDS when the model's weights fit next to the activation rows (kernels.h)
+  int lds_bytes = p.lds_rows * kBlock * (int)sizeof(float);
+  a.w_lds_off = p.lds_rows * kBlock;
+  a.blob_floats = 0;
+  if (lds_bytes + p.generic_blob_floats * (int)sizeof(float) <= 96 * 1024)
+  {
+    a.blob_floats = p.generic_blob_floats;
+    lds_bytes += p.generic_blob_floats * (int)sizeof(float);
+  }
+  NAM_HIP_CHECK(launch_generic(a, n, lds_bytes, s));
+  return NAM_HIP_OK;
+}
+
+static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTMArgs& a, int n, hipStream_t s)
+{
+  a.n_streams = n;
+  if (fn == FN_LSTM_ROW || fn == FN_LSTM_WIDE)
+  {
+    a.ps = persist_args(b);
+    NAM_HIP_CHECK(fn == FN_LSTM_ROW ? launch_lstm_row(a, s) : launch_lstm_wide(a, s));
+  }
+  else if (fn == FN_LSTM_MFMA || fn == FN_LSTM_MFMA_REG) // (launch_lstm_mfma tells the two apart: lstm_mfma_in_registers)
+    NAM_HIP_CHECK(launch_lstm_mfma(a, s));
+  else
+  {
+    // a cell whose columns exceed a CU's LDS keeps them in global memory (the reference has no size limit,
+    // lstm.cpp:31-68): slower, but it runs
+    const long need = lstm_scratch_floats(a);
+    if (need > g.scratch_floats)
+    {
+      NAM_HIP_CHECK(hipStreamSynchronize(s));
+      if (g.d_scratch)
+        NAM_HIP_CHECK(hipFree(g.d_scratch));
+      g.d_scratch = nullptr;
+      g.scratch_floats = 0;
+      NAM_HIP_CHECK(hipMalloc(&g.d_scratch, (size_t)need * sizeof(float)));
+      g.scratch_floats = need;
+    }
+    a.scratch = g.d_scratch;
+    NAM_HIP_CHECK(launch_lstm(a, s));
+  }
+  return NAM_HIP_OK;
+}
+
 // Launch one group's kernel over `n` streams given by `d_map` (nullptr = streams 0..n-1).
 int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out,
                  int n_frames, long io_stride, hipStream_t s)
@@ -460,267 +670,38 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
   if (n <= 0 || n_frames <= 0)
     return NAM_HIP_OK;
   const Plan& p = *g.plan;
-  if (p.arch == ARCH_WAVENET)
+  const LaunchQuestion q{n_frames, b->ps_launching ? b->ps.kind : (int)PERSIST_NONE, b->short_blocking_call};
+  const KernelFn fn = select_kernel(b, g, q);
+  if (p.arch != ARCH_WAVENET)
   {
-    const int kernel = kernel_for_launch(b, g, n_frames);
-    // the op program and the A1 kernels of a channel-padded model keep different ring layouts: a change of kernel
-    // family is only legal on freshly reset state
-    const int fam = state_family_of(p, kernel);
-    if (g.state_family >= 0 && g.state_family != fam)
-      return fail(NAM_HIP_ERR_INVALID_ARGUMENT,
-                  "kernel change crosses state layouts (the op program's rings, the A1 kernels' zero-padded rings and "
-                  "nam_wn_reg_kernel's conv-input histories differ): call nam_hip_batch_reset before switching");
-    g.state_family = fam;
-    if (kernel == NAM_HIP_KERNEL_WN_REG)
-    {
-      WidthGroup* one[1] = {&g};
-      const int* maps[1] = {d_map};
-      const int counts[1] = {n};
-      return launch_wr(b, one, maps, counts, 1, d_in, d_out, n_frames, io_stride, s);
-    }
-    if (kernel != NAM_HIP_KERNEL_GENERIC)
-    {
-      A1Args a;
-      a.plan = g.d_a1;
-      a.blob = g.d_blob;
-      a.state = g.d_state;
-      a.state_stride = g.state_stride;
-      a.stream_map = d_map;
-      a.in = d_in;
-      a.out = d_out;
-      a.io_stride = io_stride;
-      a.n_frames = n_frames;
-      a.act_p0 = p.a1.arr[0].act_p0; // uniform across arrays and layers for the A1 kernels (plan.cpp)
-      a.dbg = b->dbg;
-      if (b->ps_launching && b->ps.h_why)
-        a.dbg = b->ps.d_why; // (NAM_HIP_SESSION_STATS: why a lingering workgroup left — il_common.h: session_wait_command)
-      a.n_rings = p.a1.n_rings;
-      a.head_scale = p.blob[(size_t)p.a1.head_scale_off];
-      a.n_mjobs = a.tiles_off = a.consts_off = 0;
-      a.r1_off = a.xt_off = a.n_xt = a.lds_tiles_b = a.lds_xt_b = a.lds_cond_b = a.lds_bytes = a.prefetch = 0;
-      a.il_jobs = a.il_real_jobs = a.il_depth = a.il_exch = 0;
-      a.il_consts_b = a.il_xt_b = a.il_tiles_b = a.il_flag_b = a.il_lds_bytes = a.act = 0;
-      a.p_ring = nullptr;
-      a.p_ring_mask = 0;
-      a.p_cons = a.p_prog = a.p_done = nullptr;
-      a.p_grace = 0;
-      a.p_out_host = 0;
-      a.p_linger = 0;
-      a.p_cmd_count = a.p_cmd_done = nullptr;
-      a.p_seq0 = -1;
-      a.p_cmd0 = 0;
-      a.bank_member = g.d_bank_member;
-      a.bank_scal = g.d_bank_scal;
-      a.bank_stride = g.bank_stride;
-      if (g.d_bank_member && kernel != NAM_HIP_KERNEL_A1_IL)
-        return fail(NAM_HIP_ERR_UNSUPPORTED, "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank");
-      if (kernel == NAM_HIP_KERNEL_A1_IL)
-      {
-        int act = p.a1.arr[0].act;
-        for (int i = 1; i < p.a1.n_arrays; i++)
-          if (p.a1.arr[i].act != act)
-            act = -1;
-        // a bank's rows start at the kernels' region of the blob (api_bank.cpp): offsets from there
-        const int base = g.d_bank_member ? p.a1.ws_tiles_off : 0;
-        a.tiles_off = p.a1.ws_tiles_off - base;
-        a.consts_off = p.a1.ws_consts_off - base;
-        a.xt_off = p.a1.ws_xt_off - base;
-        a.n_xt = p.a1.ws_n_xt;
-        a.il_jobs = p.a1.il_jobs;
-        a.il_real_jobs = p.a1.il_real_jobs;
-        a.il_depth = p.a1.il_depth;
-        a.il_exch = p.a1.il_exch;
-        a.il_consts_b = p.a1.il_consts_b;
-        a.il_xt_b = p.a1.il_xt_b;
-        a.il_tiles_b = p.a1.il_tiles_b;
-        a.il_flag_b = p.a1.il_flag_b;
-        a.il_lds_bytes = p.a1.il_lds_bytes;
-        a.act = act;
-        if (b->ps_launching)
-        {
-          a.p_ring = b->ps.d_ring;
-          a.p_ring_mask = (int)kPRing - 1;
-          a.p_cons = b->ps.d_cons;
-          a.p_prog = b->ps.d_words;
-          a.p_done = b->ps.d_words + b->ps.done_off;
-          a.p_grace = b->ps.grace;
-          a.p_out_host = b->ps.out_is_host ? (b->ps.cmd_done_published ? 2 : 1) : 0;
-          a.p_linger = (b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus) ? session_linger_ticks(b) : 0; // (more workgroups than CUs take turns: the ones on the chip must leave when the ring is empty)
-          a.p_cmd_count = b->ps.d_cmd_count;
-          a.p_cmd_done = b->ps.d_cmd_done;
-          a.p_seq0 = b->ps.seq0;
-          a.p_cmd0 = b->ps.cmd0;
-        }
-        if (!p.a1.p2_ok) // (pick_kernel: the interleaved-frame kernels exist for the official topologies' compile-time tables only)
-          return fail(NAM_HIP_ERR_UNSUPPORTED, "NAM_HIP_KERNEL_A1_IL: not one of the official topologies");
-        if (use_pipeline(b, n_frames) && q_runs(b, p) && !b->short_blocking_call && !(b->ps_launching && !b->pipe_session && b->ps.short_bursts()))
-        {
-          // the 16 / 8 topology as twelve one-wave stages, most rings resident in LDS (kernel_a1_q.hip): its own weight block
-          // + the FULL-layout tiles of array 0 (kept in registers)
-          a.consts_off = p.a1.ws_tiles_off - base;
-          a.tiles_off = p.a1.q_w_off - base;
-          NAM_HIP_CHECK(launch_a1_q(a, n, act, s));
-        }
-        else if (use_pipeline(b, n_frames))
-          // ... as a pipeline of wave sets (three wavefronts per SIMD) across consecutive buffers
-          NAM_HIP_CHECK(launch_a1_p4(a, n, p.a1.p2_c0, p.a1.p2_c1, act, s));
-        else // one buffer: the four-wave kernel, job table compiled in
-          NAM_HIP_CHECK(launch_a1_p2(a, n, p.a1.p2_c0, p.a1.p2_c1, act, s));
-      }
-      else if (kernel == NAM_HIP_KERNEL_A1_MFMA && !p.a1.ws_ok && n_frames > (1 << 28))
-        // the K-tap kernel addresses the launch's input through a 32-bit buffer descriptor (1 GiB of float32 audio per
-        // stream and launch): longer launches take the VALU kernel, same state layout
-        NAM_HIP_CHECK(launch_a1(a, n, s));
-      else if (kernel == NAM_HIP_KERNEL_A1_MFMA && !p.a1.ws_ok && kq_runs(b, p) && use_pipeline(b, n_frames))
-      {
-        // the A2 topology with more than one buffer in the launch (a session, a render, a prewarm): the pipeline of one-wave
-        // stages compiled for it (kernel_kq.hip); same state as the K-tap kernel below
-        a.tiles_off = p.a1.kt_desc[0].tile_off;
-        a.consts_off = p.a1.kt_lds_src_off;
-        a.r1_off = p.a1.kt_rech_off;
-        a.act = p.a1.arr[0].act;
-        if (b->ps_launching)
-        {
-          a.p_ring = b->ps.d_ring;
-          a.p_ring_mask = (int)kPRing - 1;
-          a.p_cons = b->ps.d_cons;
-          a.p_prog = b->ps.d_words;
-          a.p_done = b->ps.d_words + b->ps.done_off;
-          a.p_grace = b->ps.grace;
-          a.p_out_host = b->ps.out_is_host ? (b->ps.cmd_done_published ? 2 : 1) : 0;
-          a.p_linger = (b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus) ? session_linger_ticks(b) : 0; // (more workgroups than CUs take turns: the ones on the chip must leave when the ring is empty)
-          a.p_cmd_count = b->ps.d_cmd_count;
-          a.p_cmd_done = b->ps.d_cmd_done;
-          a.p_seq0 = b->ps.seq0;
-          a.p_cmd0 = b->ps.cmd0;
-        }
-        a.tiles_off = p.a1.kq_w_off;
-        NAM_HIP_CHECK(launch_kq(a, n, p.a1.arr[0].act, s));
-      }
-      else if (kernel == NAM_HIP_KERNEL_A1_MFMA && !p.a1.ws_ok)
-        // single-array models with other kernel sizes than 3 (A2): the K-tap MFMA kernel
-        NAM_HIP_CHECK(launch_kt_mfma(a, n, p.a1.kt_nk, p.a1.arr[0].channels, p.a1.kt_lds_floats, p.a1.arr[0].act, s));
-      else if (kernel == NAM_HIP_KERNEL_A1_MFMA)
-      {
-        // uniform activation across arrays -> compile-time specialised kernel, else run-time dispatch
-        int act = p.a1.arr[0].act;
-        for (int i = 1; i < p.a1.n_arrays; i++)
-          if (p.a1.arr[i].act != act)
-            act = -1;
-        a.n_mjobs = p.a1.ws_jobs;
-        a.tiles_off = p.a1.ws_tiles_off;
-        a.consts_off = p.a1.ws_consts_off;
-        a.r1_off = p.a1.ws_r1_off;
-        a.xt_off = p.a1.ws_xt_off;
-        a.n_xt = p.a1.ws_n_xt;
-        a.lds_tiles_b = p.a1.ws_lds_tiles_b;
-        a.lds_xt_b = p.a1.ws_lds_xt_b;
-        a.lds_cond_b = p.a1.ws_lds_cond_b;
-        a.lds_bytes = p.a1.ws_lds_bytes;
-        a.prefetch = p.a1.ws_prefetch;
-        NAM_HIP_CHECK(launch_a1_mfma(a, n, act, s));
-      }
-      else
-        NAM_HIP_CHECK(launch_a1(a, n, s));
-    }
-    else
-    {
-      GenericArgs a;
-      a.ops = g.d_ops;
-      a.blob = g.d_blob;
-      a.state = g.d_state;
-      a.state_stride = g.state_stride;
-      a.stream_map = d_map;
-      a.in = d_in;
-      a.out = d_out;
-      a.io_stride = io_stride;
-      a.n_frames = n_frames;
-      a.in_ch = p.in_channels;
-      a.out_ch = p.out_channels;
-      // conv weights from LDS when the model's weights fit next to the activation rows (kernels.h)
-      int lds_bytes = p.lds_rows * kBlock * (int)sizeof(float);
-      a.w_lds_off = p.lds_rows * kBlock;
-      a.blob_floats = 0;
-      if (lds_bytes + p.generic_blob_floats * (int)sizeof(float) <= 96 * 1024)
-      {
-        a.blob_floats = p.generic_blob_floats;
-        lds_bytes += p.generic_blob_floats * (int)sizeof(float);
-      }
-      NAM_HIP_CHECK(launch_generic(a, n, lds_bytes, s));
-    }
+    LSTMArgs a = lstm_args(p.lstm);
+    common_args(a, g, d_map, d_in, d_out, n_frames, io_stride);
+    return launch_lstm_family(b, g, fn, a, n, s);
   }
-  else
+  // the op program and the A1 kernels of a channel-padded model keep different ring layouts: a change of kernel
+  // family is only legal on freshly reset state
+  const int fam = state_family_of(p, family_for_launch(b, g, q));
+  if (g.state_family >= 0 && g.state_family != fam)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT,
+                "kernel change crosses state layouts (the op program's rings, the A1 kernels' zero-padded rings and "
+                "nam_wn_reg_kernel's conv-input histories differ): call nam_hip_batch_reset before switching");
+  g.state_family = fam;
+  if (fn == FN_WN_REG)
   {
-    const LSTMPlan& L = p.lstm;
-    LSTMArgs a;
-    a.blob = g.d_blob;
-    a.state = g.d_state;
-    a.state_stride = g.state_stride;
-    a.stream_map = d_map;
-    a.in = d_in;
-    a.out = d_out;
-    a.io_stride = io_stride;
-    a.n_frames = n_frames;
-    a.n_streams = n;
-    a.n_layers = L.n_layers;
-    a.input_size = L.input_size;
-    a.hidden = L.hidden;
-    a.in_ch = L.in_ch;
-    a.out_ch = L.out_ch;
-    a.fast = L.fast;
-    a.head_w = L.head_w;
-    a.head_b = L.head_b;
-    for (int i = 0; i < 16; i++)
-    {
-      a.layer_w[i] = L.layer_w[i];
-      a.layer_b[i] = L.layer_b[i];
-    }
-    a.mf_off = L.mf_off;
-    a.mf_floats = L.mf_floats;
-    a.mf_nt = L.mf_nt;
-    a.mf_head_tiles = L.mf_head_tiles;
-    a.mf_head_bias = L.mf_head_bias;
-    a.mf_lds_bytes = L.mf_lds_bytes;
-    for (int i = 0; i < 16; i++)
-    {
-      a.mf_layer_tiles[i] = L.mf_layer_tiles[i];
-      a.mf_layer_bias[i] = L.mf_layer_bias[i];
-    }
-    // AUTO: small cells (hidden <= 4) one gate row per lane and four streams per wavefront, cells of 5 .. 32 units two
-    // gate rows per lane and one stream per wavefront, else the matrix-core kernel (16 streams per wavefront);
-    // NAM_HIP_KERNEL_A1_MFMA forces the matrix-core kernel; NAM_HIP_KERNEL_GENERIC: lanes = streams
-    if (b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA && lstm_row_eligible(a))
-    {
-      a.ps = persist_args(b);
-      NAM_HIP_CHECK(launch_lstm_row(a, s));
-    }
-    else if (b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA && lstm_wide_eligible(a))
-    {
-      a.ps = persist_args(b);
-      NAM_HIP_CHECK(launch_lstm_wide(a, s));
-    }
-    else if (L.mf_ok && b->kernel != NAM_HIP_KERNEL_GENERIC)
-      NAM_HIP_CHECK(launch_lstm_mfma(a, s));
-    else
-    {
-      // a cell whose columns exceed a CU's LDS keeps them in global memory (the reference has no size limit,
-      // lstm.cpp:31-68): slower, but it runs
-      const long need = lstm_scratch_floats(a);
-      if (need > g.scratch_floats)
-      {
-        NAM_HIP_CHECK(hipStreamSynchronize(s));
-        if (g.d_scratch)
-          NAM_HIP_CHECK(hipFree(g.d_scratch));
-        g.d_scratch = nullptr;
-        g.scratch_floats = 0;
-        NAM_HIP_CHECK(hipMalloc(&g.d_scratch, (size_t)need * sizeof(float)));
-        g.scratch_floats = need;
-      }
-      a.scratch = g.d_scratch;
-      NAM_HIP_CHECK(launch_lstm(a, s));
-    }
+    WidthGroup* one[1] = {&g};
+    const int* maps[1] = {d_map};
+    const int counts[1] = {n};
+    return launch_wr(b, one, maps, counts, 1, d_in, d_out, n_frames, io_stride, s);
   }
-  return NAM_HIP_OK;
+  if (fn == FN_GENERIC)
+  {
+    GenericArgs a;
+    common_args(a, g, d_map, d_in, d_out, n_frames, io_stride);
+    return launch_generic_program(g, a, n, s);
+  }
+  A1Args a;
+  common_args(a, g, d_map, d_in, d_out, n_frames, io_stride);
+  return launch_a1_family(b, g, fn, a, n, s);
 }
 
 // DSP::prewarm (NAM/dsp.cpp:67-101): process whole max_frames-sized buffers of silence until at

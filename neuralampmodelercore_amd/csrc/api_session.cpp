@@ -58,11 +58,9 @@ int persist_kind(const nam_hip_batch* b)
   if (g.plan->arch == ARCH_LSTM && b->kernel == NAM_HIP_KERNEL_AUTO)
   {
     const LSTMPlan& L = g.plan->lstm;
-    if (L.hidden >= 1 && L.hidden <= 4 && L.n_layers >= 1 && L.n_layers <= 2 && L.input_size >= 1 && L.input_size <= 2
-        && L.in_ch == L.input_size && L.out_ch >= 1 && L.out_ch <= 16 && (b->n_streams + 3) / 4 <= 8 * cus)
+    if (lstm_row_eligible(L) && (b->n_streams + 3) / 4 <= 8 * cus)
       return PERSIST_LSTM_ROW;
-    if (L.hidden >= 5 && L.hidden <= 32 && L.n_layers >= 1 && L.n_layers <= 2 && L.input_size >= 1 && L.input_size <= 2
-        && L.in_ch == L.input_size && L.out_ch >= 1 && L.out_ch <= 16 && b->n_streams <= 4 * cus) // one wavefront per SIMD
+    if (lstm_wide_eligible(L) && b->n_streams <= 4 * cus) // one wavefront per SIMD
       return PERSIST_LSTM_WIDE;
   }
   return PERSIST_NONE;
@@ -113,17 +111,13 @@ static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, u
       NAM_HIP_CHECK(hipMemsetAsync(ps.d_cmd_count + kPRing + 1, 0, sizeof(unsigned), ps.kstream));
     }
   }
-  const int keep = b->kernel;
-  if (ps.kind == PERSIST_A1_P2)
-    b->kernel = NAM_HIP_KERNEL_A1_IL;
-  b->ps_launching = true;
+  b->ps_launching = true; // (a session of the interleaved-frame family runs that family: api_launch.cpp, family_for_launch)
   namhip::tl_session_stop_event = ps.retired; // (the launch's own completion signal: persist_wait waits on it, not on the stream)
   const int rc = ps.kind == PERSIST_WN_REG
                    ? launch_wr_all(b, wr_groups(b), ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream)
                    : launch_group(b, g, nullptr, b->n_streams, ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream);
   namhip::tl_session_stop_event = nullptr;
   b->ps_launching = false;
-  b->kernel = keep;
   return rc;
 }
 

@@ -481,44 +481,31 @@ __global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict_
 
 namespace
 {
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST = false, bool BANK = false>
+template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, bool BANK>
 hipError_t launch_p2_inst(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST, BANK>), p2::kLdsBytes);
-  if (e != hipSuccess)
-    return e;
-  nam_launch((nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST, BANK>), dim3(n_blocks), dim3(256), p2::kLdsBytes, stream, a.blob, a);
-  return hipGetLastError();
+  return launch_instance<&nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST, BANK>>(dim3(n_blocks), dim3(256), p2::kLdsBytes, stream, a.blob, a);
 }
-// a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
-template <int ACT_T>
-hipError_t launch_p2_bank(const A1Args& a, int n_blocks, hipStream_t stream)
-{
-  if (a.p_ring)
-    return launch_p2_inst<16, 8, ACT_T, false, true, true>(a, n_blocks, stream);
-  const bool wt = a.n_frames <= 2 * kBlock;
-  return wt ? launch_p2_inst<16, 8, ACT_T, true, false, true>(a, n_blocks, stream) : launch_p2_inst<16, 8, ACT_T, false, false, true>(a, n_blocks, stream);
-}
-template <int C0, int C1>
-hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, hipStream_t stream)
+// This kernel's own rule (not kernels.h: with_session_form): its session instantiations never write through.
+// BANK, a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
+template <int C0, int C1, int ACT_T, bool BANK = false>
+hipError_t launch_p2_act(const A1Args& a, int n_blocks, hipStream_t stream)
 {
   // persistent session: plain write-back ring appends (written through, the rows a block appends would be read back
   // from memory instead of the L2 one block later: 27 us per block instead of 10.5, measured)
   if (a.p_ring)
-  {
-    if (act == ACT_FASTTANH)
-      return launch_p2_inst<C0, C1, ACT_FASTTANH, false, true>(a, n_blocks, stream);
-    if (act == ACT_TANH)
-      return launch_p2_inst<C0, C1, ACT_TANH, false, true>(a, n_blocks, stream);
-    return launch_p2_inst<C0, C1, -1, false, true>(a, n_blocks, stream);
-  }
+    return launch_p2_inst<C0, C1, ACT_T, false, true, BANK>(a, n_blocks, stream);
   const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through (see ring_store)
+  return wt ? launch_p2_inst<C0, C1, ACT_T, true, false, BANK>(a, n_blocks, stream) : launch_p2_inst<C0, C1, ACT_T, false, false, BANK>(a, n_blocks, stream);
+}
+template <int C0, int C1>
+hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, hipStream_t stream)
+{
   if (act == ACT_FASTTANH)
-    return wt ? launch_p2_inst<C0, C1, ACT_FASTTANH, true>(a, n_blocks, stream) : launch_p2_inst<C0, C1, ACT_FASTTANH, false>(a, n_blocks, stream);
+    return launch_p2_act<C0, C1, ACT_FASTTANH>(a, n_blocks, stream);
   if (act == ACT_TANH)
-    return wt ? launch_p2_inst<C0, C1, ACT_TANH, true>(a, n_blocks, stream) : launch_p2_inst<C0, C1, ACT_TANH, false>(a, n_blocks, stream);
-  return wt ? launch_p2_inst<C0, C1, -1, true>(a, n_blocks, stream) : launch_p2_inst<C0, C1, -1, false>(a, n_blocks, stream);
+    return launch_p2_act<C0, C1, ACT_TANH>(a, n_blocks, stream);
+  return launch_p2_act<C0, C1, -1>(a, n_blocks, stream);
 }
 } // namespace
 
@@ -528,7 +515,7 @@ hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, 
   {
     if (c0 != 16 || c1 != 8 || (act != ACT_FASTTANH && act != ACT_TANH))
       return hipErrorInvalidValue;
-    return act == ACT_FASTTANH ? launch_p2_bank<ACT_FASTTANH>(a, n_blocks, stream) : launch_p2_bank<ACT_TANH>(a, n_blocks, stream);
+    return act == ACT_FASTTANH ? launch_p2_act<16, 8, ACT_FASTTANH, true>(a, n_blocks, stream) : launch_p2_act<16, 8, ACT_TANH, true>(a, n_blocks, stream);
   }
   if (c0 == 16 && c1 == 8)
     return launch_p2_shape<16, 8>(a, n_blocks, act, stream);

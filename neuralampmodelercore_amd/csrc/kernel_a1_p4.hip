@@ -754,86 +754,67 @@ namespace
 #endif
 constexpr int kP4Stages = NAM_P4_STAGES;
 
-// the instantiation's code object on the device and its dynamic-LDS limit raised (what the first launch would otherwise pay: ~1.6 ms)
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, bool BANK = false>
-hipError_t p4_ready()
+// What picks the instantiation of a launch, and the launch itself. `a == nullptr`: nothing is launched — the instantiation is made
+// ready (kernels.h: instance_ready), so that what preload_a1_p4_session prepares is what launch_a1_p4 will pick: one walk for both.
+struct P4Pick
 {
-  static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  return lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_p4_kernel<C0, C1, ACT_T, WT, PERSIST, kP4Stages, BANK>), p4::lds_bytes(kP4Stages));
-}
-template <int C0, int C1, int ACT_T, bool WT, bool PERSIST = false, bool BANK = false>
-hipError_t launch_p4_inst(const A1Args& a, int n_blocks, hipStream_t stream)
+  int c0, c1, act;
+  bool bank, session, out_host;
+  const A1Args* a;
+  int n_blocks;
+  hipStream_t stream;
+};
+template <int C0, int C1, int ACT_T, bool BANK = false>
+hipError_t p4_act(const P4Pick& k)
 {
-  constexpr int lds_bytes = p4::lds_bytes(kP4Stages);
-  const hipError_t e = p4_ready<C0, C1, ACT_T, WT, PERSIST, BANK>();
-  if (e != hipSuccess)
-    return e;
-  nam_launch((nam_a1_p4_kernel<C0, C1, ACT_T, WT, PERSIST, kP4Stages, BANK>), dim3(n_blocks), dim3(kP4Stages * 256), lds_bytes, stream,
-                     a.blob, a);
-  return hipGetLastError();
-}
-// a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
-template <int ACT_T>
-hipError_t launch_p4_bank(const A1Args& a, int n_blocks, hipStream_t stream)
-{
-  if (a.p_ring)
-    return a.p_out_host != 0 ? launch_p4_inst<16, 8, ACT_T, true, true, true>(a, n_blocks, stream) : launch_p4_inst<16, 8, ACT_T, false, true, true>(a, n_blocks, stream);
-  const bool wt = a.n_frames <= 2 * kBlock;
-  return wt ? launch_p4_inst<16, 8, ACT_T, true, false, true>(a, n_blocks, stream) : launch_p4_inst<16, 8, ACT_T, false, false, true>(a, n_blocks, stream);
+  return with_session_form(k.session, k.out_host, k.a ? k.a->n_frames : 0, [&](auto wt, auto persist) {
+    constexpr auto kernel = &nam_a1_p4_kernel<C0, C1, ACT_T, decltype(wt)::value, decltype(persist)::value, kP4Stages, BANK>;
+    constexpr int lds_bytes = p4::lds_bytes(kP4Stages);
+    if (!k.a)
+      return instance_ready<kernel>(lds_bytes);
+    return launch_instance<kernel>(dim3(k.n_blocks), dim3(kP4Stages * 256), lds_bytes, k.stream, k.a->blob, *k.a);
+  });
 }
 template <int C0, int C1>
-hipError_t launch_p4_shape(const A1Args& a, int n_blocks, int act, hipStream_t stream)
+hipError_t p4_shape(const P4Pick& k)
 {
-  if (a.p_ring) // persistent session: write-back ring appends (kernel_a1_p2.hip: launch_p2_shape) ...
+  if (k.act == ACT_FASTTANH)
+    return p4_act<C0, C1, ACT_FASTTANH>(k);
+  if (k.act == ACT_TANH)
+    return p4_act<C0, C1, ACT_TANH>(k);
+  return p4_act<C0, C1, -1>(k);
+}
+hipError_t p4_walk(const P4Pick& k)
+{
+  if (k.bank) // a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
   {
-    const bool oh = a.p_out_host != 0; // ... unless its results go to host memory (kOutHost)
-    if (act == ACT_FASTTANH)
-      return oh ? launch_p4_inst<C0, C1, ACT_FASTTANH, true, true>(a, n_blocks, stream) : launch_p4_inst<C0, C1, ACT_FASTTANH, false, true>(a, n_blocks, stream);
-    if (act == ACT_TANH)
-      return oh ? launch_p4_inst<C0, C1, ACT_TANH, true, true>(a, n_blocks, stream) : launch_p4_inst<C0, C1, ACT_TANH, false, true>(a, n_blocks, stream);
-    return oh ? launch_p4_inst<C0, C1, -1, true, true>(a, n_blocks, stream) : launch_p4_inst<C0, C1, -1, false, true>(a, n_blocks, stream);
+    if (k.c0 != 16 || k.c1 != 8 || (k.act != ACT_FASTTANH && k.act != ACT_TANH))
+      return hipErrorInvalidValue;
+    return k.act == ACT_FASTTANH ? p4_act<16, 8, ACT_FASTTANH, true>(k) : p4_act<16, 8, ACT_TANH, true>(k);
   }
-  const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through (device_common.h: ring_store)
-  if (act == ACT_FASTTANH)
-    return wt ? launch_p4_inst<C0, C1, ACT_FASTTANH, true>(a, n_blocks, stream) : launch_p4_inst<C0, C1, ACT_FASTTANH, false>(a, n_blocks, stream);
-  if (act == ACT_TANH)
-    return wt ? launch_p4_inst<C0, C1, ACT_TANH, true>(a, n_blocks, stream) : launch_p4_inst<C0, C1, ACT_TANH, false>(a, n_blocks, stream);
-  return wt ? launch_p4_inst<C0, C1, -1, true>(a, n_blocks, stream) : launch_p4_inst<C0, C1, -1, false>(a, n_blocks, stream);
+  if (k.c0 == 16 && k.c1 == 8)
+    return p4_shape<16, 8>(k);
+  if (k.c0 == 12 && k.c1 == 8)
+    return p4_shape<12, 8>(k);
+  if (k.c0 == 8 && k.c1 == 4)
+    return p4_shape<8, 4>(k);
+  return hipErrorInvalidValue;
 }
 } // namespace
 
 // A session of the 16 / 8 topology may switch to this kernel in the middle of a caller's real-time loop (api_launch.cpp:
 // PersistSession::short_bursts): its session instantiation is made ready when the session starts, not at the switch.
+// (Only what nam_a1_q_kernel runs can switch: other shapes and activations have nothing to make ready.)
 hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host, bool bank)
 {
-  if (c0 != 16 || c1 != 8)
+  if (c0 != 16 || c1 != 8 || !a1_q_takes(act))
     return hipSuccess;
-  if (bank && act == ACT_FASTTANH)
-    return out_host ? p4_ready<16, 8, ACT_FASTTANH, true, true, true>() : p4_ready<16, 8, ACT_FASTTANH, false, true, true>();
-  if (bank && act == ACT_TANH)
-    return out_host ? p4_ready<16, 8, ACT_TANH, true, true, true>() : p4_ready<16, 8, ACT_TANH, false, true, true>();
-  if (act == ACT_FASTTANH)
-    return out_host ? p4_ready<16, 8, ACT_FASTTANH, true, true>() : p4_ready<16, 8, ACT_FASTTANH, false, true>();
-  if (act == ACT_TANH)
-    return out_host ? p4_ready<16, 8, ACT_TANH, true, true>() : p4_ready<16, 8, ACT_TANH, false, true>();
-  return hipSuccess;
+  return p4_walk(P4Pick{c0, c1, act, bank, true, out_host, nullptr, 0, nullptr});
 }
 
 hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream)
 {
-  if (a.bank_member)
-  {
-    if (c0 != 16 || c1 != 8 || (act != ACT_FASTTANH && act != ACT_TANH))
-      return hipErrorInvalidValue;
-    return act == ACT_FASTTANH ? launch_p4_bank<ACT_FASTTANH>(a, n_blocks, stream) : launch_p4_bank<ACT_TANH>(a, n_blocks, stream);
-  }
-  if (c0 == 16 && c1 == 8)
-    return launch_p4_shape<16, 8>(a, n_blocks, act, stream);
-  if (c0 == 12 && c1 == 8)
-    return launch_p4_shape<12, 8>(a, n_blocks, act, stream);
-  if (c0 == 8 && c1 == 4)
-    return launch_p4_shape<8, 4>(a, n_blocks, act, stream);
-  return hipErrorInvalidValue;
+  return p4_walk(P4Pick{c0, c1, act, a.bank_member != nullptr, a.p_ring != nullptr, a.p_out_host != 0, &a, n_blocks, stream});
 }
 
 } // namespace namhip

@@ -1110,29 +1110,13 @@ template __global__ void nam_a1_q_kernel<ACT_FASTTANH, false, true>(const float*
 #else
 namespace
 {
-template <int ACT_T, bool BANK, bool WT, bool PERSIST = false>
-hipError_t launch_q_inst(const A1Args& a, int n_blocks, hipStream_t stream)
-{
-  static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_q_kernel<ACT_T, WT, PERSIST, false, BANK>), aq::kLdsBytes);
-  if (e != hipSuccess)
-    return e;
-  nam_launch((nam_a1_q_kernel<ACT_T, WT, PERSIST, false, BANK>), dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
-  return hipGetLastError();
-}
 template <int ACT_T, bool BANK>
 hipError_t launch_q_bank(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  if (a.p_ring) // persistent session (kernel_a1_p4.hip: launch_p4_shape)
-    return a.p_out_host != 0 ? launch_q_inst<ACT_T, BANK, true, true>(a, n_blocks, stream) : launch_q_inst<ACT_T, BANK, false, true>(a, n_blocks, stream);
-  const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through
-  return wt ? launch_q_inst<ACT_T, BANK, true>(a, n_blocks, stream) : launch_q_inst<ACT_T, BANK, false>(a, n_blocks, stream);
-}
-template <int ACT_T>
-hipError_t launch_q_act(const A1Args& a, int n_blocks, hipStream_t stream)
-{
-  // a model bank (A1Args::bank_member) runs the BANK instantiations; one model keeps its own
-  return a.bank_member ? launch_q_bank<ACT_T, true>(a, n_blocks, stream) : launch_q_bank<ACT_T, false>(a, n_blocks, stream);
+  return with_session_form(a.p_ring != nullptr, a.p_out_host != 0, a.n_frames, [&](auto wt, auto persist) {
+    return launch_instance<&nam_a1_q_kernel<ACT_T, decltype(wt)::value, decltype(persist)::value, false, BANK>>(
+      dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
+  });
 }
 } // namespace
 
@@ -1145,18 +1129,12 @@ bool a1_q_takes(int act)
 hipError_t launch_a1_q(const A1Args& a, int n_blocks, int act, hipStream_t stream)
 {
   if (a.dbg && !a.p_ring && !a.bank_member) // developer tool (nam_hip_batch_debug_timeline): the stamped instantiation
-  {
-    static DynamicLdsLimit lds_limit;
-    const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_a1_q_kernel<ACT_FASTTANH, false, false, true>), aq::kLdsBytes);
-    if (e != hipSuccess)
-      return e;
-    hipLaunchKernelGGL((nam_a1_q_kernel<ACT_FASTTANH, false, false, true>), dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
-    return hipGetLastError();
-  }
+    return launch_instance<&nam_a1_q_kernel<ACT_FASTTANH, false, false, true>, true>(dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
+  const bool bank = a.bank_member != nullptr; // a model bank runs the BANK instantiations; one model keeps its own
   if (act == ACT_FASTTANH)
-    return launch_q_act<ACT_FASTTANH>(a, n_blocks, stream);
+    return bank ? launch_q_bank<ACT_FASTTANH, true>(a, n_blocks, stream) : launch_q_bank<ACT_FASTTANH, false>(a, n_blocks, stream);
   if (act == ACT_TANH)
-    return launch_q_act<ACT_TANH>(a, n_blocks, stream);
+    return bank ? launch_q_bank<ACT_TANH, true>(a, n_blocks, stream) : launch_q_bank<ACT_TANH, false>(a, n_blocks, stream);
   return hipErrorInvalidValue; // (other activations keep nam_a1_p4_kernel: a1_q_takes)
 }
 #endif

@@ -811,23 +811,13 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
 
 namespace
 {
-template <int ACT_T, bool WT, bool PERSIST = false>
-hipError_t launch_kq_inst(const A1Args& a, int n_blocks, hipStream_t stream)
-{
-  static DynamicLdsLimit lds_limit; // per instantiation, tracked per device (kernels.h)
-  const hipError_t e = lds_limit.ensure(reinterpret_cast<const void*>(&nam_kq_kernel<ACT_T, WT, PERSIST>), kq::kLdsBytes);
-  if (e != hipSuccess)
-    return e;
-  nam_launch((nam_kq_kernel<ACT_T, WT, PERSIST>), dim3(n_blocks), dim3(kq::kNst * 64), kq::kLdsBytes, stream, a.blob, a);
-  return hipGetLastError();
-}
 template <int ACT_T>
 hipError_t launch_kq_act(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  if (a.p_ring) // persistent session (kernel_a1_p4.hip: launch_p4_shape)
-    return a.p_out_host != 0 ? launch_kq_inst<ACT_T, true, true>(a, n_blocks, stream) : launch_kq_inst<ACT_T, false, true>(a, n_blocks, stream);
-  const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through
-  return wt ? launch_kq_inst<ACT_T, true>(a, n_blocks, stream) : launch_kq_inst<ACT_T, false>(a, n_blocks, stream);
+  return with_session_form(a.p_ring != nullptr, a.p_out_host != 0, a.n_frames, [&](auto wt, auto persist) {
+    return launch_instance<&nam_kq_kernel<ACT_T, decltype(wt)::value, decltype(persist)::value>>(dim3(n_blocks), dim3(kq::kNst * 64), kq::kLdsBytes,
+                                                                                                 stream, a.blob, a);
+  });
 }
 } // namespace
 

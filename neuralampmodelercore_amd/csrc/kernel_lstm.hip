@@ -1058,7 +1058,7 @@ hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
   }
   const int n_blocks = (a.n_streams + 15) / 16;
   // small models: everything in registers (only the I/O tiles in LDS)
-  if (a.input_size <= 4 && a.n_layers <= 2 && a.mf_nt <= 6)
+  if (lstm_mfma_in_registers(a))
   {
     // I/O tiles + a pad row that lanes without an output row store to (64 lanes + 64 steps)
     const int io_bytes = ((a.in_ch + a.out_ch) * 16 * 65 + 128) * (int)sizeof(float);
@@ -1090,12 +1090,6 @@ hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
   return hipGetLastError();
 }
 
-bool lstm_row_eligible(const LSTMArgs& a)
-{
-  return a.hidden >= 1 && a.hidden <= 4 && a.n_layers >= 1 && a.n_layers <= 2 && a.input_size >= 1 && a.input_size <= 2
-         && a.in_ch == a.input_size && a.out_ch >= 1 && a.out_ch <= 16;
-}
-
 hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
 {
   if (!lstm_row_eligible(a))
@@ -1125,12 +1119,6 @@ hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
 #undef NAM_LSTM_ROW
 #undef NAM_LSTM_ROW_H
   return hipGetLastError();
-}
-
-bool lstm_wide_eligible(const LSTMArgs& a)
-{
-  return a.hidden >= 5 && a.hidden <= 32 && a.n_layers >= 1 && a.n_layers <= 2 && a.input_size >= 1 && a.input_size <= 2
-         && a.in_ch == a.input_size && a.out_ch >= 1 && a.out_ch <= 16;
 }
 
 hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)

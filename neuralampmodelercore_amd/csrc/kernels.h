@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <type_traits>
 
 #include "plan.h"
 
@@ -46,6 +47,28 @@ inline void nam_launch(F kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipS
     hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, nullptr, tl_session_stop_event, 0, args...);
   else
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+}
+
+// One kernel instantiation on the current device, its dynamic-LDS limit raised: the limit object lives here, one per `Kernel`
+// (= per instantiation, as DynamicLdsLimit asks). Also what a first launch would otherwise pay for (~1.6 ms: the code object).
+template <auto Kernel>
+inline hipError_t instance_ready(int lds_bytes)
+{
+  static DynamicLdsLimit lds_limit;
+  return lds_limit.ensure(reinterpret_cast<const void*>(Kernel), lds_bytes);
+}
+// ... and launched: through nam_launch (every session-capable kernel), or kPlain = a plain launch
+template <auto Kernel, bool kPlain = false, typename... Args>
+inline hipError_t launch_instance(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, Args... args)
+{
+  const hipError_t e = instance_ready<Kernel>(lds_bytes);
+  if (e != hipSuccess)
+    return e;
+  if constexpr (kPlain)
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+  else
+    nam_launch(Kernel, grid, block, lds_bytes, stream, args...);
+  return hipGetLastError();
 }
 
 // Persistent session of a one-wavefront-per-workgroup kernel (persist_wave.h); ring == nullptr: an ordinary launch
@@ -97,40 +120,40 @@ struct A1Args
   int n_frames;
   float act_p0; // LeakyReLU slope when the arrays use it
   // MFMA kernel: host-known scalars passed by value so the kernel prologue has no dependent loads
-  int n_rings, n_mjobs;
-  int tiles_off, consts_off; // blob offsets (floats) of the tile areas / consts table
+  int n_rings, n_mjobs = 0;
+  int tiles_off = 0, consts_off = 0; // blob offsets (floats) of the tile areas / consts table
   float head_scale;
   // wave-specialised kernel
-  int r1_off; // blob offset of the first array's rechannel column (16 floats)
-  int xt_off, n_xt; // blob offset / count of the extra tiles
-  int lds_tiles_b, lds_xt_b, lds_cond_b, lds_bytes; // dynamic LDS layout (bytes)
-  int prefetch; // the plan's ws_prefetch (mover prefetch depth the descriptors were built for)
+  int r1_off = 0; // blob offset of the first array's rechannel column (16 floats)
+  int xt_off = 0, n_xt = 0; // blob offset / count of the extra tiles
+  int lds_tiles_b = 0, lds_xt_b = 0, lds_cond_b = 0, lds_bytes = 0; // dynamic LDS layout (bytes)
+  int prefetch = 0; // the plan's ws_prefetch (mover prefetch depth the descriptors were built for)
   // interleaved-frame kernel (plan.h: A1Plan::il_*)
-  int il_jobs, il_real_jobs, il_depth, il_exch;
-  int il_consts_b, il_xt_b, il_tiles_b, il_flag_b, il_lds_bytes;
-  int act; // the arrays' activation type when it is uniform (nam_a1_p2_kernel's run-time-dispatch instantiation)
+  int il_jobs = 0, il_real_jobs = 0, il_depth = 0, il_exch = 0;
+  int il_consts_b = 0, il_xt_b = 0, il_tiles_b = 0, il_flag_b = 0, il_lds_bytes = 0;
+  int act = 0; // the arrays' activation type when it is uniform (nam_a1_p2_kernel's run-time-dispatch instantiation)
   // persistent session of nam_a1_p2_kernel (nullptr = ordinary launch): command ring in device memory, ring size - 1,
   // commands consumed before this launch, per-workgroup progress / completion words in host-mapped memory
-  unsigned long long* p_ring;
-  int p_ring_mask;
-  unsigned* p_cons; // device memory: commands consumed per workgroup (where its next launch resumes)
-  unsigned* p_prog; // host-mapped: progress, stored every 16 commands — the host's ring bookkeeping (back-pressure), NEVER a completion signal
+  unsigned long long* p_ring = nullptr;
+  int p_ring_mask = 0;
+  unsigned* p_cons = nullptr; // device memory: commands consumed per workgroup (where its next launch resumes)
+  unsigned* p_prog = nullptr; // host-mapped: progress, stored every 16 commands — the host's ring bookkeeping (back-pressure), NEVER a completion signal
                     // (per-buffer completion: p_cmd_done below; the launch's own: p_done = count | exited bit)
-  unsigned* p_done;
-  long long p_seq0; // >= 0: every workgroup has consumed exactly this many commands (p_cons is not read) ...
-  unsigned long long p_cmd0; // ... and this is the next command (the ring is not read for it)
-  int p_grace; // ticks (100 MHz) a fresh launch looks for its first doorbell before it leaves again
-  int p_out_host; // the session's output window is HOST memory (nam_a1_p4_kernel: kOutHost — plain result stores, ring
+  unsigned* p_done = nullptr;
+  long long p_seq0 = -1; // >= 0: every workgroup has consumed exactly this many commands (p_cons is not read) ...
+  unsigned long long p_cmd0 = 0; // ... and this is the next command (the ring is not read for it)
+  int p_grace = 0; // ticks (100 MHz) a fresh launch looks for its first doorbell before it leaves again
+  int p_out_host = 0; // the session's output window is HOST memory (nam_a1_p4_kernel: kOutHost — plain result stores, ring
                   // appends written through, one system-scope release fence before the completion word). 2 (nam_a1_q_kernel,
                   // nam_kq_kernel): ticketed host buffers — results written through and p_cmd_done stored after EVERY command,
                   // behind the results: the host takes a buffer's output while the launch runs on (nam_hip_batch_wait_f32)
-  int p_linger; // ticks (100 MHz) the launch looks for the NEXT command when it finds the ring empty, before it leaves (nam_a1_q_kernel,
+  int p_linger = 0; // ticks (100 MHz) the launch looks for the NEXT command when it finds the ring empty, before it leaves (nam_a1_q_kernel,
                 // nam_kq_kernel; 0 = 1 us, the other kernels' constant): a ticket session's host hands a buffer in every 5 - 15 us
   // ticketed host buffers (p_out_host == 2): p_cmd_count[c & p_ring_mask] (device memory) counts the workgroups that have finished
   // command c and made its results visible; the last one zeroes it and stores c + 1 to p_cmd_done[c & p_ring_mask] (host-mapped):
   // ONE word for the host to poll per buffer, one PCIe write per command
-  unsigned* p_cmd_count;
-  unsigned* p_cmd_done;
+  unsigned* p_cmd_count = nullptr;
+  unsigned* p_cmd_done = nullptr;
   long long* dbg; // optional: per-job phase timestamps of workgroup 0 (profiling builds / tools only), else nullptr
   // model bank (nam_hip_batch_create_bank; nam_a1_q_kernel, nam_a1_p4_kernel, nam_a1_p2_kernel — their BANK instantiations;
   // nullptr = one model, the fields above): stream s runs member m = bank_member[s] of `blob` = [members][bank_stride] floats
@@ -140,6 +163,22 @@ struct A1Args
   const float* bank_scal;
   long bank_stride;
 };
+static_assert(sizeof(A1Args) == 288, "A1Args is a kernel argument (296 bytes of kernarg with the blob pointer in front): its layout is part of the compiled kernels");
+
+// Which instantiation of a session-capable pipeline kernel (nam_a1_p4_kernel, nam_a1_q_kernel, nam_kq_kernel) a launch takes
+// besides its model's: f(WT, PERSIST) with the two as std::bool_constant.
+// A session's launch (PERSIST) appends to its rings write-back — written through, the rows a block appends would be read back
+// from memory instead of the L2 one block later: 27 us per block instead of 10.5, measured — unless its results go to host
+// memory (A1Args::p_out_host); an ordinary launch writes ring appends through when it is short (device_common.h: ring_store).
+template <typename F>
+inline hipError_t with_session_form(bool session, bool out_host, int n_frames, F&& f)
+{
+  constexpr std::true_type yes;
+  constexpr std::false_type no;
+  if (session)
+    return out_host ? f(yes, yes) : f(no, yes);
+  return n_frames <= 2 * kBlock ? f(yes, no) : f(no, no);
+}
 
 struct LSTMArgs
 {
@@ -163,6 +202,56 @@ struct LSTMArgs
   PersistArgs ps; // nam_lstm_row_kernel / nam_lstm_wide_kernel
   float* scratch = nullptr; // nam_lstm_kernel<true>: global-memory h / c / gate columns (lstm_scratch_floats)
 };
+// the model's part of an LSTM launch's arguments; the caller adds the streams and the audio
+inline LSTMArgs lstm_args(const LSTMPlan& L)
+{
+  LSTMArgs a;
+  a.n_layers = L.n_layers;
+  a.input_size = L.input_size;
+  a.hidden = L.hidden;
+  a.in_ch = L.in_ch;
+  a.out_ch = L.out_ch;
+  a.fast = L.fast;
+  a.head_w = L.head_w;
+  a.head_b = L.head_b;
+  a.mf_off = L.mf_off;
+  a.mf_floats = L.mf_floats;
+  a.mf_nt = L.mf_nt;
+  a.mf_head_tiles = L.mf_head_tiles;
+  a.mf_head_bias = L.mf_head_bias;
+  a.mf_lds_bytes = L.mf_lds_bytes;
+  for (int i = 0; i < 16; i++)
+  {
+    a.layer_w[i] = L.layer_w[i];
+    a.layer_b[i] = L.layer_b[i];
+    a.mf_layer_tiles[i] = L.mf_layer_tiles[i];
+    a.mf_layer_bias[i] = L.mf_layer_bias[i];
+  }
+  return a;
+}
+// Which cells the small-LSTM kernels take, and which the matrix-core kernel keeps in registers. Written over LSTMPlan's
+// fields; LSTMArgs carries a copy of them (lstm_args), so the launch_lstm_* guards ask the same functions (`L`: either).
+template <typename L>
+inline bool lstm_small_io(const L& l) // one or two layers over one or two input channels, at most 16 outputs
+{
+  return l.n_layers >= 1 && l.n_layers <= 2 && l.input_size >= 1 && l.input_size <= 2 && l.in_ch == l.input_size && l.out_ch >= 1
+         && l.out_ch <= 16;
+}
+template <typename L>
+inline bool lstm_row_eligible(const L& l) // nam_lstm_row_kernel
+{
+  return l.hidden >= 1 && l.hidden <= 4 && lstm_small_io(l);
+}
+template <typename L>
+inline bool lstm_wide_eligible(const L& l) // nam_lstm_wide_kernel
+{
+  return l.hidden >= 5 && l.hidden <= 32 && lstm_small_io(l);
+}
+template <typename L>
+inline bool lstm_mfma_in_registers(const L& l) // nam_lstm_mfma_reg_kernel: everything in registers (only the I/O tiles in LDS)
+{
+  return l.input_size <= 4 && l.n_layers <= 2 && l.mf_nt <= 6;
+}
 
 // nam_wn_reg_kernel (plan.h: WrPlan). One launch serves up to kWrMaxGroups WIDTH GROUPS — streams of a slimmable model
 // (or container) that currently run different sub-models: workgroups [first, next group's first) belong to group g, each
@@ -220,9 +309,7 @@ hipError_t launch_kt_mfma(const A1Args& a, int n_blocks, int nk, int channels, i
 hipError_t launch_lstm(const LSTMArgs& a, hipStream_t stream);
 hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream);
 hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream); // hidden <= 4: one gate row per lane
-bool lstm_row_eligible(const LSTMArgs& a);
 hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream); // 5 .. 32 hidden units: two gate rows per lane
-bool lstm_wide_eligible(const LSTMArgs& a);
 int lstm_lds_bytes(const LSTMArgs& a);
 long lstm_scratch_floats(const LSTMArgs& a); // > 0: the lanes = streams kernel keeps its columns in global scratch
 hipError_t launch_fill_state(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
