@@ -80,7 +80,13 @@ constexpr int depth_in(int job) { return (is_big(job) && !res(job)) ? 4 : 2; }
 #else
 constexpr int depth_in(int) { return 2; }
 #endif
-constexpr int in_rows(int job) { return res(job) ? ring_len(job) : takes_area(job) ? (is_big(job) ? 16 * depth_in(job) : kBlockF) : 0; }
+// A big layer's resident ring is followed by a MIRROR of its first 15 rows (rows R .. R + 14 = rows 0 .. 14): the sixteen rows
+// (p + n) mod R, n = 0 .. 15, of any position p in [0, R) are then the rows p + n, one lane-invariant address plus a wave-uniform
+// offset, with no per-lane wrap. Whoever stores rows of such a ring stores the mirrored ones twice; the mirror is rebuilt from the
+// stream state when a launch starts and never goes back into it. (The small layers read 64 rows at a time: no mirror there.)
+constexpr int kMirror = 15;
+constexpr int mirror_rows(int job) { return is_big(job) && res(job) ? kMirror : 0; }
+constexpr int in_rows(int job) { return res(job) ? ring_len(job) + mirror_rows(job) : takes_area(job) ? (is_big(job) ? 16 * depth_in(job) : kBlockF) : 0; }
 constexpr int plane_b(int job) { return (in_rows(job) * 16 + 255) / 256 * 256; }
 constexpr int in_bytes(int job) { return plane_b(job) * (chans(job) / 4); }
 
@@ -124,6 +130,14 @@ constexpr int in_b(int job)
 }
 constexpr int kLdsBytes = in_b(kJobs);
 static_assert(kLdsBytes <= 160 * 1024, "aq LDS layout");
+constexpr bool mirrors_fit()
+{
+  for (int j = 0; j < kJobs; j++)
+    if (mirror_rows(j) && ((ring_len(j) + kMirror) * 16 > plane_b(j) || ring_len(j) < 2 * 16 + kMirror))
+      return false;
+  return true;
+}
+static_assert(mirrors_fit(), "aq: a mirror lies behind its ring's live rows, inside the ring's plane");
 static_assert(kFlagB % 16 == 0 && kSlotB0 % 16 == 0 && kSubSlot % 16 == 0 && kBigSlot % 16 == 0 && kSmallSlot % 16 == 0, "aq LDS alignment");
 } // namespace aq
 } // namespace namhip

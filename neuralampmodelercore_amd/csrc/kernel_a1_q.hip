@@ -45,9 +45,12 @@ __device__ void aq_sb_store4(mf::f4 v, aq_i4 rsrc, int vindex, int voffset, int 
 // differs between instantiations of one kernel (it depends on the code around the expression), and a session must render
 // bit for bit what a plain launch renders (tests/test_gpu_breadth.py: test_pipelined_kernel_against_the_four_wave_kernel).
 // Fasttanh: NAM/activations.h:91-98 (the rational, rearranged: see below); Tanh: 1 - 2 / (exp(2 x) + 1).
+// c_t1, c_t2: Fasttanh's two additive constants. A caller that runs in a loop passes them in vector registers it has set up once
+// (the packed multiply-adds take one scalar operand, so the compiler otherwise moves both into registers again per call).
+constexpr float kAqT1 = 0.893229853513558f, kAqT2 = (float)(2.45550750702956 - 2.44506634652299 * 0.893229853513558);
 #pragma clang fp contract(off)
 template <int ACT_T>
-__device__ __forceinline__ mf::f4 aq_act4(const mf::f4& v)
+__device__ __forceinline__ mf::f4 aq_act4(const mf::f4& v, float c_t1 = kAqT1, float c_t2 = kAqT2)
 {
   mf::f4 r;
 #pragma unroll
@@ -59,12 +62,12 @@ __device__ __forceinline__ mf::f4 aq_act4(const mf::f4& v)
       // x (a + a |x| + (b + c |x|) x^2) / (d + (d + x^2) |x + e x |x||) in ten instructions instead of eleven: |x + e x |x|| =
       // |x| (1 + e |x|) (e > 0), and with q = x^2 + d the numerator / x is t1 q + (t2 - d t1), whose second factor is linear
       // in |x| like t2 — x^2 never exists by itself (kernel_lstm.hip: lrow::ratio)
-      constexpr float kA1 = (float)(2.45550750702956 - 2.44506634652299 * 0.821226666969744), kA0 = (float)(2.45550750702956 - 2.44506634652299 * 0.893229853513558);
+      constexpr float kA1 = (float)(2.45550750702956 - 2.44506634652299 * 0.821226666969744);
       const float ax = __builtin_fabsf(x);
       const float q = __builtin_fmaf(ax, ax, 2.44506634652299f);
       const float w = __builtin_fmaf(0.814642734961073f, ax, 1.0f);
-      const float t1 = __builtin_fmaf(0.821226666969744f, ax, 0.893229853513558f);
-      const float t2 = __builtin_fmaf(kA1, ax, kA0);
+      const float t1 = __builtin_fmaf(0.821226666969744f, ax, c_t1);
+      const float t2 = __builtin_fmaf(kA1, ax, c_t2);
       const float den = __builtin_fmaf(q, ax * w, 2.44506634652299f);
       const float n = __builtin_fmaf(t1, q, t2);
       r[i] = (n * __builtin_amdgcn_rcpf(den)) * x;
@@ -299,6 +302,50 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
   auto prod_b = [&](int b) { return flag_b + (unsigned)(16 + 2 * b) * 4u; };
   auto cons_b = [&](int b) { return flag_b + (unsigned)(16 + 2 * b + 1) * 4u; };
 
+  // The big stages' LDS accesses take the address as a number — the workgroup's LDS starts at lds0 — so that a lane's invariant
+  // part (lds0 included) lives in one register and an access adds one scalar to it; sreg() keeps the compiler from taking such a
+  // scalar apart again (into a shift-add and a vector add of what is left)
+  using lds_f4_ptr = __attribute__((address_space(3))) mf::f4*;
+  using lds_f_ptr = __attribute__((address_space(3))) float*;
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds_aq;
+  auto lds_ld4_at = [](unsigned addr) { return *(lds_f4_ptr)(size_t)addr; };
+  auto lds_st4_at = [](unsigned addr, const mf::f4& v) { *(lds_f4_ptr)(size_t)addr = v; };
+  auto sreg = [](unsigned v) {
+    asm("" : "+s"(v));
+    return v;
+  };
+  // Sixteen rows of a big layer's resident ring from position `so` on, by the lanes whose part of a row address is `lane_b`
+  // (plane + 16 n): the rows so + n as they lie — the ring's mirror makes them addressable without a wrap (aq_table.h) — and,
+  // when some of them have a second copy (so in the first 15 rows, or the sixteen rows run over the ring's end), those again
+  auto store_rows = [&](auto r_tag, unsigned lane_b, int so, const mf::f4& v) {
+    constexpr int R = decltype(r_tag)::value;
+    const unsigned at = lane_b + sreg((unsigned)so * 16u);
+    lds_st4_at(at, v);
+    if (so < aq::kMirror || so > R - 16) // (wave-uniform)
+    {
+      // lanes below `thr` hold rows of the ring's head (copy: R rows on), the others rows beyond its end (copy: R rows back), or
+      // a row with one copy only, stored once more where it is
+      const bool low = so < aq::kMirror;
+      const int thr = (low ? aq::kMirror : R) - so;
+      const int d = (lane & 15) < thr ? (low ? R * 16 : 0) : (low ? 0 : -R * 16);
+      lds_st4_at(at + (unsigned)d, v);
+    }
+  };
+  // Sixteen rows (t + n) mod R of an HBM ring (descriptor rs, rows of row_b bytes), t wave-uniform in [0, R): unless they run over
+  // the ring's end the lane's row index is n and t goes into the scalar offset — no vector arithmetic per access
+  auto far_load = [&](i4 rs, auto r_tag, int t, int voff, int ring_off_b, int row_b) {
+    constexpr int R = decltype(r_tag)::value;
+    mf::f4 v;
+    if (t + 16 <= R)
+      v = aq_sb_load4(rs, lane & 15, voff, ring_off_b + t * row_b, 0);
+    else
+    {
+      v = aq_sb_load4(rs, (int)wrap_row(t, (unsigned)(lane & 15), R), voff, ring_off_b, 0);
+      asm volatile("" ::: "memory"); // (two loads, not one behind a select of its operands)
+    }
+    return v;
+  };
+
   // a resident ring: stream state <-> LDS planes. 16-channel rings: lane (g, n) moves the quad g of row r0 + n; 8-channel
   // rings: lane (h = lane & 1, r = lane >> 1) the quad h of row r0 + r. Every request of a ring is in flight before the
   // first row is stored (one memory round trip per ring, not one per sixteen rows: a launch of a few buffers pays for it)
@@ -321,6 +368,8 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
       const int row = i * per + rl;
       if (row < R)
         lds_st4(lds, lds_b + pl * plane_b + (unsigned)row * 16u, t[i]);
+      if (wide && i == 0 && row < aq::kMirror) // a big layer's ring: its first rows once more behind its end (aq_table.h)
+        lds_st4(lds, lds_b + pl * plane_b + (unsigned)(R + row) * 16u, t[i]);
     }
   };
   auto lds_to_ring = [&](auto r_tag, int ring_off_f, unsigned lds_b, unsigned plane_b, auto wide_tag) {
@@ -436,6 +485,17 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     for (int u = 0; u < NJS; u++)
       gb[u] = (unsigned)aq::in_b(J0 + u) + (unsigned)g * (unsigned)aq::plane_b(J0 + u);
     const unsigned gbn = (unsigned)aq::in_b(JN) + (unsigned)g * (unsigned)aq::plane_b(JN);
+    // ... and of everything a sub-block touches: these are loop-invariant, what moves (ring positions, the slot's sub-block) is
+    // wave-uniform and added as a scalar. Rings: row n of the plane; slots: row n of the head plane, word n of the input samples
+    const unsigned n16 = lds0 + (unsigned)n * 16u;
+    unsigned gl[NJS];
+#pragma unroll
+    for (int u = 0; u < NJS; u++)
+      gl[u] = gb[u] + n16;
+    const unsigned gln = gbn + n16;
+    constexpr unsigned islot_ = (unsigned)aq::slot_b(QIN < 0 ? 0 : QIN), oslot_ = (unsigned)aq::slot_b(QOUT);
+    const unsigned hd_in = islot_ + g16 * (unsigned)(DIN * 16) + n16, cnd_in = lds0 + islot_ + (unsigned)(DIN * 1024) + (unsigned)n * 4u;
+    const unsigned hd_out = oslot_ + g16 * (unsigned)(DOUT * 16) + n16, cnd_out = lds0 + oslot_ + (unsigned)(DOUT * 1024) + (unsigned)n * 4u;
     // resident rings of this stage: state -> LDS
     il::for_each_index(
       [&](auto u_tag) {
@@ -451,7 +511,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
       constexpr int R = aq::ring_len(TJ), D = aq::dil(TJ), FI = aq::far_jobs_before(SS, TJ);
 #pragma unroll
       for (int j = 0; j < 2; j++)
-        far[FI][j] = aq_sb_load4(rs16, (int)wrap_row(wrap_s(sb - (2 - j) * D, R), (unsigned)n, R), (int)g16, aq::ring_off(TJ) * 4, 0);
+        far[FI][j] = far_load(rs16, std::integral_constant<int, R>{}, wrap_s(sb - (2 - j) * D, R), (int)g16, aq::ring_off(TJ) * 4, aq::kC0 * 4);
     };
     il::for_each_index(
       [&](auto u_tag) {
@@ -485,6 +545,8 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     if constexpr (DBG)
       dbg_t[1] = clock64();
 
+    float c_t1 = kAqT1, c_t2 = kAqT2; // (aq_act4: in vector registers for the whole launch)
+    asm volatile("" : "+v"(c_t1), "+v"(c_t2));
     f4 xs, hd;
     float cnd = 0.0f;
     unsigned long long spec_cmd = 0; // PERSIST, stage 0: the early look at the next command ...
@@ -492,6 +554,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     int k = 0; // buffers finished by this stage
     int m = 0; // sub-blocks finished by this stage (4 k + i, modulo 2^32: the words are compared through differences)
     int i = 0; // sub-block of the buffer
+    int m1 = 0; // m + 1 (a vector register)
 
     // One layer on one sub-block: z = act(conv(x) + mixin(cond)); head += z; x += layer1x1(z)   (model.cpp:183-393)
     auto job = [&](auto j_tag) {
@@ -506,28 +569,36 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
       int sb = wpj + 16 * i; // ring position of the sub-block's first frame (scalar unit)
       sb -= sb >= R ? R : 0;
       // (a) the sub-block's input rows
-      const unsigned row_cur = (RES || !TAKES) ? wrap_row(sb, (unsigned)n, R) : (unsigned)(16 * (m & (DIN - 1)) + n);
       if constexpr (TAKES)
-        xs = lds_ld4(lds, gb[U] + row_cur * 16u);
+        xs = lds_ld4_at(gl[U] + sreg(RES ? (unsigned)sb * 16u : (unsigned)(m & (DIN - 1)) * 256u));
       else if constexpr (RES)
       {
-        lds_st4(lds, gb[U] + row_cur * 16u, xs);
+        store_rows(std::integral_constant<int, R>{}, gl[U], sb, xs);
         asm volatile("" ::: "memory"); // the taps read OTHER lanes' rows: not above this store
       }
       if constexpr (!RES)
-        aq_sb_store4(xs, rs16, 16 * i + n < nvalid ? (int)wrap_row(sb, (unsigned)n, R) : aq::kNoRow, (int)g16, aq::ring_off(JI) * 4, kAppAux);
+      {
+        // (a session's buffers are whole; elsewhere only a launch's last buffer is ragged)
+        if ((PERSIST || 16 * i + 16 <= nvalid) && sb + 16 <= R)
+          aq_sb_store4(xs, rs16, n, (int)g16, aq::ring_off(JI) * 4 + sb * (aq::kC0 * 4), kAppAux);
+        else
+        {
+          aq_sb_store4(xs, rs16, (PERSIST || 16 * i + n < nvalid) ? (int)wrap_row(sb, (unsigned)n, R) : aq::kNoRow, (int)g16, aq::ring_off(JI) * 4, kAppAux);
+          asm volatile("" ::: "memory");
+        }
+      }
       // (b) the taps' rows: LDS ring, or the registers requested a sub-block ago
       f4 bt[2];
 #pragma unroll
       for (int j = 0; j < 2; j++)
       {
         if constexpr (RES)
-          bt[j] = lds_ld4(lds, gb[U] + wrap_row(wrap_s(sb - (2 - j) * D, R), (unsigned)n, R) * 16u);
+          bt[j] = lds_ld4_at(gl[U] + sreg((unsigned)wrap_s(sb - (2 - j) * D, R) * 16u));
         else
           bt[j] = far[FI][j];
       }
       if constexpr (TAKES)
-        set_word(cons_b(QIN), m + 1); // every LDS read of what the previous stage may overwrite next is issued
+        set_word(cons_b(QIN), m1); // every LDS read of what the previous stage may overwrite next is issued
       // persistent session, stage 0: look at the next ring slot in the buffer's first sub-block and, when the command is
       // already there, request the next buffer's input sample from it in the third (kernel_kq.hip)
       if constexpr (PERSIST && JI == 0)
@@ -568,7 +639,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(W[U][2][s_], xs[s_], acc, 0, 0, 0);
       // (d) activation, head accumulator, layer 1x1 + residual
       const f4 b1v = cst[U][2];
-      const f4 z = aq_act4<ACT_T>(acc);
+      const f4 z = aq_act4<ACT_T>(acc, c_t1, c_t2);
       hd += z;
       xs += b1v;
 #pragma unroll
@@ -619,6 +690,8 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
 #pragma unroll 1
       for (i = 0; i < 4; i++)
       {
+        unsigned a_hd = 0, a_cnd = 0; // this lane's head row and input sample in the input slot
+        asm volatile("v_mov_b32 %0, %1" : "=v"(m1) : "s"(m + 1)); // the sub-block's number for both hand-over words, in a vector register once
         if constexpr (FIRST)
         {
           // array 0's rechannel (1 -> 16, model.cpp:488-490): x = column * input
@@ -633,9 +706,11 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
             wait_in(prod_b(QIN), m + 1);
             asm volatile("" ::: "memory");
           }
-          const unsigned qr = (unsigned)(16 * (m & (DIN - 1)) + n); // the sub-block's rows in the slot
-          hd = lds_ld4(lds, islot + g16 * (unsigned)(DIN * 16) + qr * 16u);
-          cnd = *reinterpret_cast<const float*>(lds + islot + (unsigned)(DIN * 1024) + qr * 4u);
+          const unsigned qs = (unsigned)(m & (DIN - 1)); // the sub-block's place in the slot
+          a_hd = hd_in + sreg(qs * 256u);
+          a_cnd = cnd_in + sreg(qs * 64u);
+          hd = lds_ld4_at(a_hd);
+          cnd = *(lds_f_ptr)(size_t)a_cnd;
         }
         il::for_each_index([&](auto u_tag) { job(std::integral_constant<int, J0 + decltype(u_tag)::value>{}); },
                            std::make_integer_sequence<int, NJS>{});
@@ -647,16 +722,28 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
         {
           int so = wpo + 16 * i;
           so -= (aq::res(JN) && so >= aq::ring_len(JN)) ? aq::ring_len(JN) : 0;
-          const unsigned qr = (unsigned)(16 * (m & (DOUT - 1)) + n);
-          const unsigned row = aq::res(JN) ? wrap_row(so, (unsigned)n, aq::ring_len(JN)) : qr;
-          lds_st4(lds, gbn + row * 16u, xs);
-          lds_st4(lds, oslot + g16 * (unsigned)(DOUT * 16) + qr * 16u, hd);
+          const unsigned qs = (unsigned)(m & (DOUT - 1));
+          if constexpr (aq::res(JN))
+            store_rows(std::integral_constant<int, aq::ring_len(JN)>{}, gln, so, xs);
+          else
+            lds_st4_at(gln + sreg(qs * 256u), xs);
+          // (slots of one depth: the sub-block's place in the output slot is its place in the input slot, a constant on)
+          if constexpr (FIRST || DIN != DOUT)
+          {
+            a_hd = hd_out + sreg(qs * 256u) - (oslot_ - islot_);
+            a_cnd = cnd_out + sreg(qs * 64u) - (oslot_ - islot_);
+          }
+          lds_st4_at(a_hd + (oslot_ - islot_), hd);
           if (g == 0)
-            *reinterpret_cast<float*>(lds + oslot + (unsigned)(DOUT * 1024) + qr * 4u) = cnd;
-          if (i == 0 && lane == 0)
-            *reinterpret_cast<i4*>(lds + oslot + (unsigned)(DOUT * 1024 + DOUT * 64)) = i4{(int)boff, nvalid, 0, more ? 1 : 0};
+            *(lds_f_ptr)(size_t)(a_cnd + (oslot_ - islot_)) = cnd;
+          if (i == 0) // (a scalar branch around the one-lane store, not a lane mask computed per sub-block)
+          {
+            asm volatile("" ::: "memory");
+            if (lane == 0)
+              *reinterpret_cast<i4*>(lds + oslot + (unsigned)(DOUT * 1024 + DOUT * 64)) = i4{(int)boff, nvalid, 0, more ? 1 : 0};
+          }
         }
-        set_word(prod_b(QOUT), m + 1);
+        set_word(prod_b(QOUT), m1);
         m = (int)((unsigned)m + 1u);
         if constexpr (DBG)
         {
