@@ -264,8 +264,10 @@ protected:
 };
 
 // A model bank (not in the reference; include/nam_hip.h: nam_hip_bank_create): loaded models that ONE BatchDSP runs side by
-// side, each stream bound to one member — a host that serves many captures of the official WaveNet topology (standard, lite,
-// feather; all loaded with the same fast tanh setting). A value type: copies share the immutable bank. Construction throws
+// side, each stream bound to one member — a host that serves many captures of ONE family: the official WaveNet topology
+// (standard, lite, feather; all loaded with the same fast tanh setting), or the A2 topology (A2-Full-shaped WaveNets and
+// containers such as A2.nam, which stand for their largest submodel; one activation type, the LeakyReLU slope and head_scale
+// per member; nam_kq_kernel / nam_kt_mfma_kernel). A value type: copies share the immutable bank. Construction throws
 // std::runtime_error (naming the member) when the models cannot share a launch.
 class ModelBank
 {

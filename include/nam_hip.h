@@ -192,11 +192,19 @@ NAM_HIP_API void nam_hip_batch_destroy(nam_hip_batch* batch);
 /* ---- model banks: one batch whose streams each run their own model ("captures") ----
  * A host that serves captures runs one architecture with many weight sets. A bank is an immutable set of loaded models that
  * ONE batch runs side by side — one launch, one session, one ticket queue — each stream bound to one member.
- * nam_hip_bank_create is host-only (no device call). It accepts a set when every member plans onto the same instantiation of
- * the interleaved-frame kernels with the same blob and state layout: the official WaveNet topology (two arrays of ten layers,
- * kernel size 3, dilations 1 .. 512) at 16 / 8 channels — the lite 12 / 6 and feather 8 / 4 sizes are zero-padded to it at plan
- * time —, all members Tanh or all Fasttanh (so: loaded with the same fast_tanh), no lookup tables. The plans are compared field
- * by field; the first difference — or a member of another kind: LSTM, nano, A2, FiLM / gated models, another activation, a
+ * nam_hip_bank_create is host-only (no device call). A bank is of ONE family, decided by member 0, and accepts a set when every
+ * member plans onto the same instantiation of that family's kernels with the same blob and state layout:
+ *  - the interleaved-frame kernels: the official WaveNet topology (two arrays of ten layers, kernel size 3, dilations 1 .. 512)
+ *    at 16 / 8 channels — the lite 12 / 6 and feather 8 / 4 sizes are zero-padded to it at plan time —, all members Tanh or all
+ *    Fasttanh (so: loaded with the same fast_tanh), no lookup tables;
+ *  - the A2 family (nam_kq_kernel, nam_kt_mfma_kernel): WaveNets of the A2 topology (one array of 8 channels, 23 layers with
+ *    kernel sizes 6 / 15, a 16-tap head rechannel) whose activation nam_kq_kernel is compiled for — exactly the models whose
+ *    one-model batch is session-eligible on that kernel. All members share the activation TYPE (all LeakyReLU, all ReLU, all
+ *    Tanh or all Fasttanh); the LeakyReLU negative slope (<= 1) is per member, like head_scale. A SlimmableContainer (how A2
+ *    captures ship: A2.nam holds A2-Lite and A2-Full) may be a member when its LARGEST submodel qualifies; the member IS that
+ *    submodel — the one a batch of the container runs while no size has been set. No lookup tables.
+ * The plans are compared field by field; the first difference — a member of the other family, or of another kind: LSTM, nano,
+ * A2-Lite, FiLM / gated models, another activation type, a
  * slimmable model — is refused with NAM_HIP_ERR_UNSUPPORTED and a message naming the member index and the field. n_models <= 0
  * or a NULL member: NAM_HIP_ERR_INVALID_ARGUMENT. A bank of one model is legal. The bank copies what it needs: the models may
  * be freed right after, and the bank may be freed while batches created from it live. */
@@ -208,10 +216,15 @@ NAM_HIP_API int nam_hip_bank_n_models(const nam_hip_bank* bank);
  * [0, n_models) is NAM_HIP_ERR_INVALID_ARGUMENT). The result is an ordinary batch: reset, process_*, render, set_persistent,
  * flush, submit / wait, synchronize, kernel_name* and n_streams work as for one model; set_slimmable_size returns what it
  * returns for a non-slimmable model. The members' weights live in one device allocation [member][blob]; a workgroup resolves
- * its stream's member once, in the kernel's prologue. Kernels: the NAM_HIP_KERNEL_A1_IL family for every launch shape —
- * nam_a1_q_kernel in sessions and launches of several buffers, nam_a1_p4_kernel for short bursts and short blocking calls,
- * nam_a1_p2_kernel for a lone buffer (where a one-model batch under AUTO runs nam_a1_mfma_kernel, which knows no banks);
- * nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_A1_IL, anything else is NAM_HIP_ERR_UNSUPPORTED.
+ * its stream's member once, in the kernel's prologue. Kernels of a bank of the official topology: the NAM_HIP_KERNEL_A1_IL
+ * family for every launch shape — nam_a1_q_kernel in sessions and launches of several buffers, nam_a1_p4_kernel for short
+ * bursts and short blocking calls, nam_a1_p2_kernel for a lone buffer (where a one-model batch under AUTO runs
+ * nam_a1_mfma_kernel, which knows no banks); nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_A1_IL,
+ * anything else is NAM_HIP_ERR_UNSUPPORTED. Kernels of an A2 bank: what a one-model A2 batch runs under AUTO — nam_kq_kernel
+ * in sessions and launches of several buffers (renders, the prewarm of Reset), nam_kt_mfma_kernel for a lone buffer and for
+ * everything under NAM_HIP_MAX_STAGES=1; nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_A1_MFMA,
+ * anything else is NAM_HIP_ERR_UNSUPPORTED; one launch of more than 2^28 frames (which a one-model batch hands to
+ * nam_a1_kernel) is NAM_HIP_ERR_UNSUPPORTED: split it.
  * Reset with prewarm runs the silence through every stream with its own member's weights (no cached image: it depends on the
  * weights); the state equals, bit for bit, what a one-model batch of that member holds after the same Reset. */
 NAM_HIP_API int nam_hip_batch_create_bank(const nam_hip_bank* bank, int device, int n_streams, int max_frames,

@@ -1,12 +1,18 @@
 // api_bank.cpp — model banks (include/nam_hip.h: nam_hip_bank_create, nam_hip_batch_create_bank): which models may share a
 // batch, the bank's host image, a bank batch's device image and the per-stream member binding. See api_internal.h.
 //
-// What a bank holds per member is the part of the plan's blob the interleaved-frame kernels read — from A1Plan::ws_tiles_off to
-// the end: tiles | extra tiles | constants | rechannel column | nam_a1_q_kernel's weight block — and the two scalars they take
-// by value (head_scale, act_p0). In front of that region a plan keeps the op program's weights in the model's OWN channel
-// counts, so the region starts at another offset in a lite or feather model than in a standard one; inside it the layout is
-// the padded 16 / 8 topology's and the same for every member. The launch arguments of a bank batch are therefore offsets from
-// the region's start (launch_group), and the comparison below is made on those.
+// A bank is of ONE family (BankFamily), decided by member 0:
+//  * BANK_A1_IL: the official WaveNet topology on the interleaved-frame kernels. What the bank holds per member is the part of
+//    the plan's blob those kernels read — from A1Plan::ws_tiles_off to the end: tiles | extra tiles | constants | rechannel column
+//    | nam_a1_q_kernel's weight block. In front of that region a plan keeps the op program's weights in the model's OWN channel
+//    counts, so the region starts at another offset in a lite or feather model than in a standard one; inside it the layout is
+//    the padded 16 / 8 topology's and the same for every member. The launch arguments of such a bank batch are therefore offsets
+//    from the region's start (launch_group), and the comparison below is made on those.
+//  * BANK_A2: the A2 topology (kp_table.h) on nam_kq_kernel / nam_kt_mfma_kernel. Every member has the same channel counts, so
+//    the WHOLE blob has one layout: the bank keeps whole blobs (base offset 0) and A1Plan's absolute offsets (kt_desc[].tile_off,
+//    kt_rech_off, kt_lds_src_off, kq_w_off) hold against any member's row.
+// Per member besides the blob: the two scalars the kernels take by value (head_scale, act_p0 — on the A2 topology the LeakyReLU
+// slope, 0 for ReLU as in launch_kq).
 #include "api_internal.h"
 
 namespace namhip
@@ -15,24 +21,64 @@ namespace api
 {
 namespace
 {
-// Why `p` cannot be a bank member at all ("" = it can): the family is nam_a1_q_kernel's — the official topology at 16 / 8
-// (padded) channels with Tanh or Fasttanh — and its siblings' instantiations for that shape.
-std::string member_refusal(const nam_hip_model& m)
+const char* family_name(int f)
+{
+  return f == BANK_A2 ? "A2 (nam_kq_kernel)" : "A1_IL (nam_a1_q_kernel)";
+}
+
+// What a model stands for in a bank: its full-size plan and that plan's spec (a SlimmableContainer: its largest submodel's, the
+// one a batch runs when no size has been set).
+const Plan& member_plan(const nam_hip_model& m)
+{
+  return m.plans[m.full_width];
+}
+std::shared_ptr<ModelSpec> member_spec(const nam_hip_model& m)
+{
+  return m.spec->arch == ARCH_CONTAINER ? m.spec->submodels[(size_t)m.full_width] : m.spec;
+}
+// first float of the member's blob the bank keeps (see the head of this file)
+int member_base(const Plan& p, int family)
+{
+  return family == BANK_A1_IL ? p.a1.ws_tiles_off : 0;
+}
+
+// the A2 family: what makes a one-model batch session-eligible on nam_kq_kernel (kq_runs), nam_kt_mfma_kernel for a lone buffer
+bool a2_member(const A1Plan& a)
+{
+  return a.valid && a.kt_ok && a.kp_ok && kq_takes(a.arr[0].act, a.arr[0].act_p0);
+}
+
+// Why `m` cannot be a bank member at all ("" = it can, and *family says of which family).
+std::string member_refusal(const nam_hip_model& m, int* family)
 {
   const ModelSpec& s = *m.spec;
+  *family = BANK_A1_IL;
   if (s.arch == ARCH_LSTM)
-    return "an LSTM (banks hold WaveNets of the official topology)";
+    return "an LSTM (banks hold WaveNets of the official topology or of the A2 topology)";
   if (s.arch == ARCH_CONTAINER)
-    return "a SlimmableContainer (banks hold plain WaveNets of the official topology)";
+  {
+    // a container stands for its largest submodel, and only in the A2 family (how A2 captures ship)
+    if (m.plans.empty() || member_spec(m)->arch != ARCH_WAVENET || !a2_member(member_plan(m).a1))
+      return "a SlimmableContainer whose largest submodel is not an A2-topology WaveNet on nam_kq_kernel (kt_ok / kp_ok / kq_takes)";
+    *family = BANK_A2;
+    return "";
+  }
   if (m.slimmable())
     return "a slimmable WaveNet (its widths are separate plans; banks hold one plan per member)";
-  const Plan& p = m.plans[m.full_width];
+  const Plan& p = member_plan(m);
   const A1Plan& a = p.a1;
   if (!a.valid)
     return "outside the A1 kernel family (FiLM / gating / groups / a lookup-table or per-channel activation / a post-stack head ...)";
+  if (a2_member(a))
+  {
+    *family = BANK_A2;
+    return "";
+  }
+  if (a.kt_ok && a.kp_ok)
+    return "the A2 topology with an activation nam_kq_kernel is not compiled for (kq_takes: LeakyReLU with a slope <= 1, ReLU, Tanh, Fasttanh)";
   if (!(a.il_ok && a.p2_ok && a.q_ok && a.p2_c0 == 16 && a.p2_c1 == 8))
-    return "not the official WaveNet topology at (padded) 16 / 8 channels with Tanh or Fasttanh: no nam_a1_q_kernel plan (q_ok / p2_c0 / "
-           "p2_c1)";
+    return "neither the official WaveNet topology at (padded) 16 / 8 channels with Tanh or Fasttanh (no nam_a1_q_kernel plan: q_ok / "
+           "p2_c0 / p2_c1) nor the A2 topology (no nam_kq_kernel plan: kt_ok / kp_ok)";
   if (!a1_q_takes(a.arr[0].act))
     return "an activation nam_a1_q_kernel is not compiled for (arr[0].act)";
   if (a.ws_tiles_off % 4 != 0 || a.ws_consts_off < a.ws_tiles_off || a.ws_xt_off < a.ws_tiles_off || a.q_w_off < a.ws_tiles_off
@@ -41,11 +87,11 @@ std::string member_refusal(const nam_hip_model& m)
   return "";
 }
 
-// The first field in which member `p` differs from member 0 (`q`), "" when the two run as one launch.
-std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m)
+// The first field in which member `m` differs from member 0, "" when the two run as one launch. Both are of `family`.
+std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, int family)
 {
-  const Plan& q = m0.plans[m0.full_width];
-  const Plan& p = m.plans[m.full_width];
+  const Plan& q = member_plan(m0);
+  const Plan& p = member_plan(m);
   const A1Plan& a = p.a1;
   const A1Plan& b = q.a1;
   std::string out;
@@ -53,7 +99,8 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m)
     if (out.empty() && x != y)
       out = std::string(field) + " (" + std::to_string(x) + " vs " + std::to_string(y) + ")";
   };
-  cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
+  if (family == BANK_A1_IL)
+    cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
   cmp("in_channels", p.in_channels, q.in_channels);
   cmp("out_channels", p.out_channels, q.out_channels);
   cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples);
@@ -65,7 +112,7 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m)
   for (int i = 0; i < a.n_arrays && i < kA1MaxArrays; i++)
   {
     const A1Array &x = a.arr[i], &y = b.arr[i];
-    cmp("a1.arr.act (ACT_T)", x.act, y.act);
+    cmp("a1.arr.act (ACT_T)", x.act, y.act); // (A2: after the fast_tanh rewrite; the slope is per member)
     cmp("a1.arr.channels", x.channels, y.channels);
     cmp("a1.arr.kernel", x.kernel, y.kernel);
     cmp("a1.arr.n_layers", x.n_layers, y.n_layers);
@@ -77,6 +124,32 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m)
       cmp("a1.arr.ring_len", x.ring_len[l], y.ring_len[l]);
       cmp("a1.arr.ring_id", x.ring_id[l], y.ring_id[l]);
     }
+  }
+  if (family == BANK_A2)
+  {
+    // what nam_kq_kernel and nam_kt_mfma_kernel take from the plan (the device A1Plan is member 0's), absolute blob offsets
+    cmp("blob floats", (long long)p.blob.size(), (long long)q.blob.size());
+    cmp("kt_chunks", a.kt_chunks, b.kt_chunks);
+    cmp("kt_nk", a.kt_nk, b.kt_nk);
+    for (int c = 0; c < a.kt_chunks && c < kKtChunkMax; c++)
+    {
+      const KtDesc &x = a.kt_desc[c], &y = b.kt_desc[c];
+      cmp("kt_desc.flags", x.flags, y.flags);
+      cmp("kt_desc.ntaps", x.ntaps, y.ntaps);
+      cmp("kt_desc.tile_off", x.tile_off, y.tile_off);
+      cmp("kt_desc.w1_off", x.w1_off, y.w1_off);
+      cmp("kt_desc.consts_off", x.consts_off, y.consts_off);
+      cmp("kt_desc.ring_b", x.ring_b, y.ring_b);
+      cmp("kt_desc.R", x.R, y.R);
+      cmp("kt_desc.ring_id", x.ring_id, y.ring_id);
+      for (int i = 0; i < kKtTaps; i++)
+        cmp("kt_desc.L", x.L[i], y.L[i]);
+    }
+    cmp("kt_rech_off", a.kt_rech_off, b.kt_rech_off);
+    cmp("kt_lds_src_off", a.kt_lds_src_off, b.kt_lds_src_off);
+    cmp("kt_lds_floats", a.kt_lds_floats, b.kt_lds_floats);
+    cmp("kq_w_off", a.kq_w_off, b.kq_w_off);
+    return out;
   }
   cmp("a1.p2_c0", a.p2_c0, b.p2_c0);
   cmp("a1.p2_c1", a.p2_c1, b.p2_c1);
@@ -175,34 +248,44 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
     if (!models[i])
       return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_bank_create: member " + std::to_string(i) + " is NULL");
   return guarded([&]() -> int {
+    int family = BANK_A1_IL;
     for (int i = 0; i < n_models; i++)
     {
-      const std::string why = member_refusal(*models[i]);
+      int fam = BANK_A1_IL;
+      const std::string why = member_refusal(*models[i], &fam);
       if (!why.empty())
         return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_bank_create: member " + std::to_string(i) + " is " + why);
-      const std::string diff = i ? first_difference(*models[0], *models[i]) : std::string();
+      if (i == 0)
+        family = fam;
+      std::string diff;
+      if (fam != family)
+        diff = std::string("family (") + family_name(fam) + " vs " + family_name(family) + "; a bank is of one family)";
+      else if (i)
+        diff = first_difference(*models[0], *models[i], family);
       if (!diff.empty())
         return fail(NAM_HIP_ERR_UNSUPPORTED,
                     "nam_hip_bank_create: member " + std::to_string(i) + " differs from member 0 in " + diff);
     }
     auto data = std::make_shared<nam_hip_bank_data>();
     const nam_hip_model& m0 = *models[0];
-    data->proto.spec = m0.spec;
-    data->proto.plans.push_back(m0.plans[m0.full_width]);
+    const Plan& p0 = member_plan(m0);
+    data->family = family;
+    data->proto.spec = member_spec(m0); // (a container member: the submodel's — a bank batch is not slimmable)
+    data->proto.plans.push_back(p0);
     data->proto.width_channels.push_back({});
     data->proto.full_width = 0;
     data->n_members = n_models;
-    const Plan& p0 = m0.plans[m0.full_width];
-    const size_t region = p0.blob.size() - (size_t)p0.a1.ws_tiles_off;
+    const size_t region = p0.blob.size() - (size_t)member_base(p0, family);
     data->blob_stride = (long)((region + 3) / 4 * 4);
     data->blobs.assign((size_t)n_models * (size_t)data->blob_stride, 0.f);
     data->scal.resize((size_t)n_models * 2);
     for (int i = 0; i < n_models; i++)
     {
-      const Plan& p = models[i]->plans[models[i]->full_width];
-      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + p.a1.ws_tiles_off, region * sizeof(float));
+      const Plan& p = member_plan(*models[i]);
+      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + member_base(p, family), region * sizeof(float));
       data->scal[2 * (size_t)i] = p.blob[(size_t)p.a1.head_scale_off];
-      data->scal[2 * (size_t)i + 1] = p.a1.arr[0].act_p0;
+      // nam_kq_kernel runs ReLU as LeakyReLU with slope 0 (launch_kq does the same for one model)
+      data->scal[2 * (size_t)i + 1] = (family == BANK_A2 && p.a1.arr[0].act == ACT_RELU) ? 0.0f : p.a1.arr[0].act_p0;
     }
     nam_hip_bank* bank = new nam_hip_bank();
     bank->data = std::move(data);

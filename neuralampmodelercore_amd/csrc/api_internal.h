@@ -92,15 +92,22 @@ struct nam_hip_model
   }
 };
 
-// A model bank (nam_hip_bank_create): models that plan onto ONE instantiation of the interleaved-frame kernels (nam_a1_q_kernel
-// and its siblings) with the same blob layout, so that one launch can run them side by side, each workgroup on its stream's
-// member. Immutable host data, self-contained (nothing of the member models is referenced after creation); a batch created
+// A model bank (nam_hip_bank_create): models that plan onto ONE instantiation of a kernel family — the interleaved-frame kernels
+// (nam_a1_q_kernel and its siblings: BANK_A1_IL) or the A2 topology's (nam_kq_kernel, nam_kt_mfma_kernel: BANK_A2) — with the
+// same blob layout, so that one launch can run them side by side, each workgroup on its stream's member. Immutable host data, self-contained (nothing of the member models is referenced after creation); a batch created
 // from it shares ownership of `data`, so the handle may be freed while batches live.
+enum BankFamily : int
+{
+  BANK_A1_IL = 0, // the official WaveNet topology at (padded) 16 / 8 channels
+  BANK_A2 = 1 // the A2 topology (kp_table.h)
+};
 struct nam_hip_bank_data
 {
-  nam_hip_model proto; // member 0's spec and full-size plan: everything a batch asks its model that is not a weight
+  nam_hip_model proto; // member 0's spec and full-size plan (a container member: its largest submodel's): everything a batch asks
+                       // its model that is not a weight
+  int family = BANK_A1_IL; // decided by member 0 (api_bank.cpp)
   int n_members = 0;
-  long blob_stride = 0; // floats per member in `blobs`: the plan's blob size rounded up to a multiple of four (16-byte records)
+  long blob_stride = 0; // floats per member in `blobs`: the kept part of the plan's blob (api_bank.cpp) rounded up to a multiple of four (16-byte records)
   std::vector<float> blobs; // [n_members][blob_stride]
   std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal)
 };

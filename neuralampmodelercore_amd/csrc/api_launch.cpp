@@ -97,8 +97,10 @@ constexpr size_t kKtAutoMaxStreams = 1024;
 
 int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
 {
-  if (g.d_bank_member) // a model bank: the interleaved-frame family for every launch shape (the other kernels know no banks)
-    return NAM_HIP_KERNEL_A1_IL;
+  // a model bank runs its family's kernels for every launch shape (the other kernels know no banks): the interleaved-frame family,
+  // or what a one-model A2 batch runs under AUTO (select_kernel: nam_kq_kernel / nam_kt_mfma_kernel)
+  if (g.d_bank_member)
+    return b->bank->family == BANK_A2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL;
   const bool a1 = g.plan->a1.valid && g.d_a1;
   const bool mfma = a1 && (g.plan->a1.ws_ok || g.plan->a1.kt_ok);
   const bool il = a1 && g.plan->a1.il_ok && g.plan->a1.p2_ok; // the interleaved-frame kernels: the official topologies (compile-time job tables)
@@ -546,8 +548,12 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
   a.bank_scal = g.d_bank_scal;
   a.bank_stride = g.bank_stride;
   const bool il = fn == FN_A1_P2 || fn == FN_A1_P4 || fn == FN_A1_Q;
-  if (g.d_bank_member && !il)
-    return fail(NAM_HIP_ERR_UNSUPPORTED, "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank");
+  if (g.d_bank_member && !(b->bank->family == BANK_A2 ? (fn == FN_KQ || fn == FN_KT_MFMA) : il))
+    return fail(NAM_HIP_ERR_UNSUPPORTED,
+                b->bank->family == BANK_A2
+                  ? "model bank (A2 family): only nam_kq_kernel and nam_kt_mfma_kernel run it; a launch beyond 2^28 frames would take "
+                    "nam_a1_kernel, which knows no banks: split the launch"
+                  : "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank");
   if (il)
   {
     const int act = uniform_act(p.a1);

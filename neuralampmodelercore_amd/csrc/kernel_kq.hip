@@ -146,7 +146,7 @@ constexpr int w1_b(int layer) { return kTilesB + (kTaps + layer) * kTileB; }
 constexpr int const_b(int job) { return kConstsB + job * kConstB; }
 } // namespace kq
 
-template <int ACT_T, bool WT, bool PERSIST>
+template <int ACT_T, bool WT, bool PERSIST, bool BANK = false>
 __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __restrict__ blob, const A1Args a)
 {
   using namespace mf;
@@ -169,8 +169,9 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
   const int frame = lane; // this lane's frame inside the buffer
   const float* in = a.in ? a.in + (size_t)stream * a.io_stride : nullptr;
   float* out = a.out ? a.out + (size_t)stream * a.io_stride : nullptr;
-  const float head_scale = a.head_scale;
-  const float act_p0 = a.act_p0;
+  const il::Weights w = il::weights_of<BANK>(blob, a, stream); // (a model bank: the stream's member, il_common.h)
+  const float head_scale = w.head_scale;
+  const float act_p0 = w.act_p0;
   const int act = a.act; // (only read by the run-time-dispatch instantiation)
   const unsigned frame16 = (unsigned)frame * 16u; // the lane's row in a plane of 16-byte rows
   const unsigned cls64 = (unsigned)(lane & 3) * 64u; // its weight record inside a tile
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
   constexpr int kSrc4 = kq::kLdsSrcFloats / 4; // 16-byte records
   constexpr int kS4 = (kSrc4 + NT - 1) / NT;
   {
-    const f4* __restrict__ src = reinterpret_cast<const f4*>(blob + a.tiles_off);
+    const f4* __restrict__ src = reinterpret_cast<const f4*>(w.blob + a.tiles_off);
 #pragma unroll 1
     for (int i0 = 0; i0 < kS4; i0 += 4)
     {
@@ -202,8 +203,8 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
           lds_st4(lds, (unsigned)kq::kTilesB + (unsigned)((i0 + i) * NT + tid) * 16u, t[i]);
     }
   }
-  const f4 rech0 = *reinterpret_cast<const f4*>(blob + a.tiles_off + kq::kBlobRech);
-  const f4 rech1 = *reinterpret_cast<const f4*>(blob + a.tiles_off + kq::kBlobRech + 4);
+  const f4 rech0 = *reinterpret_cast<const f4*>(w.blob + a.tiles_off + kq::kBlobRech);
+  const f4 rech1 = *reinterpret_cast<const f4*>(w.blob + a.tiles_off + kq::kBlobRech + 4);
 
   // The stream's rings through ONE descriptor with the row pitch (32 bytes) as the stride: an access names its row by
   // index and its ring by the scalar offset; kNoRow drops it.
@@ -811,13 +812,19 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
 
 namespace
 {
+template <int ACT_T, bool BANK>
+hipError_t launch_kq_bank(const A1Args& a, int n_blocks, hipStream_t stream)
+{
+  return with_session_form(a.p_ring != nullptr, a.p_out_host != 0, a.n_frames, [&](auto wt, auto persist) {
+    return launch_instance<&nam_kq_kernel<ACT_T, decltype(wt)::value, decltype(persist)::value, BANK>>(dim3(n_blocks), dim3(kq::kNst * 64),
+                                                                                                       kq::kLdsBytes, stream, a.blob, a);
+  });
+}
 template <int ACT_T>
 hipError_t launch_kq_act(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  return with_session_form(a.p_ring != nullptr, a.p_out_host != 0, a.n_frames, [&](auto wt, auto persist) {
-    return launch_instance<&nam_kq_kernel<ACT_T, decltype(wt)::value, decltype(persist)::value>>(dim3(n_blocks), dim3(kq::kNst * 64), kq::kLdsBytes,
-                                                                                                 stream, a.blob, a);
-  });
+  // a model bank (A1Args::bank_member) runs the BANK instantiations; one model keeps its own
+  return a.bank_member ? launch_kq_bank<ACT_T, true>(a, n_blocks, stream) : launch_kq_bank<ACT_T, false>(a, n_blocks, stream);
 }
 } // namespace
 
@@ -837,7 +844,7 @@ hipError_t launch_kq(const A1Args& a, int n_blocks, int act, hipStream_t stream)
     return launch_kq_act<ACT_TANH>(a, n_blocks, stream);
   if (act == ACT_FASTTANH)
     return launch_kq_act<ACT_FASTTANH>(a, n_blocks, stream);
-  if (act == ACT_RELU)
+  if (act == ACT_RELU && !a.bank_member) // (a bank of ReLU members holds slope 0 per member already: api_bank.cpp)
   {
     A1Args r = a;
     // max(v, 0 v): -0 where ReLU gives +0 — equal in every sum and product behind it — for every FINITE v. Non-finite values

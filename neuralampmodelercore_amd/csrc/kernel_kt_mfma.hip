@@ -1,5 +1,5 @@
 // kernel_kt_mfma.hip — nam_kt_mfma_kernel: fp32 MFMA for single-array models with any per-layer kernel size (A2).
-#include "device_common.h"
+#include "il_common.h"
 
 namespace namhip
 {
@@ -16,7 +16,9 @@ namespace namhip
 // last chunk activates, runs the 1x1, publishes and meets the barrier: one barrier per layer. The head rechannel
 // (A2: 16 taps over the head accumulator) is one more layer whose published input is the head accumulator.
 // State layout, ring geometry and write positions are nam_a1_kernel's (the two are interchangeable mid-stream).
-template <int NK, bool WT, int ACT_T>
+// BANK (a model bank of this topology, api_bank.cpp): tiles, rechannel column, LDS source and the two scalars are the stream's
+// member's (il::weights_of); P is member 0's plan, which every member shares field for field.
+template <int NK, bool WT, int ACT_T, bool BANK = false>
 __global__ __launch_bounds__(256) void nam_kt_mfma_kernel(const A1Plan* __restrict__ P, const float* __restrict__ blob,
                                                           const A1Args a)
 {
@@ -45,7 +47,14 @@ __global__ __launch_bounds__(256) void nam_kt_mfma_kernel(const A1Plan* __restri
   float* out = a.out ? a.out + (size_t)stream * a.io_stride : nullptr;
   const int C = P->arr[0].channels;
   const int act = P->arr[0].act;
-  const float act_p0 = a.act_p0, head_scale = a.head_scale;
+  float act_p0 = a.act_p0, head_scale = a.head_scale;
+  if constexpr (BANK) // (in this form, not through il::Weights for both, the one-model instantiations keep their machine code)
+  {
+    const il::Weights wts = il::weights_of<true>(blob, a, stream);
+    blob = wts.blob;
+    act_p0 = wts.act_p0;
+    head_scale = wts.head_scale;
+  }
   const int NCH = P->kt_chunks;
   const int n_blocks = (a.n_frames + kBlock - 1) / kBlock;
   const int total = n_blocks * NCH;
@@ -265,8 +274,14 @@ hipError_t launch_kt_mfma(const A1Args& a, int n_blocks, int nk, int channels, i
   const int lds_bytes = (2 * (kBlock + 1) * (channels + 4) + lds_aux_floats) * (int)sizeof(float);
   if (lds_bytes > 64 * 1024)
     return hipErrorInvalidValue; // (plan_a1.cpp keeps the LDS copy small; 16-channel models with 32 layers stay below)
+  const bool bank = a.bank_member != nullptr; // a model bank runs the BANK instantiations (8 channels: the A2 topology)
+  if (bank && nk != 2)
+    return hipErrorInvalidValue;
 #define NAM_KT(NK, WT, ACT) \
-  hipLaunchKernelGGL((nam_kt_mfma_kernel<NK, WT, ACT>), dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a)
+  if (NK == 2 && bank) \
+    hipLaunchKernelGGL((nam_kt_mfma_kernel<2, WT, ACT, true>), dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a); \
+  else \
+    hipLaunchKernelGGL((nam_kt_mfma_kernel<NK, WT, ACT>), dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a)
 #define NAM_KT_ACT(NK, WT) \
   switch (act) \
   { \

@@ -49,7 +49,7 @@ int nam_hip_version_support(const char* nam_file_version)
 
 const char* nam_hip_version(void)
 {
-  return "nam_hip 0.2.2 gfx950"; // 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
+  return "nam_hip 0.2.3 gfx950"; // 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
 }
 
 int nam_hip_model_load(const char* nam_path, int fast_tanh, nam_hip_model** out_model)
@@ -850,8 +850,15 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
 {
   if (!batch || kernel < NAM_HIP_KERNEL_AUTO || kernel > NAM_HIP_KERNEL_WN_REG)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_kernel: bad argument");
-  if (batch->bank && kernel != NAM_HIP_KERNEL_AUTO && kernel != NAM_HIP_KERNEL_A1_IL)
-    return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)");
+  if (batch->bank)
+  {
+    // a bank batch runs its family's kernels only (api_bank.cpp)
+    const bool a2 = batch->bank->family == BANK_A2;
+    if (kernel != NAM_HIP_KERNEL_AUTO && kernel != (a2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL))
+      return fail(NAM_HIP_ERR_UNSUPPORTED,
+                  a2 ? "nam_hip_batch_set_kernel: an A2 bank batch runs nam_kq_kernel / nam_kt_mfma_kernel only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_MFMA)"
+                     : "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)");
+  }
   NAM_HIP_CHECK(hipSetDevice(batch->device)); // (ending a session may relaunch: the launchers configure the current device)
   if (batch->ps.active)
   {

@@ -2,14 +2,15 @@
 
 256-stream persistent sessions on one GPU in bench.py's two shapes — regions of 20 commands between device synchronizes, and
 regions of 500 commands — for
-  (a) a one-model batch (wavenet_a1_standard),
+  (a) a one-model batch (wavenet_a1_standard; --family a2: A2.nam),
   (b) a bank batch with every stream on member 0,
-  (c) a bank of 256 distinct members (standard-topology models with seeded weights, tests/bank_models.py), one per stream;
+  (c) a bank of 256 distinct members (standard-topology models with seeded weights, tests/bank_models.py; --family a2:
+      A2-topology models with seeded weights, head_scale and LeakyReLU slope, tests/bank_models_a2.py), one per stream;
 and the case a bank replaces: N captures as N one-stream batches called in turn with blocking 64-frame calls (N = 16 by
 default: enough to extrapolate per-capture cost, and it keeps memory and session count small).
 Every figure is the median of --runs repetitions (each a fresh timing of --regions regions); one JSON line per case.
 
-    python tools/bank_bench.py [--streams 256] [--runs 7] [--singles 16]
+    python tools/bank_bench.py [--family a1|a2] [--streams 256] [--runs 7] [--singles 16]
 """
 import argparse
 import json
@@ -64,11 +65,16 @@ def main():
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--singles", type=int, default=16)
+    ap.add_argument("--family", choices=["a1", "a2"], default="a1",
+                    help="a1: the official topology (nam_a1_q_kernel); a2: the A2 topology (nam_kq_kernel)")
     args = ap.parse_args()
     import neuralampmodelercore_amd as nam
-    from bank_models import write_standard
+    if args.family == "a2":
+        from bank_models_a2 import write_a2 as write_standard
+    else:
+        from bank_models import write_standard
     n = args.streams
-    std_path = os.path.join(ROOT, "tests", "golden", "models", "wavenet_a1_standard.nam")
+    std_path = os.path.join(ROOT, "tests", "golden", "models", ("A2" if args.family == "a2" else "wavenet_a1_standard") + ".nam")
     std = nam.get_dsp(std_path, fast_tanh=True)
     with tempfile.TemporaryDirectory() as d:
         members = []

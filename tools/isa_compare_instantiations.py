@@ -1,24 +1,33 @@
-"""Are the one-model instantiations of the interleaved-frame kernels the same code before and after the BANK template
-parameter? Compares two sets of `hipcc -S --cuda-device-only` listings (same flags as csrc/Makefile) of kernel_a1_q.hip,
-kernel_a1_p4.hip and kernel_a1_p2.hip, kernel by kernel: the body of every kernel of the OLD listing against the kernel of the
-NEW listing whose name is the old one plus a trailing `false` template argument (BANK). Basic-block label numbers and the
+"""Are the one-model instantiations of the kernels that run model banks the same code before and after the BANK template
+parameter? Compares two sets of `hipcc -S --cuda-device-only` listings (same flags as csrc/Makefile), kernel by kernel: the
+body of every kernel of the OLD listing against the kernel of the NEW listing of the same name, or — where the new tree added
+the parameter — whose name is the old one plus a trailing `false` template argument (BANK). Basic-block label numbers and the
 kernel's own name are normalised; what remains different is printed.
 
-    hipcc <flags> --cuda-device-only -S -o old/kernel_a1_q.s <old tree>/kernel_a1_q.hip     (and p4, p2; then the new tree)
-    python tools/isa_compare_instantiations.py old/ new/
+    hipcc <flags> --cuda-device-only -S -o old/kernel_kq.s <old tree>/kernel_kq.hip     (and the others; then the new tree)
+    python tools/isa_compare_instantiations.py old/ new/ [kernel_kq kernel_kt_mfma ...]
+
+Without a list: the interleaved-frame kernels (kernel_a1_q, kernel_a1_p4, kernel_a1_p2: the A1 bank family) and the A2 family's
+(kernel_kq, kernel_kt_mfma), as far as both directories hold their listings.
 """
 import os
 import re
 import sys
 
-SUFFIX = "EEvPKfNS_6A1ArgsE"  # ...<template args> E E v (const float*, namhip::A1Args)
+DEFAULT = ("kernel_a1_q", "kernel_a1_p4", "kernel_a1_p2", "kernel_kq", "kernel_kt_mfma")
+
+
+def twin_of(name):
+    """the mangled name with one more template argument `false`: ...<args> E E v <parameters> -> ...<args> Lb0E E E v ..."""
+    i = name.index("EEvPK")
+    return name[:i] + "Lb0E" + name[i:]
 
 
 def kernels(path):
     out, name, body = {}, None, []
     for line in open(path):
         m = re.match(r"^(_Z\w+):\s", line)
-        if m and "nam_a1_" in m.group(1):
+        if m and "_kernel" in m.group(1) and "nam_" in m.group(1):
             name, body = m.group(1), []
             continue
         if name:
@@ -32,14 +41,16 @@ def kernels(path):
     return out
 
 
-def main(old_dir, new_dir):
+def main(old_dir, new_dir, names=()):
     rc = 0
-    for k in ("kernel_a1_q", "kernel_a1_p4", "kernel_a1_p2"):
+    for k in names or DEFAULT:
+        if not names and not (os.path.exists(os.path.join(old_dir, k + ".s")) and os.path.exists(os.path.join(new_dir, k + ".s"))):
+            continue
         old, new = kernels(os.path.join(old_dir, k + ".s")), kernels(os.path.join(new_dir, k + ".s"))
         norm = lambda l, n: re.sub(r"\.LBB\d+_", ".LBB_", l.replace(n, "K"))
         same, kernarg_only, other = 0, 0, []
         for name, body in old.items():
-            twin = name[:-len(SUFFIX)] + "Lb0E" + SUFFIX
+            twin = name if name in new else twin_of(name)
             if twin not in new:
                 other.append((name, "no such kernel in the new listing"))
                 continue
@@ -62,4 +73,4 @@ def main(old_dir, new_dir):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], sys.argv[3:]))
