@@ -159,15 +159,6 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, in
   cmp("xt_off (ws_xt_off - ws_tiles_off)", a.ws_xt_off - a.ws_tiles_off, b.ws_xt_off - b.ws_tiles_off);
   cmp("n_xt (ws_n_xt)", a.ws_n_xt, b.ws_n_xt);
   cmp("q_w_off - ws_tiles_off", a.q_w_off - a.ws_tiles_off, b.q_w_off - b.ws_tiles_off);
-  cmp("il_jobs", a.il_jobs, b.il_jobs);
-  cmp("il_real_jobs", a.il_real_jobs, b.il_real_jobs);
-  cmp("il_depth", a.il_depth, b.il_depth);
-  cmp("il_exch", a.il_exch, b.il_exch);
-  cmp("il_consts_b", a.il_consts_b, b.il_consts_b);
-  cmp("il_xt_b", a.il_xt_b, b.il_xt_b);
-  cmp("il_tiles_b", a.il_tiles_b, b.il_tiles_b);
-  cmp("il_flag_b", a.il_flag_b, b.il_flag_b);
-  cmp("il_lds_bytes", a.il_lds_bytes, b.il_lds_bytes);
   return out;
 }
 } // namespace

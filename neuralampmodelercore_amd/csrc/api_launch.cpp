@@ -563,15 +563,6 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
     a.consts_off = p.a1.ws_consts_off - base;
     a.xt_off = p.a1.ws_xt_off - base;
     a.n_xt = p.a1.ws_n_xt;
-    a.il_jobs = p.a1.il_jobs;
-    a.il_real_jobs = p.a1.il_real_jobs;
-    a.il_depth = p.a1.il_depth;
-    a.il_exch = p.a1.il_exch;
-    a.il_consts_b = p.a1.il_consts_b;
-    a.il_xt_b = p.a1.il_xt_b;
-    a.il_tiles_b = p.a1.il_tiles_b;
-    a.il_flag_b = p.a1.il_flag_b;
-    a.il_lds_bytes = p.a1.il_lds_bytes;
     a.act = act;
     session_args(b, a);
     if (!p.a1.p2_ok) // (pick_kernel: the interleaved-frame kernels exist for the official topologies' compile-time tables only)

@@ -1,6 +1,8 @@
 // il_common.h — helpers shared by the interleaved-frame kernels (kernel_a1_p2.hip and the pipelines built on its lane layout and
 // session protocol: kernel_a1_p4.hip, kernel_a1_q.hip, kernel_kq.hip). The descriptor-driven form of the mapping,
-// nam_a1_il_kernel, was retired in round 5: topologies outside the compile-time tables run nam_a1_mfma_kernel.
+// nam_a1_il_kernel, and its run-time job tables are gone: the job table is plan.h's namespace p2, compile-time constants in the
+// A1 kernels here; the plan compiler admits a model only if its geometry is what those say (plan_a1.cpp: build_a1_il), and
+// topologies outside them run nam_a1_mfma_kernel.
 #pragma once
 #include "device_common.h"
 

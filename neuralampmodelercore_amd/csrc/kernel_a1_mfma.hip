@@ -429,18 +429,9 @@ namespace
 template <int ACT_T, bool WT, bool PROF, int D>
 hipError_t launch_mfma_inst(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  static int lds_limit = 0; // per instantiation: dynamic LDS the runtime has been told about
-  if (a.lds_bytes > lds_limit)
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nam_a1_mfma_kernel<ACT_T, WT, PROF, D>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, a.lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    lds_limit = a.lds_bytes;
-  }
-  hipLaunchKernelGGL((nam_a1_mfma_kernel<ACT_T, WT, PROF, D>), dim3(n_blocks), dim3(512), a.lds_bytes, stream, a.plan,
-                     a.blob, a);
-  return hipGetLastError();
+  // (the LDS layout is sized per model: plan.h, ws_lds_*)
+  return launch_instance<&nam_a1_mfma_kernel<ACT_T, WT, PROF, D>, true, kLdsCu>(
+      dim3(n_blocks), dim3(512), a.lds_bytes, stream, a.plan, a.blob, a);
 }
 template <int ACT_T, bool WT, bool PROF>
 hipError_t launch_mfma_depth(const A1Args& a, int n_blocks, hipStream_t stream)

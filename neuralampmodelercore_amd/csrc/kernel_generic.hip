@@ -462,20 +462,10 @@ __global__ __launch_bounds__(64) void nam_generic_kernel(const NamOp* __restrict
 
 hipError_t launch_generic(const GenericArgs& a, int n_blocks, int lds_bytes, hipStream_t stream)
 {
-  const bool wlds = a.blob_floats > 0;
-  if (lds_bytes > 64 * 1024)
-  {
-    hipError_t e = hipFuncSetAttribute(wlds ? reinterpret_cast<const void*>(nam_generic_kernel<true>)
-                                            : reinterpret_cast<const void*>(nam_generic_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess)
-      return e;
-  }
-  if (wlds)
-    hipLaunchKernelGGL(nam_generic_kernel<true>, dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
-  else
-    hipLaunchKernelGGL(nam_generic_kernel<false>, dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
-  return hipGetLastError();
+  // (rows, and the weights behind them, sized per program: plan_ops.cpp)
+  if (a.blob_floats > 0)
+    return launch_instance<&nam_generic_kernel<true>, true, kLdsCu>(dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
+  return launch_instance<&nam_generic_kernel<false>, true, kLdsCu>(dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
 }
 
 } // namespace namhip

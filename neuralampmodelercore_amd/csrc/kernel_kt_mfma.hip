@@ -272,41 +272,35 @@ hipError_t launch_kt_mfma(const A1Args& a, int n_blocks, int nk, int channels, i
 {
   const bool wt = a.n_frames <= 2 * kBlock; // short launches write ring appends through (see ring_store)
   const int lds_bytes = (2 * (kBlock + 1) * (channels + 4) + lds_aux_floats) * (int)sizeof(float);
-  if (lds_bytes > 64 * 1024)
-    return hipErrorInvalidValue; // (plan_a1.cpp keeps the LDS copy small; 16-channel models with 32 layers stay below)
+  // (at most kLdsDefault, or the launch is refused: plan_a1.cpp keeps the LDS copy small; 16-channel models with 32 layers stay below)
   const bool bank = a.bank_member != nullptr; // a model bank runs the BANK instantiations (8 channels: the A2 topology)
   if (bank && nk != 2)
     return hipErrorInvalidValue;
 #define NAM_KT(NK, WT, ACT) \
-  if (NK == 2 && bank) \
-    hipLaunchKernelGGL((nam_kt_mfma_kernel<2, WT, ACT, true>), dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a); \
-  else \
-    hipLaunchKernelGGL((nam_kt_mfma_kernel<NK, WT, ACT>), dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a)
+  (NK == 2 && bank) \
+    ? launch_instance<&nam_kt_mfma_kernel<2, WT, ACT, true>, true, kLdsDefault>( \
+        dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a) \
+    : launch_instance<&nam_kt_mfma_kernel<NK, WT, ACT>, true, kLdsDefault>( \
+        dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a)
 #define NAM_KT_ACT(NK, WT) \
   switch (act) \
   { \
-    case ACT_LEAKYRELU: NAM_KT(NK, WT, ACT_LEAKYRELU); break; \
-    case ACT_FASTTANH: NAM_KT(NK, WT, ACT_FASTTANH); break; \
-    case ACT_TANH: NAM_KT(NK, WT, ACT_TANH); break; \
-    default: NAM_KT(NK, WT, -1); break; \
+    case ACT_LEAKYRELU: return NAM_KT(NK, WT, ACT_LEAKYRELU); \
+    case ACT_FASTTANH: return NAM_KT(NK, WT, ACT_FASTTANH); \
+    case ACT_TANH: return NAM_KT(NK, WT, ACT_TANH); \
+    default: return NAM_KT(NK, WT, -1); \
   }
   if (nk == 2)
   {
     if (wt)
       NAM_KT_ACT(2, true)
-    else
-      NAM_KT_ACT(2, false)
+    NAM_KT_ACT(2, false)
   }
-  else
-  {
-    if (wt)
-      NAM_KT_ACT(4, true)
-    else
-      NAM_KT_ACT(4, false)
-  }
+  if (wt)
+    NAM_KT_ACT(4, true)
+  NAM_KT_ACT(4, false)
 #undef NAM_KT_ACT
 #undef NAM_KT
-  return hipGetLastError();
 }
 
 } // namespace namhip

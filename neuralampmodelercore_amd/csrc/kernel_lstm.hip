@@ -1021,41 +1021,13 @@ hipError_t launch_lstm(const LSTMArgs& a, hipStream_t stream)
     if (!a.scratch)
       return hipErrorInvalidValue;
     const int io_bytes = (a.in_ch + a.out_ch) * kBlock * 65 * (int)sizeof(float);
-    if (io_bytes > 160 * 1024)
-      return hipErrorInvalidValue;
-    static DynamicLdsLimit lim;
-    if (io_bytes > 64 * 1024)
-    {
-      const hipError_t e = lim.ensure(reinterpret_cast<const void*>(nam_lstm_kernel<true>), 160 * 1024);
-      if (e != hipSuccess)
-        return e;
-    }
-    hipLaunchKernelGGL(nam_lstm_kernel<true>, dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a);
-    return hipGetLastError();
+    return launch_instance<&nam_lstm_kernel<true>, true, kLdsCu>(dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a);
   }
-  const int lds_bytes = lstm_lds_bytes(a);
-  if (lds_bytes > 64 * 1024)
-  {
-    static DynamicLdsLimit lim;
-    const hipError_t e = lim.ensure(reinterpret_cast<const void*>(nam_lstm_kernel<false>), 160 * 1024);
-    if (e != hipSuccess)
-      return e;
-  }
-  hipLaunchKernelGGL(nam_lstm_kernel<false>, dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a);
-  return hipGetLastError();
+  return launch_instance<&nam_lstm_kernel<false>, true, kLdsCu>(dim3(n_blocks), dim3(64), lstm_lds_bytes(a), stream, a.blob, a);
 }
 
 hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
 {
-  static int lds_limit = 0;
-  if (a.mf_lds_bytes > lds_limit)
-  {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nam_lstm_mfma_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, a.mf_lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    lds_limit = a.mf_lds_bytes;
-  }
   const int n_blocks = (a.n_streams + 15) / 16;
   // small models: everything in registers (only the I/O tiles in LDS)
   if (lstm_mfma_in_registers(a))
@@ -1063,31 +1035,29 @@ hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
     // I/O tiles + a pad row that lanes without an output row store to (64 lanes + 64 steps)
     const int io_bytes = ((a.in_ch + a.out_ch) * 16 * 65 + 128) * (int)sizeof(float);
 #define NAM_LSTM_REG(NL, NT) \
-  if (a.fast) \
-    hipLaunchKernelGGL((nam_lstm_mfma_reg_kernel<NL, NT, true>), dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a); \
-  else \
-    hipLaunchKernelGGL((nam_lstm_mfma_reg_kernel<NL, NT, false>), dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a)
+  return a.fast ? launch_instance<&nam_lstm_mfma_reg_kernel<NL, NT, true>, true, kLdsDefault>( \
+                    dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a) \
+                : launch_instance<&nam_lstm_mfma_reg_kernel<NL, NT, false>, true, kLdsDefault>( \
+                    dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a)
     const int key = a.n_layers * 10 + a.mf_nt;
     switch (key)
     {
-      case 11: NAM_LSTM_REG(1, 1); break;
-      case 12: NAM_LSTM_REG(1, 2); break;
-      case 13: NAM_LSTM_REG(1, 3); break;
-      case 14: NAM_LSTM_REG(1, 4); break;
-      case 21: NAM_LSTM_REG(2, 1); break;
-      case 22: NAM_LSTM_REG(2, 2); break;
-      case 23: NAM_LSTM_REG(2, 3); break;
-      case 24: NAM_LSTM_REG(2, 4); break;
-      case 15: NAM_LSTM_REG(1, 5); break;
-      case 16: NAM_LSTM_REG(1, 6); break;
-      case 25: NAM_LSTM_REG(2, 5); break;
-      default: NAM_LSTM_REG(2, 6); break;
+      case 11: NAM_LSTM_REG(1, 1);
+      case 12: NAM_LSTM_REG(1, 2);
+      case 13: NAM_LSTM_REG(1, 3);
+      case 14: NAM_LSTM_REG(1, 4);
+      case 21: NAM_LSTM_REG(2, 1);
+      case 22: NAM_LSTM_REG(2, 2);
+      case 23: NAM_LSTM_REG(2, 3);
+      case 24: NAM_LSTM_REG(2, 4);
+      case 15: NAM_LSTM_REG(1, 5);
+      case 16: NAM_LSTM_REG(1, 6);
+      case 25: NAM_LSTM_REG(2, 5);
+      default: NAM_LSTM_REG(2, 6);
     }
 #undef NAM_LSTM_REG
-    return hipGetLastError();
   }
-  hipLaunchKernelGGL(nam_lstm_mfma_kernel, dim3(n_blocks), dim3(64), a.mf_lds_bytes, stream, a.blob, a);
-  return hipGetLastError();
+  return launch_instance<&nam_lstm_mfma_kernel, true, kLdsCu>(dim3(n_blocks), dim3(64), a.mf_lds_bytes, stream, a.blob, a);
 }
 
 hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
@@ -1097,28 +1067,27 @@ hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
   const int n_blocks = (a.n_streams + 3) / 4;
   const int lds_bytes = (4 * a.hidden * 65 + 128) * (int)sizeof(float); // h history of the block + the dump slots
 #define NAM_LSTM_ROW_H(NL, NI, NH) \
-  if (a.fast) \
-    nam_launch((nam_lstm_row_kernel<NL, NI, NH, true>), dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a); \
-  else \
-    nam_launch((nam_lstm_row_kernel<NL, NI, NH, false>), dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a)
+  return a.fast ? launch_instance<&nam_lstm_row_kernel<NL, NI, NH, true>, false, kLdsDefault>( \
+                    dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a) \
+                : launch_instance<&nam_lstm_row_kernel<NL, NI, NH, false>, false, kLdsDefault>( \
+                    dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a)
 #define NAM_LSTM_ROW(NL, NI) \
   switch (a.hidden) \
   { \
-    case 1: NAM_LSTM_ROW_H(NL, NI, 1); break; \
-    case 2: NAM_LSTM_ROW_H(NL, NI, 2); break; \
-    case 3: NAM_LSTM_ROW_H(NL, NI, 3); break; \
-    default: NAM_LSTM_ROW_H(NL, NI, 4); break; \
+    case 1: NAM_LSTM_ROW_H(NL, NI, 1); \
+    case 2: NAM_LSTM_ROW_H(NL, NI, 2); \
+    case 3: NAM_LSTM_ROW_H(NL, NI, 3); \
+    default: NAM_LSTM_ROW_H(NL, NI, 4); \
   }
   switch (a.n_layers * 10 + a.input_size)
   {
-    case 11: NAM_LSTM_ROW(1, 1); break;
-    case 12: NAM_LSTM_ROW(1, 2); break;
-    case 21: NAM_LSTM_ROW(2, 1); break;
-    default: NAM_LSTM_ROW(2, 2); break;
+    case 11: NAM_LSTM_ROW(1, 1);
+    case 12: NAM_LSTM_ROW(1, 2);
+    case 21: NAM_LSTM_ROW(2, 1);
+    default: NAM_LSTM_ROW(2, 2);
   }
 #undef NAM_LSTM_ROW
 #undef NAM_LSTM_ROW_H
-  return hipGetLastError();
 }
 
 hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)
@@ -1128,31 +1097,30 @@ hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)
   const int nh = (a.hidden + 3) & ~3;
   const int lds_bytes = (kBlock * (nh + 4) + a.out_ch * nh + a.out_ch) * (int)sizeof(float);
 #define NAM_LSTM_WIDE_H(NL, NI, NH) \
-  if (a.fast) \
-    nam_launch((nam_lstm_wide_kernel<NL, NI, NH, true>), dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a); \
-  else \
-    nam_launch((nam_lstm_wide_kernel<NL, NI, NH, false>), dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a)
+  return a.fast ? launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, true>, false, kLdsDefault>( \
+                    dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a) \
+                : launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, false>, false, kLdsDefault>( \
+                    dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a)
 #define NAM_LSTM_WIDE(NL, NI) \
   switch (nh) \
   { \
-    case 8: NAM_LSTM_WIDE_H(NL, NI, 8); break; \
-    case 12: NAM_LSTM_WIDE_H(NL, NI, 12); break; \
-    case 16: NAM_LSTM_WIDE_H(NL, NI, 16); break; \
-    case 20: NAM_LSTM_WIDE_H(NL, NI, 20); break; \
-    case 24: NAM_LSTM_WIDE_H(NL, NI, 24); break; \
-    case 28: NAM_LSTM_WIDE_H(NL, NI, 28); break; \
-    default: NAM_LSTM_WIDE_H(NL, NI, 32); break; \
+    case 8: NAM_LSTM_WIDE_H(NL, NI, 8); \
+    case 12: NAM_LSTM_WIDE_H(NL, NI, 12); \
+    case 16: NAM_LSTM_WIDE_H(NL, NI, 16); \
+    case 20: NAM_LSTM_WIDE_H(NL, NI, 20); \
+    case 24: NAM_LSTM_WIDE_H(NL, NI, 24); \
+    case 28: NAM_LSTM_WIDE_H(NL, NI, 28); \
+    default: NAM_LSTM_WIDE_H(NL, NI, 32); \
   }
   switch (a.n_layers * 10 + a.input_size)
   {
-    case 11: NAM_LSTM_WIDE(1, 1); break;
-    case 12: NAM_LSTM_WIDE(1, 2); break;
-    case 21: NAM_LSTM_WIDE(2, 1); break;
-    default: NAM_LSTM_WIDE(2, 2); break;
+    case 11: NAM_LSTM_WIDE(1, 1);
+    case 12: NAM_LSTM_WIDE(1, 2);
+    case 21: NAM_LSTM_WIDE(2, 1);
+    default: NAM_LSTM_WIDE(2, 2);
   }
 #undef NAM_LSTM_WIDE
 #undef NAM_LSTM_WIDE_H
-  return hipGetLastError();
 }
 
 hipError_t launch_fill_state(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,

@@ -1704,42 +1704,19 @@ hipError_t launch_wn_reg(const WrArgs& a, int n_workgroups, int lds_bytes, bool 
 {
   if (n_workgroups <= 0 || a.n_frames <= 0)
     return hipSuccess;
-  if (stages > 1)
-  {
-    static DynamicLdsLimit lds_limit2[6];
-    auto launch2 = [&](auto kernel, int set) -> hipError_t {
-      if (lds_bytes > 64 * 1024)
-      {
-        const hipError_t e = lds_limit2[set].ensure(reinterpret_cast<const void*>(kernel), kWrMaxLdsBytes);
-        if (e != hipSuccess)
-          return e;
-      }
-      nam_launch(kernel, dim3(n_workgroups), dim3(64 * stages), (unsigned)lds_bytes, stream, a);
-      return hipGetLastError();
-    };
-    const int set = ((layers && runs) || rt_layers) ? 2 : runs ? 1 : 0;
-    if (stages == 4)
-      return set == 2 ? launch2(nam_wn_reg4_kernel<2>, 5) : set == 1 ? launch2(nam_wn_reg4_kernel<1>, 4) : launch2(nam_wn_reg4_kernel<0>, 3);
-    return set == 2 ? launch2(nam_wn_reg2_kernel<2>, 2) : set == 1 ? launch2(nam_wn_reg2_kernel<1>, 1) : launch2(nam_wn_reg2_kernel<0>, 0);
-  }
   // more than the default 64 KB of dynamic LDS per workgroup (long dilations at 4+ channels: the official nano size
-  // keeps 68 KB of rings): raised once per instantiation
-  static DynamicLdsLimit lds_limit[3]; // per instantiation, tracked per device (kernels.h)
-  auto launch = [&](auto kernel, int set) -> hipError_t {
-    if (lds_bytes > 64 * 1024)
-    {
-      const hipError_t e = lds_limit[set].ensure(reinterpret_cast<const void*>(kernel), kWrMaxLdsBytes);
-      if (e != hipSuccess)
-        return e;
-    }
-    nam_launch(kernel, dim3(n_workgroups), dim3(64), (unsigned)lds_bytes, stream, a);
-    return hipGetLastError();
-  };
-  if ((layers && runs) || rt_layers)
-    return launch(nam_wn_reg_kernel<2>, 2);
-  if (runs)
-    return launch(nam_wn_reg_kernel<1>, 1);
-  return launch(nam_wn_reg_kernel<0>, 0);
+  // keeps 68 KB of rings): up to kWrMaxLdsBytes
+  const int set = ((layers && runs) || rt_layers) ? 2 : runs ? 1 : 0;
+#define NAM_WR_LAUNCH(KERNEL) \
+  return set == 2 ? launch_instance<&KERNEL<2>, false, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a) \
+       : set == 1 ? launch_instance<&KERNEL<1>, false, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a) \
+                  : launch_instance<&KERNEL<0>, false, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a)
+  if (stages == 4)
+    NAM_WR_LAUNCH(nam_wn_reg4_kernel);
+  if (stages > 1)
+    NAM_WR_LAUNCH(nam_wn_reg2_kernel);
+  NAM_WR_LAUNCH(nam_wn_reg_kernel);
+#undef NAM_WR_LAUNCH
 }
 #endif
 

@@ -49,19 +49,27 @@ inline void nam_launch(F kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipS
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
 }
 
-// One kernel instantiation on the current device, its dynamic-LDS limit raised: the limit object lives here, one per `Kernel`
-// (= per instantiation, as DynamicLdsLimit asks). Also what a first launch would otherwise pay for (~1.6 ms: the code object).
+// One kernel instantiation on the current device, its dynamic-LDS limit raised to `lds_ceiling`: the limit object lives here, one
+// per `Kernel` (= per instantiation, as DynamicLdsLimit asks). Also what a first launch would otherwise pay for (~1.6 ms: the
+// code object).
+constexpr int kLdsDefault = 64 * 1024; // what a launch may ask for without the attribute
+constexpr int kLdsCu = 160 * 1024; // a CU's LDS
 template <auto Kernel>
-inline hipError_t instance_ready(int lds_bytes)
+inline hipError_t instance_ready(int lds_ceiling)
 {
   static DynamicLdsLimit lds_limit;
-  return lds_limit.ensure(reinterpret_cast<const void*>(Kernel), lds_bytes);
+  return lds_limit.ensure(reinterpret_cast<const void*>(Kernel), lds_ceiling);
 }
-// ... and launched: through nam_launch (every session-capable kernel), or kPlain = a plain launch
-template <auto Kernel, bool kPlain = false, typename... Args>
+// ... and launched: through nam_launch (every session-capable kernel), or kPlain = a plain launch. DynamicLdsLimit records
+// "raised", not a size: a kernel whose LDS request differs from launch to launch names the most it may ask for as kLdsCeiling
+// (0: every launch of the instantiation asks for the same lds_bytes). kLdsDefault as the ceiling is a refusal bound only: those
+// kernels never need the attribute raised, and one call per device that sets what is the default anyway costs nothing.
+template <auto Kernel, bool kPlain = false, int kLdsCeiling = 0, typename... Args>
 inline hipError_t launch_instance(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, Args... args)
 {
-  const hipError_t e = instance_ready<Kernel>(lds_bytes);
+  if (kLdsCeiling && lds_bytes > kLdsCeiling)
+    return hipErrorInvalidValue;
+  const hipError_t e = instance_ready<Kernel>(kLdsCeiling ? kLdsCeiling : lds_bytes);
   if (e != hipSuccess)
     return e;
   if constexpr (kPlain)
@@ -128,9 +136,6 @@ struct A1Args
   int xt_off = 0, n_xt = 0; // blob offset / count of the extra tiles
   int lds_tiles_b = 0, lds_xt_b = 0, lds_cond_b = 0, lds_bytes = 0; // dynamic LDS layout (bytes)
   int prefetch = 0; // the plan's ws_prefetch (mover prefetch depth the descriptors were built for)
-  // interleaved-frame kernel (plan.h: A1Plan::il_*)
-  int il_jobs = 0, il_real_jobs = 0, il_depth = 0, il_exch = 0;
-  int il_consts_b = 0, il_xt_b = 0, il_tiles_b = 0, il_flag_b = 0, il_lds_bytes = 0;
   int act = 0; // the arrays' activation type when it is uniform (nam_a1_p2_kernel's run-time-dispatch instantiation)
   // persistent session of nam_a1_p2_kernel (nullptr = ordinary launch): command ring in device memory, ring size - 1,
   // commands consumed before this launch, per-workgroup progress / completion words in host-mapped memory
@@ -163,7 +168,7 @@ struct A1Args
   const float* bank_scal;
   long bank_stride;
 };
-static_assert(sizeof(A1Args) == 288, "A1Args is a kernel argument (296 bytes of kernarg with the blob pointer in front): its layout is part of the compiled kernels");
+static_assert(sizeof(A1Args) == 248, "A1Args is a kernel argument (256 bytes of kernarg with the blob pointer in front): its layout is part of the compiled kernels");
 
 // Which instantiation of a session-capable pipeline kernel (nam_a1_p4_kernel, nam_a1_q_kernel, nam_kq_kernel) a launch takes
 // besides its model's: f(WT, PERSIST) with the two as std::bool_constant.

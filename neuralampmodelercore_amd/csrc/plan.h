@@ -185,12 +185,14 @@ static_assert(sizeof(CDesc) == 32 && sizeof(VDesc) == 64, "descriptor sizes are 
 // into LDS once per launch, job by job, and publishes its progress in an LDS word the compute waves check.
 enum IlKind : int32_t
 {
-  IL_IDLE = 0, // padding job (jobs per block are padded to a multiple of the request depth)
+  IL_IDLE = 0, // no job
   IL_HIST = 1,
   IL_DPP = 2,
   IL_EXCH = 3
 };
-struct IlDesc // 16 x int32, one s_load_dwordx16
+// One job / the requests issued during one job, as records: what p2::desc / p2::fetch return. The kernels instantiate them as
+// compile-time constants (nothing loads one), the plan compiler compares them with the model's geometry (plan_a1.cpp: a1_is_p2).
+struct IlDesc
 {
   int32_t flags; // CDescFlags
   int32_t kind; // IlKind
@@ -203,23 +205,22 @@ struct IlDesc // 16 x int32, one s_load_dwordx16
   int32_t n_ready; // loader progress required before the next job's operands may be read (its job index + 1)
   int32_t pad[2];
 };
-struct IlFetch // 8 x int32: the two ring requests issued now for the job `depth` ahead
+struct IlFetch // the two ring requests issued now for the job `depth` ahead
 {
   int32_t ring_b, R, ring_id, row_b;
   int32_t LA, LB; // lookbacks in frames (0 = no request)
   int32_t nA, nB; // lanes j < n request (16 = every lane)
 };
-static_assert(sizeof(IlDesc) == 64 && sizeof(IlFetch) == 32, "descriptor sizes are part of the kernel ABI");
-constexpr int kIlJobMax = kWsJobMax + 8;
 constexpr int kIlWinRowB = kMfSC * 4; // LDS window row pitch (bytes)
 constexpr int kIlWinB = 2 * kBlock * kIlWinRowB; // one window: [previous 64 | current 64] frames
 
 // ---- The official A1 topology at compile time (nam_a1_p2_kernel) ----------------------------------------------
 // Every official WaveNet size (standard 16/8, lite 12/6, feather 8/4 channels) is two arrays of ten layers, kernel
 // size 3, dilations 1, 2, 4, ... 512. For that topology the whole job table of the interleaved-frame kernel is a
-// function of the two (padded) channel counts: these constexpr functions restate plan_a1.cpp's build_a1_il for it, the
-// kernel instantiates them as compile-time constants (no descriptor loads, no kind / layout / flag branches, immediate
-// LDS offsets), and plan.cpp sets A1Plan::p2_ok only if they reproduce the model's il_desc / il_fetch tables exactly.
+// function of the two (padded) channel counts: these constexpr functions are that table, the kernels instantiate them as
+// compile-time constants (no descriptor loads, no kind / layout / flag branches, immediate LDS offsets), and plan_a1.cpp
+// sets A1Plan::p2_ok only if the model's own geometry — rings, dilations, per-job flags, extra tiles — is what they say
+// (a1_is_p2). A model outside them has no interleaved-frame kernel: it runs nam_a1_mfma_kernel.
 namespace p2
 {
 constexpr int kLayers = 10, kJobs = 20, kDepth = 10, kXt = 3;
@@ -344,13 +345,7 @@ struct A1Plan
   CDesc cdesc[kWsJobMax];
   VDesc vdesc[kWsJobMax];
   // interleaved-frame MFMA kernel (shares ws_tiles_off / ws_consts_off / ws_xt_off with the kernel above)
-  int32_t il_ok = 0;
-  int32_t il_jobs = 0, il_real_jobs = 0; // jobs per block incl. padding / real layers
-  int32_t il_depth = 5; // request depth = unroll factor (10 when it divides the layer count, else 5)
-  int32_t il_exch = 0; // IL_EXCH jobs (= workgroup barriers) per block
-  int32_t il_consts_b = 0, il_xt_b = 0, il_tiles_b = 0, il_flag_b = 0, il_lds_bytes = 0; // LDS layout (bytes); windows at 0
-  IlDesc il_desc[kIlJobMax];
-  IlFetch il_fetch[kIlJobMax];
+  int32_t il_ok = 0; // every dilation fits the interleaved-frame mapping and its LDS layout fits a CU (plan_a1.cpp: a1_il_fits)
   int32_t p2_ok = 0; // nam_a1_p2_kernel<p2_c0, p2_c1> runs this model (the official topology, see namespace p2)
   int32_t p2_c0 = 0, p2_c1 = 0; // the two arrays' (padded) channel counts
   // K-tap MFMA kernel

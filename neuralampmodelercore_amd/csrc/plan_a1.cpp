@@ -273,149 +273,85 @@ void build_a1_ws(const WaveNetSpec& wn, Plan& plan)
   a1.ws_ok = 1;
 }
 
-// Job table of the interleaved-frame mapping (plan.h: IlDesc / IlFetch; nam_a1_p2_kernel's compile-time tables are checked against it). Built from the finished A1 plan: same eligibility, tiles,
-// constants and per-job flags as nam_a1_mfma_kernel; ring offsets are final (write-position table included).
+namespace
+{
+// How the interleaved-frame mapping (plan.h: IlKind) reaches a layer's two dilated taps; IL_IDLE: it cannot
+int il_kind(int d)
+{
+  // every tap in an earlier block. Across a block boundary of one launch a lane may only re-read rows it stored itself
+  // (same-wave program order is the only ordering there is without a barrier): lookbacks must be whole blocks
+  if (d >= kBlock)
+    return d % kBlock == 0 ? IL_HIST : IL_IDLE;
+  if (d == 4 || d == 8 || d == 16 || d == 32)
+    return IL_DPP;
+  // tap 0 from the LDS window (2d <= 64), or from the ring at a lookback of whole blocks (see above)
+  return 2 * d <= kBlock || (2 * d) % kBlock == 0 ? IL_EXCH : IL_IDLE;
+}
+// A1Plan::il_ok: the mapping takes every layer, and its LDS layout fits a CU
+bool a1_il_fits(const A1Plan& a1, int n_layers)
+{
+  if (n_layers > kWsJobMax)
+    return false;
+  for (int ai = 0; ai < a1.n_arrays; ai++)
+    for (int l = 0; l < a1.arr[ai].n_layers; l++)
+      if (il_kind(a1.arr[ai].dil[l]) == IL_IDLE)
+        return false;
+  // exchange windows [2] | constants [jobs][64] | extra tiles [n][256] | tiles [jobs][1024] | loader progress word (p2::kLdsBytes)
+  return 2 * kIlWinB + n_layers * 256 + a1.ws_n_xt * 1024 + n_layers * kWsTileFloats * 4 + 64 <= 160 * 1024;
+}
+// A1Plan::p2_ok: the compile-time tables of the official topology (plan.h: namespace p2) ARE this model's. Field by field:
+//   IlDesc   flags, act, gp                 the job's CDesc (build_a1_ws)
+//            kind, dil, tap0_lds            the layer's dilation
+//            ring_b, R, ring_id, row_b      the layer's ring and its array's channels
+//            n_xt_b                         the NEXT job's extra-tile slot (j + 1 runs over all twenty jobs, so job j's is checked here)
+//            n_consts_b, n_tiles_b, n_ready functions of the job index and of p2::kJobs / kXt alone (twenty layers, ws_n_xt == kXt)
+//   IlFetch  ring_b, R, ring_id, row_b      the ring of the job p2::kDepth ahead: job j's is checked against fetch(j - kDepth)
+//            LA, LB, nA, nB                 functions of that job's kind and dilation alone, which its IlDesc pins
+bool a1_is_p2(const A1Plan& a1, int n_layers)
+{
+  if (a1.n_arrays != 2 || n_layers != p2::kJobs || a1.ws_n_xt != p2::kXt || a1.arr[0].act != a1.arr[1].act)
+    return false;
+  const int C0 = a1.arr[0].channels, C1 = a1.arr[1].channels;
+  if (!((C0 == 16 && C1 == 8) || (C0 == 12 && C1 == 8) || (C0 == 8 && C1 == 4))) // instantiated in kernel_a1_p2.hip
+    return false;
+  int j = 0;
+  for (int ai = 0; ai < 2; ai++)
+    for (int l = 0; l < a1.arr[ai].n_layers; l++, j++)
+    {
+      const A1Array& A = a1.arr[ai];
+      const CDesc& c = a1.cdesc[j];
+      const IlDesc e = p2::desc(C0, C1, a1.arr[0].act, j);
+      const IlFetch f = p2::fetch(C0, C1, (j + p2::kJobs - p2::kDepth) % p2::kJobs);
+      const int d = A.dil[l], kind = il_kind(d);
+      const bool same = c.flags == e.flags && c.act == e.act && (c.gp & 0xff) == e.gp && kind == e.kind && d == e.dil
+                        && (kind == IL_EXCH && 2 * d <= kBlock ? 1 : 0) == e.tap0_lds && A.ring_off[l] * 4 == e.ring_b
+                        && A.ring_len[l] == e.R && A.ring_id[l] == e.ring_id && A.channels * 4 == e.row_b
+                        && c.xt_b - a1.ws_lds_xt_b == p2::xt_index(j) * 1024 && A.ring_off[l] * 4 == f.ring_b
+                        && A.ring_len[l] == f.R && A.ring_id[l] == f.ring_id && A.channels * 4 == f.row_b;
+      if (!same)
+        return false;
+    }
+  return true;
+}
+} // namespace
+
+// Which models the interleaved-frame kernels take (nam_a1_p2_kernel and the pipelines on its lane layout), from the finished A1
+// plan: same eligibility, tiles, constants and per-job flags as nam_a1_mfma_kernel; ring offsets are final.
 void build_a1_il(Plan& plan)
 {
   A1Plan& a1 = plan.a1;
-  a1.il_ok = 0;
+  a1.il_ok = a1.p2_ok = 0;
   if (!a1.valid || !a1.ws_ok)
     return;
   int n_layers = 0;
   for (int ai = 0; ai < a1.n_arrays; ai++)
     n_layers += a1.arr[ai].n_layers;
-  // the kernel's job loop is unrolled 10 deep: jobs per block are padded to a multiple of 10 with idle jobs
-  const int D = 10;
-  const int NJ = (n_layers + 9) / 10 * 10;
-  if (NJ > kIlJobMax || n_layers > kWsJobMax)
-    return;
-  struct Geo
+  a1.il_ok = a1_il_fits(a1, n_layers);
+  a1.p2_ok = a1.il_ok && a1_is_p2(a1, n_layers);
+  if (a1.p2_ok)
   {
-    int C = 4, d = 1, R = 64, ring_b = 0, ring_id = 0, kind = IL_IDLE;
-  };
-  std::vector<Geo> geo((size_t)NJ);
-  int j = 0, n_exch = 0;
-  for (int ai = 0; ai < a1.n_arrays; ai++)
-    for (int l = 0; l < a1.arr[ai].n_layers; l++, j++)
-    {
-      Geo& G = geo[(size_t)j];
-      const A1Array& A = a1.arr[ai];
-      G.C = A.channels;
-      G.d = A.dil[l];
-      G.R = A.ring_len[l];
-      G.ring_b = A.ring_off[l] * 4;
-      G.ring_id = A.ring_id[l];
-      if (G.d >= kBlock)
-      {
-        // every tap lies in an earlier block. Across a block boundary of one launch a lane may only re-read rows it
-        // stored itself (same-wave program order is the only ordering there is without a barrier): lookbacks must be
-        // whole blocks
-        if (G.d % kBlock != 0)
-          return;
-        G.kind = IL_HIST;
-      }
-      else if (G.d == 4 || G.d == 8 || G.d == 16 || G.d == 32)
-        G.kind = IL_DPP;
-      else
-      {
-        if (2 * G.d > kBlock && (2 * G.d) % kBlock != 0)
-          return; // tap 0 would come from the ring at a lookback that is not a whole number of blocks (see above)
-        G.kind = IL_EXCH;
-        n_exch++;
-      }
-    }
-  a1.il_jobs = NJ;
-  a1.il_real_jobs = n_layers;
-  a1.il_depth = D;
-  a1.il_exch = n_exch;
-  // LDS: exchange windows [2] | constants [jobs][64] | extra tiles [n][256] | tiles [jobs][1024] | loader progress word
-  a1.il_consts_b = 2 * kIlWinB;
-  a1.il_xt_b = a1.il_consts_b + n_layers * 256;
-  a1.il_tiles_b = a1.il_xt_b + a1.ws_n_xt * 1024;
-  a1.il_flag_b = a1.il_tiles_b + n_layers * kWsTileFloats * 4;
-  a1.il_lds_bytes = a1.il_flag_b + 64;
-  if (a1.il_lds_bytes > 160 * 1024)
-    return;
-  std::memset(a1.il_desc, 0, sizeof(a1.il_desc));
-  std::memset(a1.il_fetch, 0, sizeof(a1.il_fetch));
-  auto xt_of = [&](int job) { return a1.il_xt_b + (a1.cdesc[job].xt_b - a1.ws_lds_xt_b); };
-  for (j = 0; j < NJ; j++)
-  {
-    const Geo& G = geo[(size_t)j];
-    IlDesc& Dd = a1.il_desc[j];
-    Dd.kind = G.kind;
-    if (G.kind != IL_IDLE)
-    {
-      Dd.flags = a1.cdesc[j].flags;
-      Dd.act = a1.cdesc[j].act;
-      Dd.gp = a1.cdesc[j].gp & 0xff;
-      Dd.ring_b = G.ring_b;
-      Dd.R = G.R;
-      Dd.ring_id = G.ring_id;
-      Dd.row_b = G.C * 4;
-      Dd.dil = G.d;
-      Dd.tap0_lds = (G.kind == IL_EXCH && 2 * G.d <= kBlock) ? 1 : 0;
-    }
-    else
-    {
-      Dd.R = kBlock;
-      Dd.row_b = 16;
-    }
-    // operands of the next real job (padding jobs pass job 0's along: they sit at the end of the block)
-    const int nj = (j + 1) % NJ;
-    const int nreal = geo[(size_t)nj].kind != IL_IDLE ? nj : 0;
-    Dd.n_consts_b = a1.il_consts_b + nreal * 256;
-    Dd.n_xt_b = xt_of(nreal);
-    Dd.n_tiles_b = a1.il_tiles_b + nreal * kWsTileFloats * 4;
-    Dd.n_ready = nreal + 1;
-    // requests for the job D ahead
-    const Geo& F = geo[(size_t)((j + D) % NJ)];
-    IlFetch& Ff = a1.il_fetch[j];
-    Ff.ring_b = F.ring_b;
-    Ff.R = F.kind != IL_IDLE ? F.R : kBlock;
-    Ff.ring_id = F.kind != IL_IDLE ? F.ring_id : 0;
-    Ff.row_b = F.kind != IL_IDLE ? F.C * 4 : 16;
-    Ff.nA = Ff.nB = 16;
-    switch (F.kind)
-    {
-      case IL_HIST:
-        Ff.LA = 2 * F.d;
-        Ff.LB = F.d;
-        break;
-      case IL_DPP:
-        Ff.LA = 2 * F.d;
-        Ff.LB = F.d;
-        Ff.nA = std::min(16, F.d / 2);
-        Ff.nB = F.d / 4;
-        break;
-      case IL_EXCH:
-        Ff.LA = kBlock; // the lane's own frame of the previous block, for the "previous" half of the LDS window
-        Ff.LB = 2 * F.d > kBlock ? 2 * F.d : 0; // tap 0 from the ring
-        break;
-      default: Ff.LA = Ff.LB = 0; break;
-    }
-  }
-  a1.il_ok = 1;
-  // the official topology with compile-time tables (plan.h: namespace p2): only if those tables ARE this model's
-  a1.p2_ok = 0;
-  if (a1.n_arrays == 2 && n_layers == p2::kJobs && NJ == p2::kJobs && D == p2::kDepth && a1.ws_n_xt == p2::kXt
-      && a1.il_consts_b == p2::kConstsB && a1.il_xt_b == p2::kXtB && a1.il_tiles_b == p2::kTilesB
-      && a1.il_flag_b == p2::kFlagB && a1.arr[0].act == a1.arr[1].act)
-  {
-    const int C0 = a1.arr[0].channels, C1 = a1.arr[1].channels;
-    bool same = (C0 == 16 && C1 == 8) || (C0 == 12 && C1 == 8) || (C0 == 8 && C1 == 4); // instantiated in kernel_a1_p2.hip
-    for (j = 0; same && j < NJ; j++)
-    {
-      const IlDesc e = p2::desc(C0, C1, a1.arr[0].act, j);
-      const IlFetch f = p2::fetch(C0, C1, j);
-      same = std::memcmp(&e, &a1.il_desc[j], sizeof(e)) == 0 && std::memcmp(&f, &a1.il_fetch[j], sizeof(f)) == 0;
-    }
-    if (same)
-    {
-      a1.p2_ok = 1;
-      a1.p2_c0 = C0;
-      a1.p2_c1 = C1;
-    }
+    a1.p2_c0 = a1.arr[0].channels;
+    a1.p2_c1 = a1.arr[1].channels;
   }
 }
 

@@ -55,8 +55,8 @@ def test_a1_standard_has_no_sample_rate_and_fast_kernels(nam_lib):
     ("lstm", 0)])
 def test_kernel_eligibility_reported_by_the_plan_compiler(nam_lib, name, bits):
     """has_a1_kernel: bit 0 = the VALU A1 kernel, bit 1 = one of the MFMA kernels (plan_a1.cpp: build_a1 / build_a1_ws /
-    build_a1_kt), bit 2 = the interleaved-frame MFMA kernel (build_a1_il), bit 3 = its compile-time-topology
-    form for the official sizes (plan.h: namespace p2), bit 4 = nam_wn_reg_kernel (plan_wr.cpp: build_wr). Decided on the host at load time, so it is checkable without a GPU."""
+    build_a1_kt), bits 2 and 3 = the interleaved-frame MFMA kernels: the model's own geometry is what their compile-time
+    tables say (plan_a1.cpp: build_a1_il — a1_il_fits and a1_is_p2; plan.h: namespace p2), bit 4 = nam_wn_reg_kernel (plan_wr.cpp: build_wr). Decided on the host at load time, so it is checkable without a GPU."""
     assert nam_lib.get_dsp(model_path(name)).info.has_a1_kernel == bits
 
 
@@ -82,6 +82,33 @@ def _variant(name, mutate):
     j = json.load(open(model_path(name)))
     mutate(j)
     return json.dumps(j)
+
+
+def _dilation(array, old, new):
+    def mutate(j):
+        d = j["config"]["layers"][array]["dilations"]
+        d[d.index(old)] = new
+    return mutate
+
+
+@pytest.mark.parametrize("mutate,il,p2", [
+    (_dilation(0, 512, 256), 1, 0),  # whole blocks back, but not the official topology's ring
+    (_dilation(0, 128, 192), 1, 0),
+    (_dilation(0, 2, 3), 1, 0),  # taps through the LDS window (2 d <= 64)
+    (_dilation(0, 32, 48), 0, 0),  # tap 0 at 96 frames: across a block boundary at a lookback that is no whole block
+    (lambda j: j["config"]["layers"][1].__setitem__("activation", "ReLU"), 1, 0),  # array 0 keeps Tanh
+], ids=["512to256", "128to192", "2to3", "32to48", "activations_differ"])
+def test_near_misses_of_the_official_topology_keep_the_general_kernels(nam_lib, mutate, il, p2):
+    """wavenet_a1_standard with one thing changed (a dilation: the weight count stays): the interleaved-frame mapping
+    may still fit (a1_il), the compile-time tables no longer describe the model (a1_p2), and has_a1_kernel offers VALU + MFMA."""
+    m = nam_lib.get_dsp_json(_variant("wavenet_a1_standard", mutate))
+    assert f" a1_valu=1 a1_mfma=1 kt_mfma=0 kp=0 a1_il={il} a1_p2={p2}" in m.describe()
+    assert m.info.has_a1_kernel == 3
+
+
+@pytest.mark.parametrize("name", ["wavenet_a1_standard", "synth_a1_lite", "synth_a1_feather"])
+def test_official_sizes_run_the_compile_time_tables(nam_lib, name):
+    assert " a1_il=1 a1_p2=1" in nam_lib.get_dsp(model_path(name)).describe()
 
 
 def test_reference_error_behaviour(nam_lib, tmp_path):
