@@ -1,8 +1,15 @@
 // il_common.h — helpers shared by the interleaved-frame kernels (kernel_a1_p2.hip and the pipelines built on its lane layout and
-// session protocol: kernel_a1_p4.hip, kernel_a1_q.hip, kernel_kq.hip). The descriptor-driven form of the mapping,
-// nam_a1_il_kernel, and its run-time job tables are gone: the job table is plan.h's namespace p2, compile-time constants in the
-// A1 kernels here; the plan compiler admits a model only if its geometry is what those say (plan_a1.cpp: build_a1_il), and
-// topologies outside them run nam_a1_mfma_kernel.
+// session protocol: kernel_a1_p4.hip, kernel_a1_q.hip, kernel_kq.hip); kernel_kt_mfma.hip includes it for weights_of,
+// kernel_lstm.hip for for_each_index. The job table of the A1 kernels is plan.h's namespace p2, compile-time constants; the plan
+// compiler admits a model only if its geometry is what those say (plan_a1.cpp: build_a1_il), and topologies outside them run
+// nam_a1_mfma_kernel. What it holds:
+//   * the lane-layout pieces: Slot / Ops, row_shr / dpp_taps, for_each_index, kOob;
+//   * weights_of<BANK>: what a workgroup reads its weights from (one model or a bank member);
+//   * the pipelines' ring addressing, once: i4 / sb_load4 / sb_store4 (the struct-buffer intrinsics), ring_desc, wrap_row /
+//     wrap_s, stage_write_positions, and wait_lds_word (p4's and kq's LDS word wait; q's scalar-unit form stays in q);
+//   * session_wait_command / session_leaving: how a session launch waits for its next command.
+// Each kernel keeps its own stream prologue (stream, state, input / output rows and their descriptors): moved into a shared
+// helper it compiles to other device code in p4 and kq (profiles/il_prologue/README.md).
 #pragma once
 #include "device_common.h"
 
@@ -80,6 +87,68 @@ __device__ __forceinline__ Weights weights_of(const float* __restrict__ blob, co
   }
   else
     return Weights{blob, a.head_scale, a.act_p0};
+}
+
+// MUBUF with index AND offset registers (address = base + soffset + index * stride + offset): the ring row index goes
+// in as it is — no multiply / shift / add per address — and an index beyond num_records makes the access a no-op. clang
+// has builtins for the raw form only; the LLVM intrinsics are declared by name (the compiler's wait-count bookkeeping
+// covers them like any other vector-memory instruction).
+using i4 = __attribute__((ext_vector_type(4))) int;
+__device__ f4 sb_load4(i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.load.v4f32");
+__device__ void sb_store4(f4 v, i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.store.v4f32");
+
+// A descriptor of the stream's rings with the row pitch as the stride (64 bytes: 16-channel rows, 32 bytes: 8-channel rows
+// ...): an access names its row by INDEX and its ring by the scalar offset. `rows` = num_records, far above every real row
+// index: an index no descriptor holds (the kernels' kNoRow) drops the access / returns 0 without a compare.
+__device__ __forceinline__ i4 ring_desc(const float* st, int row_b, int rows)
+{
+  const unsigned long long st_addr = (unsigned long long)st;
+  return i4{uni((int)(unsigned)st_addr), uni((int)((unsigned)(st_addr >> 32) & 0xffffu) | (row_b << 16)), rows, 0x00020000};
+}
+// row (sb + off) mod R for a wave-uniform sb in [0, R) and a lane offset below 64 <= R (kNoRow on either side stays beyond
+// num_records)
+__device__ __forceinline__ unsigned wrap_row(int sb, unsigned off, unsigned R)
+{
+  const unsigned v = (unsigned)sb + off;
+  return min(v, v - R);
+}
+__device__ __forceinline__ int wrap_s(int v, int R) // wave-uniform, v in (-R, R)
+{
+  v += v < 0 ? R : 0;
+  return v;
+}
+// The write positions of stage S's rings as SCALARS, advanced on the scalar unit from here on: wp[u] = ring of job
+// FIRST_JOB(S) + u, from wposv (lane r = write position of ring r = job r). FIRST_JOB(s): first job of stage s, stage NST = end.
+// (S and wposv by reference and plain `inline`: by value the pipelines' register allocation moves.)
+template <int NST, int (*FIRST_JOB)(int), int MAXJ>
+__device__ inline void stage_write_positions(const int& S, const int& wposv, int (&wp)[MAXJ])
+{
+  for_each_index(
+    [&](auto s_tag) {
+      constexpr int SS = decltype(s_tag)::value;
+      if (S == SS)
+      {
+        constexpr int J0 = FIRST_JOB(SS), NJS = FIRST_JOB(SS + 1) - J0;
+#pragma unroll
+        for (int u = 0; u < MAXJ; u++)
+          wp[u] = u < NJS ? __builtin_amdgcn_readlane(wposv, J0 + (u < NJS ? u : 0)) : 0;
+      }
+    },
+    std::make_integer_sequence<int, NST>{});
+}
+// Until the LDS word at byte_addr has reached `want`. The pipelines' synchronisation words have ONE writer each (plain
+// stores, no atomics); the waiting side polls from inline asm — a wait loop in C++ is a LOOP to the compiler: it splits the
+// live ranges of the request slots around it, shuffles them with copies at the joins and drains every ring request in flight
+// (vmcnt(0)) to do so; an asm statement is straight-line code. One wave's LDS operations execute in program order: "data,
+// then flag" needs nothing in between.
+__device__ __forceinline__ void wait_lds_word(unsigned byte_addr, int want)
+{
+  int tmp;
+  asm volatile("1:\n\tds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)\n\tv_sub_u32 %0, %0, %2\n\tv_cmp_gt_i32 vcc, 0, %0\n\t"
+               "s_cbranch_vccz 2f\n\ts_sleep 1\n\ts_branch 1b\n2:"
+               : "=&v"(tmp)
+               : "v"(byte_addr), "v"(want)
+               : "vcc");
 }
 } // namespace il
 

@@ -36,14 +36,6 @@ namespace namhip
 // Same state (rings, write positions), weights and LDS tiles as nam_a1_p2_kernel — the two alternate freely between
 // launches of one stream; sums are associated differently (one chain per product): equal to ~1e-6.
 // ================================================================================================
-// MUBUF with index AND offset registers (address = base + soffset + index * stride + offset): the ring row index goes
-// in as it is — no multiply / shift / add per address — and an index beyond num_records makes the access a no-op. clang
-// has builtins for the raw form only; the LLVM intrinsics are declared by name (the compiler's wait-count bookkeeping
-// covers them like any other vector-memory instruction).
-using p4_i4 = __attribute__((ext_vector_type(4))) int;
-__device__ mf::f4 p4_sb_load(p4_i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.load.v4f32");
-__device__ void p4_sb_store(mf::f4 v, p4_i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.store.v4f32");
-
 namespace p4
 {
 constexpr int kNoRow = 1 << 26; // a ring row index no descriptor holds: the access is dropped / returns 0
@@ -62,6 +54,8 @@ constexpr int first_job(int nst, int s)
     return s == 1 ? 6 : 13; // 6 full-width | 4 full + 3 half | 7 half-width jobs
   return 5 * s; // four stages of five
 }
+template <int NST>
+constexpr int first_job_of(int s) { return first_job(NST, s); }
 constexpr int stage_of(int nst, int job)
 {
   int s = 0;
@@ -108,6 +102,7 @@ template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, int NST, bool BANK =
 __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __restrict__ blob0, const A1Args a)
 {
   using namespace mf;
+  using il::i4;
   using il::kOob;
   using il::Ops;
   constexpr int NJ = p2::kJobs, MAXJ = p4::max_jobs(NST);
@@ -139,7 +134,6 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
   const int io_bytes = PERSIST ? 0x7ffffff0 : a.n_frames * 4;
   const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc((void*)(in ? in : st), 0, in ? io_bytes : 0, 0x00020000);
   const auto rsrc_out = __builtin_amdgcn_make_buffer_rsrc((void*)(out ? out : st), 0, out ? io_bytes : 0, 0x00020000);
-  using i4 = __attribute__((ext_vector_type(4))) int;
   // rsrc_in once more, as plain dwords (base, stride 0, num_records, flags): for the one load issued from inline asm
   const unsigned long long in_addr = (unsigned long long)(in ? in : st);
   const i4 in_desc = {uni((int)(unsigned)in_addr), uni((int)(unsigned)(in_addr >> 32) & 0xffff), in ? io_bytes : 0, 0x00020000};
@@ -162,33 +156,16 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
   const f4 c0v = csrc[min(tid, NJ * 16 - 1)]; // 320 constant records
   const f4 x0v = xsrc[min(tid, p2::kXt * 64 - 1)]; // 192 extra-tile records
 
-  // Ring descriptors with the row pitch as the stride (64 bytes: 16-channel rows, 32 bytes: 8-channel rows ...): a ring
-  // access names its row by INDEX. Lane constants: the lane's channel-quad byte offset inside a row when it appends
-  // (app_off) and when it fetches history (fch[array]: the half layout reads quad g & 1), and its frame `t` as an index
-  // offset — kNoRow for the lanes of an array that hold no channels (their appends drop out without a compare).
-  const unsigned long long st_addr = (unsigned long long)st;
-  auto ring_desc = [&](int row_b) {
-    return i4{uni((int)(unsigned)st_addr), uni((int)((unsigned)(st_addr >> 32) & 0xffffu) | (row_b << 16)), p4::kRows, 0x00020000};
-  };
-  const i4 rs_a0 = ring_desc(C0 * 4), rs_a1 = ring_desc(C1 * 4);
+  // One ring descriptor per array (il_common.h: ring_desc). Lane constants: the lane's channel-quad byte offset inside a row
+  // when it appends (app_off) and when it fetches history (fch[array]: the half layout reads quad g & 1), and its frame `t`
+  // as an index offset — kNoRow for the lanes of an array that hold no channels (their appends drop out without a compare).
+  const i4 rs_a0 = il::ring_desc(st, C0 * 4, p4::kRows), rs_a1 = il::ring_desc(st, C1 * 4, p4::kRows);
   const int fch0 = (int)min(C0 == 8 ? (v_g16 & 16u) : v_g16, (unsigned)(C0 * 4 - 16)); // (8 channels: the half layout)
   const int fch1 = (int)min(C1 == 8 ? (v_g16 & 16u) : v_g16, (unsigned)(C1 * 4 - 16));
   auto tl_app_of = [&](int nv, int C) { return (t < nv && (int)v_g16 <= 16 * (C / 4 - 1)) ? t : p4::kNoRow; };
   int tl_app0 = tl_app_of(kBlock, C0), tl_app1 = tl_app_of(kBlock, C1);
-  // the write positions of this stage's rings as SCALARS (wp[u] = ring of job J0 + u): advanced on the scalar unit
-  int wp[MAXJ];
-  il::for_each_index(
-    [&](auto s_tag) {
-      constexpr int SS = decltype(s_tag)::value;
-      if (S == SS)
-      {
-        constexpr int J0 = p4::first_job(NST, SS), NJS = p4::first_job(NST, SS + 1) - J0;
-#pragma unroll
-        for (int u = 0; u < MAXJ; u++)
-          wp[u] = u < NJS ? __builtin_amdgcn_readlane(wposv, J0 + (u < NJS ? u : 0)) : 0;
-      }
-    },
-    std::make_integer_sequence<int, NST>{});
+  int wp[MAXJ]; // the write positions of this stage's rings as scalars (wp[u] = ring of job J0 + u)
+  il::stage_write_positions<NST, p4::first_job_of<NST>>(S, wposv, wp);
   // the ring requests of job TJ for the block AHEAD blocks after the one the write positions stand at; `wpj`: the
   // job's write position, `valid`: wave-uniform
   auto fetch = [&](f4& ra, f4& rb, auto tj_tag, auto ahead_tag, bool valid, int tl, int wpj) {
@@ -206,14 +183,12 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
       if (L > 0) // (compile time: exchange jobs have one request)
       {
         // row of lane frame tl: (wpj + AHEAD * 64 - L + tl) mod R — the lane-independent part on the scalar unit
-        int sb_ = wpj + (AHEAD ? kBlock : 0) - L;
-        sb_ += sb_ < 0 ? F.R : 0;
+        int sb_ = il::wrap_s(wpj + (AHEAD ? kBlock : 0) - L, F.R);
         sb_ -= sb_ >= F.R ? F.R : 0;
         sb_ = valid ? sb_ : p4::kNoRow;
         const int tq = n >= 16 ? tl : (tl < 4 * n ? tl : p4::kNoRow); // lanes j < n only
-        const unsigned v = (unsigned)(sb_ + tq);
-        const int idx = (int)min(v, v - (unsigned)F.R);
-        const f4 r = p4_sb_load(arr1 ? rs_a1 : rs_a0, idx, arr1 ? fch1 : fch0, F.ring_b, 0);
+        const int idx = (int)il::wrap_row(sb_, (unsigned)tq, F.R);
+        const f4 r = il::sb_load4(arr1 ? rs_a1 : rs_a0, idx, arr1 ? fch1 : fch0, F.ring_b, 0);
         if (q == 0)
           ra = r;
         else
@@ -237,20 +212,11 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
   // Synchronisation words in LDS, each with ONE writer (so plain stores, no atomics): wave w of stage s publishes its
   // barrier generation in flags[4 s + w]; producer wave w of queue q its count of buffers handed over in
   // flags[16 + 8 q + w], the consumer wave its count taken out in flags[16 + 8 q + 4 + w]. The waiting side polls
-  // from inline asm — a wait loop in C++ is a LOOP to the compiler: it splits the live ranges of the request slots
-  // around it, shuffles them with copies at the joins and drains every ring request in flight (vmcnt(0)) to do so; an
-  // asm statement is straight-line code. One wave's LDS operations execute in program order: "data, then flag" needs
-  // nothing in between. The queue's data moves inside the same asm statements as its flags (volatile asm statements
-  // keep their order; plain LDS accesses may move across them, which is harmless: different addresses).
+  // from inline asm (il_common.h: wait_lds_word, and why). The queue's data moves inside the same asm statements as its
+  // flags (volatile asm statements keep their order; plain LDS accesses may move across them, which is harmless:
+  // different addresses).
   const unsigned flag_b = (unsigned)p4::kFlagB;
-  auto wait_word = [&](unsigned byte_addr, int want) { // until the word has reached `want`
-    int tmp;
-    asm volatile("1:\n\tds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)\n\tv_sub_u32 %0, %0, %2\n\tv_cmp_gt_i32 vcc, 0, %0\n\t"
-                 "s_cbranch_vccz 2f\n\ts_sleep 1\n\ts_branch 1b\n2:"
-                 : "=&v"(tmp)
-                 : "v"(byte_addr), "v"(want)
-                 : "vcc");
-  };
+  auto wait_word = [&](unsigned byte_addr, int want) { il::wait_lds_word(byte_addr, want); }; // until the word has reached `want`
   int bar_gen = 0; // this wave's count of stage barriers passed
   auto stage_barrier = [&]() { // the four waves of this stage: every wave publishes its generation, waits for all four
     asm volatile("" ::: "memory"); // (the exchange window's plain stores / loads stay on their side)
@@ -449,9 +415,8 @@ __global__ __launch_bounds__(NST * 256) void nam_a1_p4_kernel(const float* __res
     // this job's input -> its history ring: row (position + frame) mod R; lanes without channels carry kNoRow
     const int wpj = wp[SL];
     {
-      const unsigned v = (unsigned)(wpj + (arr1 ? tl_app1 : tl_app0));
-      const int widx = (int)min(v, v - (unsigned)J.R);
-      p4_sb_store(x, arr1 ? rs_a1 : rs_a0, widx, (int)gl16, J.ring_b, WT && !PERSIST ? 17 : 0);
+      const int widx = (int)il::wrap_row(wpj, (unsigned)(arr1 ? tl_app1 : tl_app0), J.R);
+      il::sb_store4(x, arr1 ? rs_a1 : rs_a0, widx, (int)gl16, J.ring_b, WT && !PERSIST ? 17 : 0);
     }
     // persistent session, stage 0: every wave looks at the next ring slot in job 1 and, when the command is already
     // there, requests the next buffer's input sample from it in job 3 (unconditional load, out-of-range offset on a miss)

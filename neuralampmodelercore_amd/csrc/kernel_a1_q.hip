@@ -37,10 +37,6 @@ namespace namhip
 //     buffer ahead into registers. HBM traffic per stream and buffer: 48 KB instead of 114.
 // Sums: one chain per product seeded with bias + mixin * input, taps oldest first (as nam_a1_p4_kernel / nam_kq_kernel).
 // ================================================================================================
-using aq_i4 = __attribute__((ext_vector_type(4))) int;
-__device__ mf::f4 aq_sb_load4(aq_i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.load.v4f32");
-__device__ void aq_sb_store4(mf::f4 v, aq_i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.store.v4f32");
-
 // The activations with every fused multiply-add spelled out and contraction off: the compiler's own choice of what to fuse
 // differs between instantiations of one kernel (it depends on the code around the expression), and a session must render
 // bit for bit what a plain launch renders (tests/test_gpu_breadth.py: test_pipelined_kernel_against_the_four_wave_kernel).
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     dbg_t[0] = clock64();
   using namespace mf;
   using il::kOob;
-  using i4 = aq_i4;
+  using il::i4;
   constexpr int NST = aq::kNst;
   extern __shared__ __attribute__((aligned(16))) float lds_aq[];
   char* const lds = reinterpret_cast<char*>(lds_aq);
@@ -226,22 +222,10 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     }
   };
 
-  // The stream's rings through two descriptors with the row pitch as the stride (64 / 32 bytes): an access names its row by
-  // index and its ring by the scalar offset; kNoRow drops it.
-  const unsigned long long st_addr = (unsigned long long)st;
-  auto ring_desc = [&](int row_b) {
-    return i4{uni((int)(unsigned)st_addr), uni((int)((unsigned)(st_addr >> 32) & 0xffffu) | (row_b << 16)), aq::kRowsMax, 0x00020000};
-  };
-  const i4 rs16 = ring_desc(aq::kC0 * 4), rs8 = ring_desc(aq::kC1 * 4);
-  // row (sb + off) mod R for a wave-uniform sb in [0, R) and a lane offset below 64 <= R
-  auto wrap_row = [](int sb, unsigned off, unsigned R) {
-    const unsigned v = (unsigned)sb + off;
-    return min(v, v - R);
-  };
-  auto wrap_s = [](int v, int R) { // wave-uniform, v in (-R, R)
-    v += v < 0 ? R : 0;
-    return v;
-  };
+  // the stream's rings through two descriptors (64- / 32-byte rows: il_common.h); kNoRow drops an access
+  const i4 rs16 = il::ring_desc(st, aq::kC0 * 4, aq::kRowsMax), rs8 = il::ring_desc(st, aq::kC1 * 4, aq::kRowsMax);
+  using il::wrap_row;
+  using il::wrap_s;
 
   constexpr bool kOutHost = PERSIST && WT; // (kernel_a1_p4.hip: a session whose results go to host memory)
   constexpr int kInAux = PERSIST ? 17 : 0; // session inputs bypass the caches (the caller may rewrite the buffer between commands)
@@ -337,10 +321,10 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     constexpr int R = decltype(r_tag)::value;
     mf::f4 v;
     if (t + 16 <= R)
-      v = aq_sb_load4(rs, lane & 15, voff, ring_off_b + t * row_b, 0);
+      v = il::sb_load4(rs, lane & 15, voff, ring_off_b + t * row_b, 0);
     else
     {
-      v = aq_sb_load4(rs, (int)wrap_row(t, (unsigned)(lane & 15), R), voff, ring_off_b, 0);
+      v = il::sb_load4(rs, (int)wrap_row(t, (unsigned)(lane & 15), R), voff, ring_off_b, 0);
       asm volatile("" ::: "memory"); // (two loads, not one behind a select of its operands)
     }
     return v;
@@ -360,7 +344,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     for (int i = 0; i < NI; i++)
     {
       const int row = i * per + rl;
-      t[i] = aq_sb_load4(wide ? rs16 : rs8, row < R ? row : aq::kNoRow, (int)(pl * 16u), ring_off_f * 4, 0);
+      t[i] = il::sb_load4(wide ? rs16 : rs8, row < R ? row : aq::kNoRow, (int)(pl * 16u), ring_off_f * 4, 0);
     }
 #pragma unroll
     for (int i = 0; i < NI; i++)
@@ -386,7 +370,7 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
     for (int i = 0; i < NI; i++)
     {
       const int row = i * per + rl;
-      aq_sb_store4(t[i], wide ? rs16 : rs8, row < R ? row : aq::kNoRow, (int)(pl * 16u), ring_off_f * 4, kWbAux);
+      il::sb_store4(t[i], wide ? rs16 : rs8, row < R ? row : aq::kNoRow, (int)(pl * 16u), ring_off_f * 4, kWbAux);
     }
   };
 
@@ -580,10 +564,10 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
       {
         // (a session's buffers are whole; elsewhere only a launch's last buffer is ragged)
         if ((PERSIST || 16 * i + 16 <= nvalid) && sb + 16 <= R)
-          aq_sb_store4(xs, rs16, n, (int)g16, aq::ring_off(JI) * 4 + sb * (aq::kC0 * 4), kAppAux);
+          il::sb_store4(xs, rs16, n, (int)g16, aq::ring_off(JI) * 4 + sb * (aq::kC0 * 4), kAppAux);
         else
         {
-          aq_sb_store4(xs, rs16, (PERSIST || 16 * i + n < nvalid) ? (int)wrap_row(sb, (unsigned)n, R) : aq::kNoRow, (int)g16, aq::ring_off(JI) * 4, kAppAux);
+          il::sb_store4(xs, rs16, (PERSIST || 16 * i + n < nvalid) ? (int)wrap_row(sb, (unsigned)n, R) : aq::kNoRow, (int)g16, aq::ring_off(JI) * 4, kAppAux);
           asm volatile("" ::: "memory");
         }
       }
@@ -861,8 +845,8 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
       for (int j = 0; j < 2; j++)
       {
         const int idx = (int)wrap_row(wrap_s(wpj - (2 - j) * D, R), (unsigned)frame, R);
-        far[FI][j].q0 = aq_sb_load4(rs8, idx, 0, aq::ring_off(TJ) * 4, 0);
-        far[FI][j].q1 = aq_sb_load4(rs8, idx, 16, aq::ring_off(TJ) * 4, 0);
+        far[FI][j].q0 = il::sb_load4(rs8, idx, 0, aq::ring_off(TJ) * 4, 0);
+        far[FI][j].q1 = il::sb_load4(rs8, idx, 16, aq::ring_off(TJ) * 4, 0);
       }
     };
     il::for_each_index(
@@ -914,8 +898,8 @@ __global__ __launch_bounds__(aq::kNst * 64) void nam_a1_q_kernel(const float* __
       if constexpr (!RES)
       {
         const int widx = frame < nvalid ? (int)row0 : aq::kNoRow;
-        aq_sb_store4(x0, rs8, widx, 0, aq::ring_off(JI) * 4, kAppAux);
-        aq_sb_store4(x1, rs8, widx, 16, aq::ring_off(JI) * 4, kAppAux);
+        il::sb_store4(x0, rs8, widx, 0, aq::ring_off(JI) * 4, kAppAux);
+        il::sb_store4(x1, rs8, widx, 16, aq::ring_off(JI) * 4, kAppAux);
       }
       int wpn = wpj + nvalid;
       wpn -= wpn >= R ? R : 0;

@@ -33,10 +33,6 @@ namespace namhip
 //   * weights: one 256-byte tile per tap in LDS [lane % 4][h][c], read as four broadcast b128.
 // Sums: per output half one chain per layer seeded with bias + mixin * input, taps oldest first, input channels in order.
 // ================================================================================================
-using kq_i4 = __attribute__((ext_vector_type(4))) int;
-__device__ mf::f4 kq_sb_load4(kq_i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.load.v4f32");
-__device__ void kq_sb_store4(mf::f4 v, kq_i4 rsrc, int vindex, int voffset, int soffset, int aux) __asm("llvm.amdgcn.struct.buffer.store.v4f32");
-
 namespace kq
 {
 using namespace kp;
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
 {
   using namespace mf;
   using il::kOob;
-  using i4 = kq_i4;
+  using il::i4;
   constexpr int NST = kq::kNst, NJ = kq::kJobs, MAXJ = kq::max_jobs(), MAXF = kq::max_far();
   extern __shared__ __attribute__((aligned(16))) float lds_kq[];
   char* const lds = reinterpret_cast<char*>(lds_kq);
@@ -206,26 +202,11 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
   const f4 rech0 = *reinterpret_cast<const f4*>(w.blob + a.tiles_off + kq::kBlobRech);
   const f4 rech1 = *reinterpret_cast<const f4*>(w.blob + a.tiles_off + kq::kBlobRech + 4);
 
-  // The stream's rings through ONE descriptor with the row pitch (32 bytes) as the stride: an access names its row by
-  // index and its ring by the scalar offset; kNoRow drops it.
-  const unsigned long long st_addr = (unsigned long long)st;
-  const i4 rs = {uni((int)(unsigned)st_addr), uni((int)((unsigned)(st_addr >> 32) & 0xffffu) | ((kq::kC * 4) << 16)), kq::kRows, 0x00020000};
+  const i4 rs = il::ring_desc(st, kq::kC * 4, kq::kRows); // the stream's rings through ONE descriptor (32-byte rows); kNoRow drops an access
   auto app_of = [&](int nv) { return frame < nv ? frame : kq::kNoRow; };
   int app_idx = app_of(kBlock); // this lane's frame as a row offset when it appends
-  // the write positions of this stage's rings as SCALARS (wp[u] = ring of job J0 + u)
-  int wp[MAXJ];
-  il::for_each_index(
-    [&](auto s_tag) {
-      constexpr int SS = decltype(s_tag)::value;
-      if (S == SS)
-      {
-        constexpr int J0 = kq::first_job(SS), NJS = kq::first_job(SS + 1) - J0;
-#pragma unroll
-        for (int u = 0; u < MAXJ; u++)
-          wp[u] = u < NJS ? __builtin_amdgcn_readlane(wposv, J0 + (u < NJS ? u : 0)) : 0;
-      }
-    },
-    std::make_integer_sequence<int, NST>{});
+  int wp[MAXJ]; // the write positions of this stage's rings as scalars (wp[u] = ring of job J0 + u)
+  il::stage_write_positions<NST, kq::first_job>(S, wposv, wp);
   // a ring row per lane: frame f of the buffer that starts at write position `wpj`, `L` frames back
   struct Row
   {
@@ -234,12 +215,9 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
   auto fetch = [&](Row& R_, auto tj_tag, int L, int wpj, int fq) {
     constexpr int TJ = decltype(tj_tag)::value;
     constexpr int RL = kq::ring_len(TJ);
-    int sb_ = wpj - L;
-    sb_ += sb_ < 0 ? RL : 0;
-    const unsigned v = (unsigned)(sb_ + fq);
-    const int idx = (int)min(v, v - (unsigned)RL);
-    R_.q0 = kq_sb_load4(rs, idx, 0, kq::ring_off(TJ) * 4, 0);
-    R_.q1 = kq_sb_load4(rs, idx, 16, kq::ring_off(TJ) * 4, 0);
+    const int idx = (int)il::wrap_row(il::wrap_s(wpj - L, RL), (unsigned)fq, RL);
+    R_.q0 = il::sb_load4(rs, idx, 0, kq::ring_off(TJ) * 4, 0);
+    R_.q1 = il::sb_load4(rs, idx, 16, kq::ring_off(TJ) * 4, 0);
   };
   Row rows[MAXF > 0 ? MAXF : 1];
   float inp = 0.0f;
@@ -251,14 +229,7 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
   };
   // ---- queues: kernel_a1_p4.hip's one-slot queues, one wave on either side ----
   const unsigned flag_b = (unsigned)kq::kFlagB;
-  auto wait_word = [&](unsigned byte_addr, int want) { // until the word has reached `want`
-    int tmp;
-    asm volatile("1:\n\tds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)\n\tv_sub_u32 %0, %0, %2\n\tv_cmp_gt_i32 vcc, 0, %0\n\t"
-                 "s_cbranch_vccz 2f\n\ts_sleep 1\n\ts_branch 1b\n2:"
-                 : "=&v"(tmp)
-                 : "v"(byte_addr), "v"(want)
-                 : "vcc");
-  };
+  auto wait_word = [&](unsigned byte_addr, int want) { il::wait_lds_word(byte_addr, want); }; // until the word has reached `want`
   auto queue_put = [&](int q, int k, const f4& x0, const f4& x1, const f4& h0, const f4& h1, float vc, const i4& tok) {
     const unsigned slot = (unsigned)kq::kQueueB + (unsigned)(q * kq::kSlotB);
     const unsigned prod = flag_b + (unsigned)(16 + 2 * q) * 4u, cons = flag_b + (unsigned)(16 + 2 * q + 1) * 4u;
@@ -392,7 +363,7 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
               {
                 const int r = r0 + frame;
                 const int idx = r < RL ? r : kq::kNoRow;
-                const f4 q0 = kq_sb_load4(rs, idx, 0, kq::ring_off(TJ) * 4, 0), q1 = kq_sb_load4(rs, idx, 16, kq::ring_off(TJ) * 4, 0);
+                const f4 q0 = il::sb_load4(rs, idx, 0, kq::ring_off(TJ) * 4, 0), q1 = il::sb_load4(rs, idx, 16, kq::ring_off(TJ) * 4, 0);
                 const unsigned rw = (unsigned)(r < RL ? r : RL) * 16u;
                 lds_st4(lds, (unsigned)WB0 + rw, q0);
                 lds_st4(lds, (unsigned)WB1 + rw, q1);
@@ -435,18 +406,14 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
     const int wpj = wp[U];
     if (!(lazy && kq::far_taps(JI) == 0 && T > 0))
     {
-      const unsigned v = (unsigned)(wpj + app_idx);
-      const int widx = (int)min(v, v - (unsigned)RL);
-      kq_sb_store4(in0, rs, widx, 0, kq::ring_off(JI) * 4, WT && !PERSIST ? 17 : 0);
-      kq_sb_store4(in1, rs, widx, 16, kq::ring_off(JI) * 4, WT && !PERSIST ? 17 : 0);
+      const int widx = (int)il::wrap_row(wpj, (unsigned)app_idx, RL);
+      il::sb_store4(in0, rs, widx, 0, kq::ring_off(JI) * 4, WT && !PERSIST ? 17 : 0);
+      il::sb_store4(in1, rs, widx, 16, kq::ring_off(JI) * 4, WT && !PERSIST ? 17 : 0);
     }
     unsigned old16 = 0; // resident ring: byte offset of the lane's OLDEST tap row, (position - T + frame) mod R; tap j is j d rows on
     if constexpr (T > kBlock)
     {
-      int sb_ = wpj - T;
-      sb_ += sb_ < 0 ? RL : 0;
-      const unsigned v = (unsigned)(sb_ + frame);
-      old16 = min(v, v - (unsigned)RL) * 16u;
+      old16 = il::wrap_row(il::wrap_s(wpj - T, RL), (unsigned)frame, RL) * 16u;
       // this buffer's row: (position + frame) mod R, as the append to the HBM ring would have it = T rows on from the oldest tap
       const unsigned c = old16 + (unsigned)(T * 16);
       const unsigned cur16 = min(c, c - (unsigned)(RL * 16));
@@ -750,12 +717,9 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
                 asm volatile("" : "+v"(fr));
                 const unsigned row = (unsigned)(fr < T ? fr : 0) * 16u;
                 const f4 q0 = lds_ld4(lds, (unsigned)WB0 + row), q1 = lds_ld4(lds, (unsigned)WB1 + row);
-                int sb_ = wp[U] - T;
-                sb_ += sb_ < 0 ? RL : 0;
-                const unsigned v = (unsigned)(sb_ + fr);
-                const int idx = fr < T ? (int)min(v, v - (unsigned)RL) : kq::kNoRow;
-                kq_sb_store4(q0, rs, idx, 0, kq::ring_off(TJ) * 4, 0);
-                kq_sb_store4(q1, rs, idx, 16, kq::ring_off(TJ) * 4, 0);
+                const int idx = fr < T ? (int)il::wrap_row(il::wrap_s(wp[U] - T, RL), (unsigned)fr, RL) : kq::kNoRow;
+                il::sb_store4(q0, rs, idx, 0, kq::ring_off(TJ) * 4, 0);
+                il::sb_store4(q1, rs, idx, 16, kq::ring_off(TJ) * 4, 0);
               }
               else if constexpr (T > kBlock) // the resident ring goes back as it lies
               {
@@ -767,8 +731,8 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
                   const int r = r0 + fr;
                   const unsigned row = (unsigned)(r < RL ? r : 0) * 16u;
                   const f4 q0 = lds_ld4(lds, (unsigned)WB0 + row), q1 = lds_ld4(lds, (unsigned)WB1 + row);
-                  kq_sb_store4(q0, rs, r < RL ? r : kq::kNoRow, 0, kq::ring_off(TJ) * 4, 0);
-                  kq_sb_store4(q1, rs, r < RL ? r : kq::kNoRow, 16, kq::ring_off(TJ) * 4, 0);
+                  il::sb_store4(q0, rs, r < RL ? r : kq::kNoRow, 0, kq::ring_off(TJ) * 4, 0);
+                  il::sb_store4(q1, rs, r < RL ? r : kq::kNoRow, 16, kq::ring_off(TJ) * 4, 0);
                 }
               }
             },
