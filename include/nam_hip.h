@@ -203,7 +203,11 @@ NAM_HIP_API void nam_hip_batch_destroy(nam_hip_batch* batch);
  *    Tanh or all Fasttanh); the LeakyReLU negative slope (<= 1) is per member, like head_scale. A SlimmableContainer (how A2
  *    captures ship: A2.nam holds A2-Lite and A2-Full) may be a member when its LARGEST submodel qualifies; the member IS that
  *    submodel — the one a batch of the container runs while no size has been set. No lookup tables.
- * The plans are compared field by field; the first difference — a member of the other family, or of another kind: LSTM, nano,
+ *  - the LSTM family (nam_lstm_row_kernel, nam_lstm_wide_kernel): LSTMs of ONE shape — the same layer count (1 or 2), input
+ *    size (1 or 2), hidden size (<= 32) and output channels —, loaded with the same fast_tanh, from files of one sample rate
+ *    (the prewarm is half a second of it). A member's initial state (h0 / c0, part of an LSTM's weight stream) is its own.
+ *    Larger cells run on kernels whose streams share one wavefront's weights: they are refused.
+ * The plans are compared field by field; the first difference — a member of another family, or of another kind: nano,
  * A2-Lite, FiLM / gated models, another activation type, a
  * slimmable model — is refused with NAM_HIP_ERR_UNSUPPORTED and a message naming the member index and the field. n_models <= 0
  * or a NULL member: NAM_HIP_ERR_INVALID_ARGUMENT. A bank of one model is legal. The bank copies what it needs: the models may
@@ -224,14 +228,17 @@ NAM_HIP_API int nam_hip_bank_n_models(const nam_hip_bank* bank);
  * in sessions and launches of several buffers (renders, the prewarm of Reset), nam_kt_mfma_kernel for a lone buffer and for
  * everything under NAM_HIP_MAX_STAGES=1; nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_A1_MFMA,
  * anything else is NAM_HIP_ERR_UNSUPPORTED; one launch of more than 2^28 frames (which a one-model batch hands to
- * nam_a1_kernel) is NAM_HIP_ERR_UNSUPPORTED: split it.
+ * nam_a1_kernel) is NAM_HIP_ERR_UNSUPPORTED: split it. Kernels of an LSTM bank: nam_lstm_row_kernel (hidden <= 4) or
+ * nam_lstm_wide_kernel for every launch shape and in sessions; nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO only
+ * (the matrix-core and lanes kernels know no banks), anything else is NAM_HIP_ERR_UNSUPPORTED.
  * Reset with prewarm runs the silence through every stream with its own member's weights (no cached image: it depends on the
  * weights); the state equals, bit for bit, what a one-model batch of that member holds after the same Reset. */
 NAM_HIP_API int nam_hip_batch_create_bank(const nam_hip_bank* bank, int device, int n_streams, int max_frames,
                                           const int* stream_model, nam_hip_batch** out_batch);
 /* Binds the listed streams (NULL: all) to `member`, following nam_hip_batch_set_slimmable_size's contract: a running session's
  * launch ends first (the kernels load weights in their prologue), the streams that change member start from a freshly reset
- * (and, if the batch was last reset with prewarm, prewarmed) state of the new member; every other stream's state and output
+ * (and, if the batch was last reset with prewarm, prewarmed) state of the new member — an LSTM member's own h0 / c0, then the
+ * prewarm: what a newly created one-model batch of that member holds after the same Reset —; every other stream's state and output
  * are untouched; a stream already bound to `member` is left alone. A stream or member out of range — or a batch that was not
  * created from a bank — is NAM_HIP_ERR_INVALID_ARGUMENT and changes nothing. */
 NAM_HIP_API int nam_hip_batch_set_stream_model(nam_hip_batch* batch, const int* stream_ids, int n_ids, int member);

@@ -11,8 +11,11 @@
 //  * BANK_A2: the A2 topology (kp_table.h) on nam_kq_kernel / nam_kt_mfma_kernel. Every member has the same channel counts, so
 //    the WHOLE blob has one layout: the bank keeps whole blobs (base offset 0) and A1Plan's absolute offsets (kt_desc[].tile_off,
 //    kt_rech_off, kt_lds_src_off, kq_w_off) hold against any member's row.
-// Per member besides the blob: the two scalars the kernels take by value (head_scale, act_p0 — on the A2 topology the LeakyReLU
-// slope, 0 for ReLU as in launch_kq).
+//  * BANK_LSTM: LSTMs of one shape on nam_lstm_row_kernel (hidden <= 4) / nam_lstm_wide_kernel (5 .. 32 units). Whole blobs again
+//    (base offset 0): LSTMPlan's absolute offsets (layer_w[], layer_b[], head_w, head_b) hold against any member's row. No A1Plan,
+//    no scalars; instead every member's initial state (h0 / c0 are part of an LSTM's weight stream: LSTMPlan::init_state).
+// Per member besides the blob, WaveNet families: the two scalars the kernels take by value (head_scale, act_p0 — on the A2
+// topology the LeakyReLU slope, 0 for ReLU as in launch_kq).
 #include "api_internal.h"
 
 namespace namhip
@@ -23,6 +26,8 @@ namespace
 {
 const char* family_name(int f)
 {
+  if (f == BANK_LSTM)
+    return "LSTM (nam_lstm_row_kernel / nam_lstm_wide_kernel)";
   return f == BANK_A2 ? "A2 (nam_kq_kernel)" : "A1_IL (nam_a1_q_kernel)";
 }
 
@@ -54,7 +59,16 @@ std::string member_refusal(const nam_hip_model& m, int* family)
   const ModelSpec& s = *m.spec;
   *family = BANK_A1_IL;
   if (s.arch == ARCH_LSTM)
-    return "an LSTM (banks hold WaveNets of the official topology or of the A2 topology)";
+  {
+    const LSTMPlan& L = member_plan(m).lstm;
+    if (!(lstm_row_eligible(L) || lstm_wide_eligible(L)))
+      return "an LSTM outside nam_lstm_row_kernel / nam_lstm_wide_kernel (hidden " + std::to_string(L.hidden) + ", "
+             + std::to_string(L.n_layers) + " layer(s), input_size " + std::to_string(L.input_size)
+             + ": more than 32 hidden units, more than two layers or more than two inputs run on nam_lstm_mfma_kernel / "
+               "nam_lstm_kernel, whose streams share one wavefront's weights: they know no banks)";
+    *family = BANK_LSTM;
+    return "";
+  }
   if (s.arch == ARCH_CONTAINER)
   {
     // a container stands for its largest submodel, and only in the A2 family (how A2 captures ship)
@@ -99,6 +113,29 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, in
     if (out.empty() && x != y)
       out = std::string(field) + " (" + std::to_string(x) + " vs " + std::to_string(y) + ")";
   };
+  if (family == BANK_LSTM)
+  {
+    // what nam_lstm_row_kernel / nam_lstm_wide_kernel are instantiated on and what their arguments take from the plan (member 0's)
+    const LSTMPlan &x = p.lstm, &y = q.lstm;
+    cmp("fast_tanh", x.fast ? 1 : 0, y.fast ? 1 : 0);
+    cmp("lstm.n_layers", x.n_layers, y.n_layers);
+    cmp("lstm.input_size", x.input_size, y.input_size);
+    cmp("lstm.hidden", x.hidden, y.hidden);
+    cmp("lstm.in_ch", x.in_ch, y.in_ch);
+    cmp("lstm.out_ch", x.out_ch, y.out_ch);
+    cmp("lstm.head_w", x.head_w, y.head_w);
+    cmp("lstm.head_b", x.head_b, y.head_b);
+    for (int l = 0; l < x.n_layers && l < 16; l++)
+    {
+      cmp("lstm.layer_w", x.layer_w[l], y.layer_w[l]);
+      cmp("lstm.layer_b", x.layer_b[l], y.layer_b[l]);
+    }
+    cmp("blob floats", (long long)p.blob.size(), (long long)q.blob.size());
+    cmp("lstm.init_state floats", (long long)x.init_state.size(), (long long)y.init_state.size());
+    cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples); // (half a second at the file's sample rate)
+    cmp("state_floats", p.state_floats, q.state_floats);
+    return out;
+  }
   if (family == BANK_A1_IL)
     cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
   cmp("in_channels", p.in_channels, q.in_channels);
@@ -164,21 +201,38 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, in
 } // namespace
 
 // The device image of a bank batch's one group (instead of upload_group): every member's kernel region in ONE allocation, the
-// per-member scalars, the per-stream member index.
+// per-member scalars (BANK_LSTM: the per-member initial states instead), the per-stream member index.
 int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
 {
   const nam_hip_bank_data& bank = *b->bank;
   const Plan& p = *g.plan;
   NAM_HIP_CHECK(hipMalloc(&g.d_blob, bank.blobs.size() * sizeof(float)));
   NAM_HIP_CHECK(hipMemcpy(g.d_blob, bank.blobs.data(), bank.blobs.size() * sizeof(float), hipMemcpyHostToDevice));
-  NAM_HIP_CHECK(hipMalloc(&g.d_a1, sizeof(A1Plan)));
-  NAM_HIP_CHECK(hipMemcpy(g.d_a1, &p.a1, sizeof(A1Plan), hipMemcpyHostToDevice));
-  NAM_HIP_CHECK(hipMalloc(&g.d_bank_scal, bank.scal.size() * sizeof(float)));
-  NAM_HIP_CHECK(hipMemcpy(g.d_bank_scal, bank.scal.data(), bank.scal.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (bank.family == BANK_LSTM)
+  {
+    NAM_HIP_CHECK(hipMalloc(&g.d_init, std::max<size_t>(bank.init.size(), 1) * sizeof(float)));
+    NAM_HIP_CHECK(hipMemcpy(g.d_init, bank.init.data(), bank.init.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  else
+  {
+    NAM_HIP_CHECK(hipMalloc(&g.d_a1, sizeof(A1Plan)));
+    NAM_HIP_CHECK(hipMemcpy(g.d_a1, &p.a1, sizeof(A1Plan), hipMemcpyHostToDevice));
+    NAM_HIP_CHECK(hipMalloc(&g.d_bank_scal, bank.scal.size() * sizeof(float)));
+    NAM_HIP_CHECK(hipMemcpy(g.d_bank_scal, bank.scal.data(), bank.scal.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
   NAM_HIP_CHECK(hipMalloc(&g.d_bank_member, (size_t)b->n_streams * sizeof(int)));
   NAM_HIP_CHECK(hipMemcpy(g.d_bank_member, b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
   g.bank_stride = bank.blob_stride;
   g.state_stride = p.state_floats;
+  return NAM_HIP_OK;
+}
+
+// BANK_LSTM: h0 / c0 of their members into `n` streams (`d_map`: which; nullptr = streams 0 .. n - 1), the rest of the state zero.
+// On the batch's stream.
+int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n)
+{
+  NAM_HIP_CHECK(launch_fill_state_bank(g.d_state, g.state_stride, d_map, n, g.d_init, g.d_bank_member, b->bank->n_init,
+                                       g.plan->state_floats, b->stream));
   return NAM_HIP_OK;
 }
 
@@ -216,7 +270,11 @@ int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, in
   int* d_moved = nullptr;
   NAM_HIP_CHECK(hipMalloc(&d_moved, moved.size() * sizeof(int)));
   NAM_HIP_CHECK(hipMemcpy(d_moved, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice));
-  const int rc = reset_streams(b, g, d_moved, (int)moved.size(), b->was_reset && b->reset_with_prewarm, -1);
+  // An LSTM's Reset clears nothing (the reference's has nothing to clear: its state is h / c, born from the weight stream), so the
+  // moved streams would keep the OLD member's h / c: they get the new member's h0 / c0 here, as a newly created batch's streams do
+  int rc = b->bank->family == BANK_LSTM ? bank_fill_initial_state(b, g, d_moved, (int)moved.size()) : NAM_HIP_OK;
+  if (rc == NAM_HIP_OK)
+    rc = reset_streams(b, g, d_moved, (int)moved.size(), b->was_reset && b->reset_with_prewarm, -1);
   const hipError_t e = hipStreamSynchronize(b->stream);
   (void)hipFree(d_moved);
   if (rc != NAM_HIP_OK)
@@ -269,11 +327,22 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
     const size_t region = p0.blob.size() - (size_t)member_base(p0, family);
     data->blob_stride = (long)((region + 3) / 4 * 4);
     data->blobs.assign((size_t)n_models * (size_t)data->blob_stride, 0.f);
-    data->scal.resize((size_t)n_models * 2);
+    if (family == BANK_LSTM)
+    {
+      data->n_init = (int)p0.lstm.init_state.size();
+      data->init.assign((size_t)n_models * (size_t)data->n_init, 0.f);
+    }
+    else
+      data->scal.resize((size_t)n_models * 2);
     for (int i = 0; i < n_models; i++)
     {
       const Plan& p = member_plan(*models[i]);
       std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + member_base(p, family), region * sizeof(float));
+      if (family == BANK_LSTM)
+      {
+        std::copy(p.lstm.init_state.begin(), p.lstm.init_state.end(), data->init.begin() + (size_t)i * (size_t)data->n_init);
+        continue;
+      }
       data->scal[2 * (size_t)i] = p.blob[(size_t)p.a1.head_scale_off];
       // nam_kq_kernel runs ReLU as LeakyReLU with slope 0 (launch_kq does the same for one model)
       data->scal[2 * (size_t)i + 1] = (family == BANK_A2 && p.a1.arr[0].act == ACT_RELU) ? 0.0f : p.a1.arr[0].act_p0;

@@ -93,13 +93,15 @@ struct nam_hip_model
 };
 
 // A model bank (nam_hip_bank_create): models that plan onto ONE instantiation of a kernel family — the interleaved-frame kernels
-// (nam_a1_q_kernel and its siblings: BANK_A1_IL) or the A2 topology's (nam_kq_kernel, nam_kt_mfma_kernel: BANK_A2) — with the
-// same blob layout, so that one launch can run them side by side, each workgroup on its stream's member. Immutable host data, self-contained (nothing of the member models is referenced after creation); a batch created
-// from it shares ownership of `data`, so the handle may be freed while batches live.
+// (nam_a1_q_kernel and its siblings: BANK_A1_IL), the A2 topology's (nam_kq_kernel, nam_kt_mfma_kernel: BANK_A2) or the small
+// LSTM cells' (nam_lstm_row_kernel, nam_lstm_wide_kernel: BANK_LSTM) — with the same blob layout, so that one launch can run
+// them side by side, each workgroup on its stream's member. Immutable host data, self-contained (nothing of the member models is
+// referenced after creation); a batch created from it shares ownership of `data`, so the handle may be freed while batches live.
 enum BankFamily : int
 {
   BANK_A1_IL = 0, // the official WaveNet topology at (padded) 16 / 8 channels
-  BANK_A2 = 1 // the A2 topology (kp_table.h)
+  BANK_A2 = 1, // the A2 topology (kp_table.h)
+  BANK_LSTM = 2 // LSTMs of one shape on the gate-row kernels (hidden <= 32, one or two layers, one or two inputs)
 };
 struct nam_hip_bank_data
 {
@@ -109,7 +111,9 @@ struct nam_hip_bank_data
   int n_members = 0;
   long blob_stride = 0; // floats per member in `blobs`: the kept part of the plan's blob (api_bank.cpp) rounded up to a multiple of four (16-byte records)
   std::vector<float> blobs; // [n_members][blob_stride]
-  std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal)
+  std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal); BANK_LSTM: empty (no kernel of it reads any)
+  int n_init = 0; // BANK_LSTM: floats of a member's initial state (LSTMPlan::init_state: h0 / c0 from ITS weight stream)
+  std::vector<float> init; // BANK_LSTM: [n_members][n_init]
 };
 struct nam_hip_bank
 {
@@ -147,6 +151,7 @@ struct WidthGroup
   // a bank batch's one group (api_bank.cpp): d_blob holds [members][bank_stride] floats, and the kernels pick a stream's member
   // through d_bank_member[stream] (indexed by STREAM, not by launch position) and its scalars from d_bank_scal[2 member].
   // No prewarm cache: a member's prewarmed state depends on its weights, so a Reset runs the silence for every stream.
+  // BANK_LSTM: no d_a1 and no d_bank_scal; d_init holds [members][n_init] floats, a stream's h0 / c0 are its member's row.
   int* d_bank_member = nullptr;
   float* d_bank_scal = nullptr;
   long bank_stride = 0;
@@ -384,6 +389,7 @@ void free_group(WidthGroup& g);
 int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out);
 // api_bank.cpp
 int upload_bank_group(nam_hip_batch* b, WidthGroup& g);
+int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n);
 int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, int member);
 // api_host_io.cpp
 bool host_windows(nam_hip_batch* b, int slots, float*& in_bar, float*& h_out_map, float*& d_out_map, bool& failed, bool prealloc = false);

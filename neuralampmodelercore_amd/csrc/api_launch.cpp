@@ -46,6 +46,8 @@ int ensure_state(nam_hip_batch* b, WidthGroup& g)
   const size_t bytes = (size_t)b->n_streams * g.state_stride * sizeof(float);
   NAM_HIP_CHECK(hipMalloc(&g.d_state, bytes));
   NAM_HIP_CHECK(hipMemsetAsync(g.d_state, 0, bytes, b->stream));
+  if (g.plan->arch == ARCH_LSTM && g.d_bank_member) // a bank: every stream its member's h0 / c0
+    return bank_fill_initial_state(b, g, nullptr, b->n_streams);
   if (g.plan->arch == ARCH_LSTM) // h0 / c0 from the weight stream, once per (sub)model instance (lstm.cpp:24-28)
     NAM_HIP_CHECK(launch_fill_state(g.d_state, g.state_stride, nullptr, b->n_streams, g.d_init,
                                     (int)g.plan->lstm.init_state.size(), g.plan->state_floats, b->stream));
@@ -98,8 +100,9 @@ constexpr size_t kKtAutoMaxStreams = 1024;
 int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
 {
   // a model bank runs its family's kernels for every launch shape (the other kernels know no banks): the interleaved-frame family,
-  // or what a one-model A2 batch runs under AUTO (select_kernel: nam_kq_kernel / nam_kt_mfma_kernel)
-  if (g.d_bank_member)
+  // or what a one-model A2 batch runs under AUTO (select_kernel: nam_kq_kernel / nam_kt_mfma_kernel). An LSTM bank's group is no
+  // WaveNet group: select_kernel answers for it (the gate-row kernels), nobody asks here.
+  if (g.d_bank_member && b->bank->family != BANK_LSTM)
     return b->bank->family == BANK_A2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL;
   const bool a1 = g.plan->a1.valid && g.d_a1;
   const bool mfma = a1 && (g.plan->a1.ws_ok || g.plan->a1.kt_ok);
@@ -456,7 +459,9 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const
     // AUTO: small cells (hidden <= 4) one gate row per lane and four streams per wavefront, cells of 5 .. 32 units two
     // gate rows per lane and one stream per wavefront, else the matrix-core kernel (16 streams per wavefront);
     // NAM_HIP_KERNEL_A1_MFMA forces the matrix-core kernel; NAM_HIP_KERNEL_GENERIC: lanes = streams
-    const bool small = b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA;
+    // A model bank (BANK_LSTM) runs the first two whatever b->kernel says: the other LSTM kernels share one wavefront's weights
+    // among their streams and know no banks (api_bank.cpp admits only cells one of the two takes)
+    const bool small = g.d_bank_member || (b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA);
     if (small && lstm_row_eligible(p.lstm))
       return FN_LSTM_ROW;
     if (small && lstm_wide_eligible(p.lstm))
@@ -634,6 +639,8 @@ static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTM
   a.n_streams = n;
   if (fn == FN_LSTM_ROW || fn == FN_LSTM_WIDE)
   {
+    a.bank_member = g.d_bank_member; // (a bank: a.blob is [members][bank_stride], whole plan blobs)
+    a.bank_stride = g.bank_stride;
     a.ps = persist_args(b);
     NAM_HIP_CHECK(fn == FN_LSTM_ROW ? launch_lstm_row(a, s) : launch_lstm_wide(a, s));
   }

@@ -572,8 +572,16 @@ __device__ __forceinline__ float gate_row(const float x0, const float x1, const 
 #undef NAM_LROW_TERM
 } // namespace lrow
 
-template <int NL, int NI, int NH, bool FAST>
-__global__ __launch_bounds__(64) void nam_lstm_row_kernel(const float* __restrict__ blob, const LSTMArgs a)
+// BANK (a model bank: LSTMArgs::bank_member): every 16-lane row is its own stream and may be its own member, so the blob base
+// is PER LANE — for the gate-row loads of the prologue only. The head behind the step loop works on one row at a time with
+// wave-uniform weights: the four rows' members wait for it in scalar registers. Nothing per lane outlives the prologue.
+// The BANK form names the scheduler's occupancy target (8 waves per SIMD: what the one-model form reaches unasked): without it
+// the per-lane loads of the prologue lower the function-wide target, and the scheduler then spreads the 64 unrolled steps over
+// 22 .. 54 more registers in another instruction order. With it the step block is allocated like the one-model form's
+// (profiles/bank_lstm/resources.txt). The one-model form keeps the default (1: no constraint) and compiles as before.
+template <int NL, int NI, int NH, bool FAST, bool BANK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BANK ? 8 : 1))) void nam_lstm_row_kernel(
+    const float* __restrict__ blob, const LSTMArgs a)
 {
   // The 64 steps of a block are unrolled (compile-time t): the input sample of step t is a DPP row broadcast out of
   // the lane / register that loaded it (lane q of the row keeps frames q, q + 16, q + 32, q + 48), so neither an LDS
@@ -587,6 +595,16 @@ __global__ __launch_bounds__(64) void nam_lstm_row_kernel(const float* __restric
   const int s0 = blockIdx.x * 4;
   const bool live = s0 + row < a.n_streams;
   const int stream = live ? (a.stream_map ? a.stream_map[s0 + row] : s0 + row) : 0;
+  // the row's member, looked up by STREAM (a dead row: stream 0's, valid memory), and the members of the four rows as scalars
+  const float* __restrict__ wblob = blob;
+  [[maybe_unused]] int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+  if constexpr (BANK)
+  {
+    const int member = a.bank_member[stream];
+    wblob = blob + (size_t)member * (size_t)a.bank_stride;
+    m0 = __builtin_amdgcn_readlane(member, 0), m1 = __builtin_amdgcn_readlane(member, 16);
+    m2 = __builtin_amdgcn_readlane(member, 32), m3 = __builtin_amdgcn_readlane(member, 48);
+  }
   constexpr int H = NH; // hidden units (compile time: no broadcast / FMA is spent on padding units)
   const int out_ch = a.out_ch;
   const bool unit = u < H;
@@ -608,8 +626,8 @@ __global__ __launch_bounds__(64) void nam_lstm_row_kernel(const float* __restric
   for (int l = 0; l < NL; l++)
   {
     const int I = l == 0 ? NI : H;
-    const float* __restrict__ W = blob + a.layer_w[l] + (size_t)(k * H + (unit ? u : 0)) * (I + H);
-    wb[l] = unit ? cB * blob[a.layer_b[l] + k * H + u] : 0.0f;
+    const float* __restrict__ W = wblob + a.layer_w[l] + (size_t)(k * H + (unit ? u : 0)) * (I + H);
+    wb[l] = unit ? cB * wblob[a.layer_b[l] + k * H + u] : 0.0f;
 #pragma unroll
     for (int e = 0; e < NW; e++)
       wi[l][e] = (unit && e < I) ? cB * W[e] : 0.0f;
@@ -719,16 +737,20 @@ __global__ __launch_bounds__(64) void nam_lstm_row_kernel(const float* __restric
         const int s = __shfl(stream, r * 16);
         if (s0 + r >= a.n_streams)
           break;
+        // the head weights of row r's member (wave-uniform: scalar loads, as in the one-model form)
+        const float* __restrict__ hblob = blob;
+        if constexpr (BANK)
+          hblob = blob + (size_t)(r == 0 ? m0 : r == 1 ? m1 : r == 2 ? m2 : m3) * (size_t)a.bank_stride;
         float hv[NH];
 #pragma unroll
         for (int j = 0; j < NH; j++)
           hv[j] = hs[(r * NH + j) * 65 + lane];
         for (int ch = 0; ch < out_ch; ch++)
         {
-          float y = blob[a.head_b + ch];
+          float y = hblob[a.head_b + ch];
 #pragma unroll
           for (int j = 0; j < NH; j++)
-            y = fmaf(blob[a.head_w + ch * H + j], hv[j], y);
+            y = fmaf(hblob[a.head_w + ch * H + j], hv[j], y);
           if (lane < nvalid)
             a.out[((size_t)s * out_ch + ch) * a.io_stride + f0 + lane] = y;
         }
@@ -809,7 +831,9 @@ __device__ __forceinline__ f2 tanh2(const f2 x)
 }
 } // namespace lwide
 
-template <int NL, int NI, int NH, bool FAST>
+// BANK (a model bank): the wavefront's one stream has one member — wave-uniform, resolved right behind the stream; the member's
+// blob base stays on the scalar unit and is read from in the prologue only (gate rows, the LDS copy of the head).
+template <int NL, int NI, int NH, bool FAST, bool BANK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void nam_lstm_wide_kernel(
   const float* __restrict__ blob, const LSTMArgs a)
 {
@@ -822,6 +846,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   const int H = a.hidden; // <= NH (NH: the next multiple of 4; padding units have zero rows and stay at h = c = 0)
   const bool unit = u < H;
   const int stream = a.stream_map ? a.stream_map[blockIdx.x] : (int)blockIdx.x;
+  const float* __restrict__ wblob = blob;
+  if constexpr (BANK)
+    wblob = blob + (size_t)uni(a.bank_member[uni(stream)]) * (size_t)a.bank_stride; // looked up by STREAM
   const int out_ch = a.out_ch;
   float* const hist = lds; // [64 steps][HP]: the top layer's h
   float* const hw = lds + kBlock * HP; // head weights [out_ch][NH] (zero padded), then the head bias [out_ch]
@@ -836,9 +863,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   for (int l = 0; l < NL; l++)
   {
     const int I = l == 0 ? NI : H;
-    const float* __restrict__ W0 = blob + a.layer_w[l] + (size_t)(g0 * H + (unit ? u : 0)) * (I + H);
-    const float* __restrict__ W1 = blob + a.layer_w[l] + (size_t)(g1 * H + (unit ? u : 0)) * (I + H);
-    wb[l] = unit ? f2{s0 * blob[a.layer_b[l] + g0 * H + u], 0.5f * blob[a.layer_b[l] + g1 * H + u]} : f2{0.0f, 0.0f};
+    const float* __restrict__ W0 = wblob + a.layer_w[l] + (size_t)(g0 * H + (unit ? u : 0)) * (I + H);
+    const float* __restrict__ W1 = wblob + a.layer_w[l] + (size_t)(g1 * H + (unit ? u : 0)) * (I + H);
+    wb[l] = unit ? f2{s0 * wblob[a.layer_b[l] + g0 * H + u], 0.5f * wblob[a.layer_b[l] + g1 * H + u]} : f2{0.0f, 0.0f};
 #pragma unroll
     for (int e = 0; e < NIN; e++)
       wi[l][e] = (unit && e < I) ? f2{s0 * W0[e], 0.5f * W1[e]} : f2{0.0f, 0.0f};
@@ -848,9 +875,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   }
   const float a0 = odd ? 1.0f : 0.5f, b0 = odd ? 0.0f : 0.5f; // row 0's activation = a0 T(z) + b0
   for (int i = lane; i < out_ch * NH; i += kBlock)
-    hw[i] = (i % NH) < H ? blob[a.head_w + (i / NH) * H + (i % NH)] : 0.0f;
+    hw[i] = (i % NH) < H ? wblob[a.head_w + (i / NH) * H + (i % NH)] : 0.0f;
   if (lane < out_ch)
-    hw[out_ch * NH + lane] = blob[a.head_b + lane];
+    hw[out_ch * NH + lane] = wblob[a.head_b + lane];
 
   // persistent session (persist_wave.h): blocks come from commands, not from a frame count
   const bool pers = a.ps.ring != nullptr;
@@ -999,6 +1026,17 @@ __global__ void nam_fill_state_kernel(float* state, long state_stride, const int
     st[i] = (init && i < n_init) ? init[i] : 0.0f;
 }
 
+// the bank form: `init` = [member][n_init] (every member's h0 / c0 come from ITS weight stream), the stream's row by member_of[stream]
+__global__ void nam_fill_state_bank_kernel(float* state, long state_stride, const int* stream_map, int n_streams,
+                                           const float* init, const int* member_of, int n_init, int state_floats)
+{
+  const int stream = stream_map ? stream_map[blockIdx.x] : (int)blockIdx.x;
+  float* st = state + (size_t)stream * state_stride;
+  const float* mine = init + (size_t)member_of[stream] * (size_t)n_init;
+  for (int i = threadIdx.x; i < state_floats; i += blockDim.x)
+    st[i] = i < n_init ? mine[i] : 0.0f;
+}
+
 int lstm_lds_bytes(const LSTMArgs& a)
 {
   const long floats = (long)(a.in_ch + a.out_ch) * kBlock * 65 + 2l * a.n_layers * a.hidden * kBlock + 4l * a.hidden * kBlock;
@@ -1066,11 +1104,15 @@ hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
     return hipErrorInvalidValue;
   const int n_blocks = (a.n_streams + 3) / 4;
   const int lds_bytes = (4 * a.hidden * 65 + 128) * (int)sizeof(float); // h history of the block + the dump slots
-#define NAM_LSTM_ROW_H(NL, NI, NH) \
-  return a.fast ? launch_instance<&nam_lstm_row_kernel<NL, NI, NH, true>, false, kLdsDefault>( \
+#define NAM_LSTM_ROW_B(NL, NI, NH, BANK) \
+  return a.fast ? launch_instance<&nam_lstm_row_kernel<NL, NI, NH, true, BANK>, false, kLdsDefault>( \
                     dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a) \
-                : launch_instance<&nam_lstm_row_kernel<NL, NI, NH, false>, false, kLdsDefault>( \
+                : launch_instance<&nam_lstm_row_kernel<NL, NI, NH, false, BANK>, false, kLdsDefault>( \
                     dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a)
+#define NAM_LSTM_ROW_H(NL, NI, NH) \
+  if (a.bank_member) \
+    NAM_LSTM_ROW_B(NL, NI, NH, true); \
+  NAM_LSTM_ROW_B(NL, NI, NH, false)
 #define NAM_LSTM_ROW(NL, NI) \
   switch (a.hidden) \
   { \
@@ -1088,6 +1130,7 @@ hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
   }
 #undef NAM_LSTM_ROW
 #undef NAM_LSTM_ROW_H
+#undef NAM_LSTM_ROW_B
 }
 
 hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)
@@ -1096,11 +1139,15 @@ hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)
     return hipErrorInvalidValue;
   const int nh = (a.hidden + 3) & ~3;
   const int lds_bytes = (kBlock * (nh + 4) + a.out_ch * nh + a.out_ch) * (int)sizeof(float);
-#define NAM_LSTM_WIDE_H(NL, NI, NH) \
-  return a.fast ? launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, true>, false, kLdsDefault>( \
+#define NAM_LSTM_WIDE_B(NL, NI, NH, BANK) \
+  return a.fast ? launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, true, BANK>, false, kLdsDefault>( \
                     dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a) \
-                : launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, false>, false, kLdsDefault>( \
+                : launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, false, BANK>, false, kLdsDefault>( \
                     dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a)
+#define NAM_LSTM_WIDE_H(NL, NI, NH) \
+  if (a.bank_member) \
+    NAM_LSTM_WIDE_B(NL, NI, NH, true); \
+  NAM_LSTM_WIDE_B(NL, NI, NH, false)
 #define NAM_LSTM_WIDE(NL, NI) \
   switch (nh) \
   { \
@@ -1121,6 +1168,7 @@ hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)
   }
 #undef NAM_LSTM_WIDE
 #undef NAM_LSTM_WIDE_H
+#undef NAM_LSTM_WIDE_B
 }
 
 hipError_t launch_fill_state(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
@@ -1128,6 +1176,16 @@ hipError_t launch_fill_state(float* state, long state_stride, const int* stream_
 {
   hipLaunchKernelGGL(nam_fill_state_kernel, dim3(n_streams), dim3(256), 0, stream, state, state_stride, stream_map,
                      n_streams, init, n_init, state_floats);
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_state_bank(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
+                                  const int* member_of, int n_init, int state_floats, hipStream_t stream)
+{
+  if (!init || !member_of)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(nam_fill_state_bank_kernel, dim3(n_streams), dim3(256), 0, stream, state, state_stride, stream_map,
+                     n_streams, init, member_of, n_init, state_floats);
   return hipGetLastError();
 }
 

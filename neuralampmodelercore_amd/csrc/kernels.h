@@ -206,6 +206,12 @@ struct LSTMArgs
   int mf_layer_bias[16];
   PersistArgs ps; // nam_lstm_row_kernel / nam_lstm_wide_kernel
   float* scratch = nullptr; // nam_lstm_kernel<true>: global-memory h / c / gate columns (lstm_scratch_floats)
+  // model bank (nam_hip_batch_create_bank; the BANK instantiations of nam_lstm_row_kernel / nam_lstm_wide_kernel; nullptr = one
+  // model): stream s runs member m = bank_member[s] of `blob` = [members][bank_stride] floats (whole plan blobs, a multiple of
+  // four). The offsets above are the same for every member (api_bank.cpp compares the plans). Read in the prologue only. Behind
+  // every other field: the one-model instantiations find theirs where they were.
+  const int* bank_member = nullptr;
+  long bank_stride = 0;
 };
 // the model's part of an LSTM launch's arguments; the caller adds the streams and the audio
 inline LSTMArgs lstm_args(const LSTMPlan& L)
@@ -319,5 +325,8 @@ int lstm_lds_bytes(const LSTMArgs& a);
 long lstm_scratch_floats(const LSTMArgs& a); // > 0: the lanes = streams kernel keeps its columns in global scratch
 hipError_t launch_fill_state(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
                              int n_init, int state_floats, hipStream_t stream);
+// the bank form: `init` = [member][n_init], stream s takes row member_of[s] (indexed by STREAM, like LSTMArgs::bank_member)
+hipError_t launch_fill_state_bank(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
+                                  const int* member_of, int n_init, int state_floats, hipStream_t stream);
 
 } // namespace namhip

@@ -49,7 +49,7 @@ int nam_hip_version_support(const char* nam_file_version)
 
 const char* nam_hip_version(void)
 {
-  return "nam_hip 0.2.3 gfx950"; // 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
+  return "nam_hip 0.2.4 gfx950"; // 0.2.4: nam_hip_bank_create accepts the LSTM family (cells nam_lstm_row_kernel / nam_lstm_wide_kernel take); 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
 }
 
 int nam_hip_model_load(const char* nam_path, int fast_tanh, nam_hip_model** out_model)
@@ -854,7 +854,10 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
   {
     // a bank batch runs its family's kernels only (api_bank.cpp)
     const bool a2 = batch->bank->family == BANK_A2;
-    if (kernel != NAM_HIP_KERNEL_AUTO && kernel != (a2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL))
+    if (batch->bank->family == BANK_LSTM && kernel != NAM_HIP_KERNEL_AUTO)
+      return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_batch_set_kernel: an LSTM bank batch runs nam_lstm_row_kernel / nam_lstm_wide_kernel only "
+                                           "(NAM_HIP_KERNEL_AUTO); the matrix-core and lanes kernels know no banks");
+    if (batch->bank->family != BANK_LSTM && kernel != NAM_HIP_KERNEL_AUTO && kernel != (a2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL))
       return fail(NAM_HIP_ERR_UNSUPPORTED,
                   a2 ? "nam_hip_batch_set_kernel: an A2 bank batch runs nam_kq_kernel / nam_kt_mfma_kernel only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_MFMA)"
                      : "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)");

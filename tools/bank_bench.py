@@ -11,6 +11,13 @@ default: enough to extrapolate per-capture cost, and it keeps memory and session
 Every figure is the median of --runs repetitions (each a fresh timing of --regions regions); one JSON line per case.
 
     python tools/bank_bench.py [--family a1|a2] [--streams 256] [--runs 7] [--singles 16]
+
+--family lstm: the LSTM family's two kernels in their bench shapes — one layer of 3 units at 1,024 streams (config 3's shape:
+nam_lstm_row_kernel, four streams per wavefront) and one layer of 24 units at 256 streams (nam_lstm_wide_kernel, one stream
+per wavefront); members from tests/bank_models_lstm.py, (a) is member 0 as a one-model batch. The three cases are INTERLEAVED:
+run r times (a), (b), (c) one after the other before run r + 1 starts, so that a drift of the box lands on all three.
+
+    python tools/bank_bench.py --family lstm [--runs 7] [--singles 16]
 """
 import argparse
 import json
@@ -56,6 +63,60 @@ def time_session(batch, n_streams, region, regions, runs):
     return statistics.median(per_step), min(per_step), max(per_step)
 
 
+def time_sessions_interleaved(batches, n_streams, in_ch, region, regions, runs):
+    """time_session for several batches of one shape at once: {name: (median, min, max)}, run r of every batch before run r + 1"""
+    import torch
+    T = BLOCK * region
+    xd = (0.2 * torch.randn(n_streams, in_ch, T, device="cuda")).contiguous()
+    yd = torch.zeros(n_streams, 1, T, device="cuda")
+
+    def one_region(batch):
+        for k in range(region):
+            batch.process_device(xd.data_ptr() + k * BLOCK * 4, yd.data_ptr() + k * BLOCK * 4, BLOCK, T)
+        batch.flush()
+        torch.cuda.synchronize()
+
+    for batch in batches.values():
+        assert batch.set_persistent(True)
+        batch.Reset(prewarm=True)
+        for _ in range(3):
+            one_region(batch)
+    per_step = {name: [] for name in batches}
+    for _ in range(runs):
+        for name, batch in batches.items():
+            t0 = time.perf_counter()
+            for _ in range(regions):
+                one_region(batch)
+            per_step[name].append((time.perf_counter() - t0) * 1e6 / (regions * region))
+    assert bool(torch.isfinite(yd).all())
+    return {name: (statistics.median(v), min(v), max(v)) for name, v in per_step.items()}
+
+
+def main_lstm(args, nam):
+    from bank_models_lstm import write_lstm
+    for shape, hidden, n in (("row_1x3", 3, 1024), ("wide_1x24", 24, 256)):
+        with tempfile.TemporaryDirectory() as d:
+            members = []
+            for i in range(n):
+                p = os.path.join(d, f"m{i}.nam")
+                write_lstm(p, 2000 + i, num_layers=1, input_size=1, hidden=hidden, out_channels=1)
+                members.append(nam.get_dsp(p, fast_tanh=True))
+        for region, regions in ((20, 50), (500, 4)):
+            batches = {
+                "a_one_model": members[0].batch(n, BLOCK),
+                "b_bank_all_member_0": nam.ModelBank(members[:8]).batch(n, BLOCK),
+                "c_bank_distinct_members": nam.ModelBank(members).batch(n, BLOCK, stream_model=list(range(n))),
+            }
+            res = time_sessions_interleaved(batches, n, 1, region, regions, args.runs)
+            for name, (med, lo, hi) in res.items():
+                print(json.dumps(dict(case=name, shape=shape, streams=n, region_commands=region, us_per_step_median=round(med, 3),
+                                      us_min=round(lo, 3), us_max=round(hi, 3), xrt=round(xrt(n, med)), kernel=batches[name].kernel_name(),
+                                      runs=args.runs, interleaved=True)), flush=True)
+            for b in batches.values():
+                b.close()
+        singles_in_turn(args, members, shape)
+
+
 def xrt(n_streams, us_per_step):
     return n_streams * BLOCK / 48000.0 / (us_per_step * 1e-6)
 
@@ -65,10 +126,13 @@ def main():
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--singles", type=int, default=16)
-    ap.add_argument("--family", choices=["a1", "a2"], default="a1",
-                    help="a1: the official topology (nam_a1_q_kernel); a2: the A2 topology (nam_kq_kernel)")
+    ap.add_argument("--family", choices=["a1", "a2", "lstm"], default="a1",
+                    help="a1: the official topology (nam_a1_q_kernel); a2: the A2 topology (nam_kq_kernel); "
+                         "lstm: nam_lstm_row_kernel / nam_lstm_wide_kernel in their own shapes (--streams is not read)")
     args = ap.parse_args()
     import neuralampmodelercore_amd as nam
+    if args.family == "lstm":
+        return main_lstm(args, nam)
     if args.family == "a2":
         from bank_models_a2 import write_a2 as write_standard
     else:
@@ -95,7 +159,11 @@ def main():
             b.close()
             print(json.dumps(dict(case=name, streams=n, region_commands=region, us_per_step_median=round(med, 3), us_min=round(lo, 3),
                                   us_max=round(hi, 3), xrt=round(xrt(n, med)), kernel=kernel, runs=args.runs)), flush=True)
-    # the case a bank replaces: one batch per capture, blocking 64-frame calls in turn
+    singles_in_turn(args, members)
+
+
+def singles_in_turn(args, members, shape=None):
+    """the case a bank replaces: one batch per capture, blocking 64-frame calls in turn"""
     k = args.singles
     batches = []
     for i in range(k):
@@ -117,7 +185,7 @@ def main():
     med = statistics.median(per_round)
     print(json.dumps(dict(case="d_one_stream_batches_in_turn", captures=k, us_per_round_median=round(med, 2), us_per_call=round(med / k, 2),
                           us_min=round(min(per_round), 2), us_max=round(max(per_round), 2), xrt=round(xrt(k, med)),
-                          kernel=batches[0].kernel_name(), runs=args.runs,
+                          kernel=batches[0].kernel_name(), runs=args.runs, **(dict(shape=shape) if shape else {}),
                           note="per-capture cost is serial on the host: N captures cost N x us_per_call per 64 frames")), flush=True)
     for b in batches:
         b.close()
