@@ -16,6 +16,9 @@
 //    no scalars; instead every member's initial state (h0 / c0 are part of an LSTM's weight stream: LSTMPlan::init_state).
 // Per member besides the blob, WaveNet families: the two scalars the kernels take by value (head_scale, act_p0 — on the A2
 // topology the LeakyReLU slope, 0 for ReLU as in launch_kq).
+//
+// A family's rules are its row of kBankFamily below (api_internal.h: BankFamilyRules); the other files ask that row and name no
+// family. Here a family is named by member_refusal (which family a model is of), by its comparison function and by its row.
 #include "api_internal.h"
 
 namespace namhip
@@ -24,13 +27,6 @@ namespace api
 {
 namespace
 {
-const char* family_name(int f)
-{
-  if (f == BANK_LSTM)
-    return "LSTM (nam_lstm_row_kernel / nam_lstm_wide_kernel)";
-  return f == BANK_A2 ? "A2 (nam_kq_kernel)" : "A1_IL (nam_a1_q_kernel)";
-}
-
 // What a model stands for in a bank: its full-size plan and that plan's spec (a SlimmableContainer: its largest submodel's, the
 // one a batch runs when no size has been set).
 const Plan& member_plan(const nam_hip_model& m)
@@ -41,12 +37,6 @@ std::shared_ptr<ModelSpec> member_spec(const nam_hip_model& m)
 {
   return m.spec->arch == ARCH_CONTAINER ? m.spec->submodels[(size_t)m.full_width] : m.spec;
 }
-// first float of the member's blob the bank keeps (see the head of this file)
-int member_base(const Plan& p, int family)
-{
-  return family == BANK_A1_IL ? p.a1.ws_tiles_off : 0;
-}
-
 // the A2 family: what makes a one-model batch session-eligible on nam_kq_kernel (kq_runs), nam_kt_mfma_kernel for a lone buffer
 bool a2_member(const A1Plan& a)
 {
@@ -101,43 +91,22 @@ std::string member_refusal(const nam_hip_model& m, int* family)
   return "";
 }
 
-// The first field in which member `m` differs from member 0, "" when the two run as one launch. Both are of `family`.
-std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, int family)
+// The comparisons below: member `m` against member 0, field by field. The recorder keeps the FIRST field that differs (what a
+// refusal names); "" = the two run as one launch.
+struct FirstDifference
 {
-  const Plan& q = member_plan(m0);
-  const Plan& p = member_plan(m);
-  const A1Plan& a = p.a1;
-  const A1Plan& b = q.a1;
-  std::string out;
-  auto cmp = [&](const char* field, long long x, long long y) {
-    if (out.empty() && x != y)
-      out = std::string(field) + " (" + std::to_string(x) + " vs " + std::to_string(y) + ")";
-  };
-  if (family == BANK_LSTM)
+  std::string text;
+  void operator()(const char* field, long long x, long long y)
   {
-    // what nam_lstm_row_kernel / nam_lstm_wide_kernel are instantiated on and what their arguments take from the plan (member 0's)
-    const LSTMPlan &x = p.lstm, &y = q.lstm;
-    cmp("fast_tanh", x.fast ? 1 : 0, y.fast ? 1 : 0);
-    cmp("lstm.n_layers", x.n_layers, y.n_layers);
-    cmp("lstm.input_size", x.input_size, y.input_size);
-    cmp("lstm.hidden", x.hidden, y.hidden);
-    cmp("lstm.in_ch", x.in_ch, y.in_ch);
-    cmp("lstm.out_ch", x.out_ch, y.out_ch);
-    cmp("lstm.head_w", x.head_w, y.head_w);
-    cmp("lstm.head_b", x.head_b, y.head_b);
-    for (int l = 0; l < x.n_layers && l < 16; l++)
-    {
-      cmp("lstm.layer_w", x.layer_w[l], y.layer_w[l]);
-      cmp("lstm.layer_b", x.layer_b[l], y.layer_b[l]);
-    }
-    cmp("blob floats", (long long)p.blob.size(), (long long)q.blob.size());
-    cmp("lstm.init_state floats", (long long)x.init_state.size(), (long long)y.init_state.size());
-    cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples); // (half a second at the file's sample rate)
-    cmp("state_floats", p.state_floats, q.state_floats);
-    return out;
+    if (text.empty() && x != y)
+      text = std::string(field) + " (" + std::to_string(x) + " vs " + std::to_string(y) + ")";
   }
-  if (family == BANK_A1_IL)
-    cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
+};
+
+// both WaveNet families: channels, prewarm, state, the arrays and their rings
+void wavenet_geometry(FirstDifference& cmp, const Plan& p, const Plan& q)
+{
+  const A1Plan &a = p.a1, &b = q.a1;
   cmp("in_channels", p.in_channels, q.in_channels);
   cmp("out_channels", p.out_channels, q.out_channels);
   cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples);
@@ -162,32 +131,14 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, in
       cmp("a1.arr.ring_id", x.ring_id[l], y.ring_id[l]);
     }
   }
-  if (family == BANK_A2)
-  {
-    // what nam_kq_kernel and nam_kt_mfma_kernel take from the plan (the device A1Plan is member 0's), absolute blob offsets
-    cmp("blob floats", (long long)p.blob.size(), (long long)q.blob.size());
-    cmp("kt_chunks", a.kt_chunks, b.kt_chunks);
-    cmp("kt_nk", a.kt_nk, b.kt_nk);
-    for (int c = 0; c < a.kt_chunks && c < kKtChunkMax; c++)
-    {
-      const KtDesc &x = a.kt_desc[c], &y = b.kt_desc[c];
-      cmp("kt_desc.flags", x.flags, y.flags);
-      cmp("kt_desc.ntaps", x.ntaps, y.ntaps);
-      cmp("kt_desc.tile_off", x.tile_off, y.tile_off);
-      cmp("kt_desc.w1_off", x.w1_off, y.w1_off);
-      cmp("kt_desc.consts_off", x.consts_off, y.consts_off);
-      cmp("kt_desc.ring_b", x.ring_b, y.ring_b);
-      cmp("kt_desc.R", x.R, y.R);
-      cmp("kt_desc.ring_id", x.ring_id, y.ring_id);
-      for (int i = 0; i < kKtTaps; i++)
-        cmp("kt_desc.L", x.L[i], y.L[i]);
-    }
-    cmp("kt_rech_off", a.kt_rech_off, b.kt_rech_off);
-    cmp("kt_lds_src_off", a.kt_lds_src_off, b.kt_lds_src_off);
-    cmp("kt_lds_floats", a.kt_lds_floats, b.kt_lds_floats);
-    cmp("kq_w_off", a.kq_w_off, b.kq_w_off);
-    return out;
-  }
+}
+
+void a1_il_difference(FirstDifference& cmp, const nam_hip_model& m0, const nam_hip_model& m)
+{
+  const Plan &p = member_plan(m), &q = member_plan(m0);
+  const A1Plan &a = p.a1, &b = q.a1;
+  cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
+  wavenet_geometry(cmp, p, q);
   cmp("a1.p2_c0", a.p2_c0, b.p2_c0);
   cmp("a1.p2_c1", a.p2_c1, b.p2_c1);
   // the launch arguments, as offsets from the kernel region's start (see the head of this file)
@@ -196,19 +147,100 @@ std::string first_difference(const nam_hip_model& m0, const nam_hip_model& m, in
   cmp("xt_off (ws_xt_off - ws_tiles_off)", a.ws_xt_off - a.ws_tiles_off, b.ws_xt_off - b.ws_tiles_off);
   cmp("n_xt (ws_n_xt)", a.ws_n_xt, b.ws_n_xt);
   cmp("q_w_off - ws_tiles_off", a.q_w_off - a.ws_tiles_off, b.q_w_off - b.ws_tiles_off);
-  return out;
 }
+
+void a2_difference(FirstDifference& cmp, const nam_hip_model& m0, const nam_hip_model& m)
+{
+  const Plan &p = member_plan(m), &q = member_plan(m0);
+  const A1Plan &a = p.a1, &b = q.a1;
+  wavenet_geometry(cmp, p, q);
+  // what nam_kq_kernel and nam_kt_mfma_kernel take from the plan (the device A1Plan is member 0's), absolute blob offsets
+  cmp("blob floats", (long long)p.blob.size(), (long long)q.blob.size());
+  cmp("kt_chunks", a.kt_chunks, b.kt_chunks);
+  cmp("kt_nk", a.kt_nk, b.kt_nk);
+  for (int c = 0; c < a.kt_chunks && c < kKtChunkMax; c++)
+  {
+    const KtDesc &x = a.kt_desc[c], &y = b.kt_desc[c];
+    cmp("kt_desc.flags", x.flags, y.flags);
+    cmp("kt_desc.ntaps", x.ntaps, y.ntaps);
+    cmp("kt_desc.tile_off", x.tile_off, y.tile_off);
+    cmp("kt_desc.w1_off", x.w1_off, y.w1_off);
+    cmp("kt_desc.consts_off", x.consts_off, y.consts_off);
+    cmp("kt_desc.ring_b", x.ring_b, y.ring_b);
+    cmp("kt_desc.R", x.R, y.R);
+    cmp("kt_desc.ring_id", x.ring_id, y.ring_id);
+    for (int i = 0; i < kKtTaps; i++)
+      cmp("kt_desc.L", x.L[i], y.L[i]);
+  }
+  cmp("kt_rech_off", a.kt_rech_off, b.kt_rech_off);
+  cmp("kt_lds_src_off", a.kt_lds_src_off, b.kt_lds_src_off);
+  cmp("kt_lds_floats", a.kt_lds_floats, b.kt_lds_floats);
+  cmp("kq_w_off", a.kq_w_off, b.kq_w_off);
+}
+
+void lstm_difference(FirstDifference& cmp, const nam_hip_model& m0, const nam_hip_model& m)
+{
+  const Plan &p = member_plan(m), &q = member_plan(m0);
+  // what nam_lstm_row_kernel / nam_lstm_wide_kernel are instantiated on and what their arguments take from the plan (member 0's)
+  const LSTMPlan &x = p.lstm, &y = q.lstm;
+  cmp("fast_tanh", x.fast ? 1 : 0, y.fast ? 1 : 0);
+  cmp("lstm.n_layers", x.n_layers, y.n_layers);
+  cmp("lstm.input_size", x.input_size, y.input_size);
+  cmp("lstm.hidden", x.hidden, y.hidden);
+  cmp("lstm.in_ch", x.in_ch, y.in_ch);
+  cmp("lstm.out_ch", x.out_ch, y.out_ch);
+  cmp("lstm.head_w", x.head_w, y.head_w);
+  cmp("lstm.head_b", x.head_b, y.head_b);
+  for (int l = 0; l < x.n_layers && l < 16; l++)
+  {
+    cmp("lstm.layer_w", x.layer_w[l], y.layer_w[l]);
+    cmp("lstm.layer_b", x.layer_b[l], y.layer_b[l]);
+  }
+  cmp("blob floats", (long long)p.blob.size(), (long long)q.blob.size());
+  cmp("lstm.init_state floats", (long long)x.init_state.size(), (long long)y.init_state.size());
+  cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples); // (half a second at the file's sample rate)
+  cmp("state_floats", p.state_floats, q.state_floats);
+}
+
+// ... by family, in kBankFamily's order
+void (*const kFirstDifference[BANK_FAMILY_COUNT])(FirstDifference&, const nam_hip_model& m0, const nam_hip_model& m) = {
+  a1_il_difference, a2_difference, lstm_difference};
 } // namespace
 
+// The families' rules, indexed by BankFamily (api_internal.h: BankFamilyRules); the texts are what a caller reads in nam_hip_last_error
+const BankFamilyRules kBankFamily[BANK_FAMILY_COUNT] = {
+  {"A1_IL (nam_a1_q_kernel)", NAM_HIP_KERNEL_A1_IL,
+   "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)",
+   1u << FN_A1_P2 | 1u << FN_A1_P4 | 1u << FN_A1_Q,
+   "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank",
+   /*kernel_region_only*/ true, /*init_states*/ false},
+  {"A2 (nam_kq_kernel)", NAM_HIP_KERNEL_A1_MFMA,
+   "nam_hip_batch_set_kernel: an A2 bank batch runs nam_kq_kernel / nam_kt_mfma_kernel only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_MFMA)",
+   1u << FN_KQ | 1u << FN_KT_MFMA,
+   "model bank (A2 family): only nam_kq_kernel and nam_kt_mfma_kernel run it; a launch beyond 2^28 frames would take "
+   "nam_a1_kernel, which knows no banks: split the launch",
+   /*kernel_region_only*/ false, /*init_states*/ false},
+  // (no WaveNet group: pick_kernel is not asked and launch_a1_family not reached; select_kernel answers one of the two functions)
+  {"LSTM (nam_lstm_row_kernel / nam_lstm_wide_kernel)", NAM_HIP_KERNEL_AUTO,
+   "nam_hip_batch_set_kernel: an LSTM bank batch runs nam_lstm_row_kernel / nam_lstm_wide_kernel only "
+   "(NAM_HIP_KERNEL_AUTO); the matrix-core and lanes kernels know no banks",
+   1u << FN_LSTM_ROW | 1u << FN_LSTM_WIDE, "", /*kernel_region_only*/ false, /*init_states*/ true},
+};
+
+int bank_blob_base(const Plan& p, int family)
+{
+  return kBankFamily[family].kernel_region_only ? p.a1.ws_tiles_off : 0;
+}
+
 // The device image of a bank batch's one group (instead of upload_group): every member's kernel region in ONE allocation, the
-// per-member scalars (BANK_LSTM: the per-member initial states instead), the per-stream member index.
+// per-member scalars (or the per-member initial states: BankFamilyRules::init_states), the per-stream member index.
 int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
 {
   const nam_hip_bank_data& bank = *b->bank;
   const Plan& p = *g.plan;
   NAM_HIP_CHECK(hipMalloc(&g.d_blob, bank.blobs.size() * sizeof(float)));
   NAM_HIP_CHECK(hipMemcpy(g.d_blob, bank.blobs.data(), bank.blobs.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (bank.family == BANK_LSTM)
+  if (kBankFamily[bank.family].init_states)
   {
     NAM_HIP_CHECK(hipMalloc(&g.d_init, std::max<size_t>(bank.init.size(), 1) * sizeof(float)));
     NAM_HIP_CHECK(hipMemcpy(g.d_init, bank.init.data(), bank.init.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -227,7 +259,7 @@ int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
   return NAM_HIP_OK;
 }
 
-// BANK_LSTM: h0 / c0 of their members into `n` streams (`d_map`: which; nullptr = streams 0 .. n - 1), the rest of the state zero.
+// (init_states families) h0 / c0 of their members into `n` streams (`d_map`: which; nullptr = streams 0 .. n - 1), the rest of the state zero.
 // On the batch's stream.
 int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n)
 {
@@ -272,7 +304,7 @@ int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, in
   NAM_HIP_CHECK(hipMemcpy(d_moved, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice));
   // An LSTM's Reset clears nothing (the reference's has nothing to clear: its state is h / c, born from the weight stream), so the
   // moved streams would keep the OLD member's h / c: they get the new member's h0 / c0 here, as a newly created batch's streams do
-  int rc = b->bank->family == BANK_LSTM ? bank_fill_initial_state(b, g, d_moved, (int)moved.size()) : NAM_HIP_OK;
+  int rc = kBankFamily[b->bank->family].init_states ? bank_fill_initial_state(b, g, d_moved, (int)moved.size()) : NAM_HIP_OK;
   if (rc == NAM_HIP_OK)
     rc = reset_streams(b, g, d_moved, (int)moved.size(), b->was_reset && b->reset_with_prewarm, -1);
   const hipError_t e = hipStreamSynchronize(b->stream);
@@ -306,14 +338,14 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
         return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_bank_create: member " + std::to_string(i) + " is " + why);
       if (i == 0)
         family = fam;
-      std::string diff;
+      FirstDifference diff;
       if (fam != family)
-        diff = std::string("family (") + family_name(fam) + " vs " + family_name(family) + "; a bank is of one family)";
+        diff.text = std::string("family (") + kBankFamily[fam].name + " vs " + kBankFamily[family].name + "; a bank is of one family)";
       else if (i)
-        diff = first_difference(*models[0], *models[i], family);
-      if (!diff.empty())
+        kFirstDifference[family](diff, *models[0], *models[i]);
+      if (!diff.text.empty())
         return fail(NAM_HIP_ERR_UNSUPPORTED,
-                    "nam_hip_bank_create: member " + std::to_string(i) + " differs from member 0 in " + diff);
+                    "nam_hip_bank_create: member " + std::to_string(i) + " differs from member 0 in " + diff.text);
     }
     auto data = std::make_shared<nam_hip_bank_data>();
     const nam_hip_model& m0 = *models[0];
@@ -324,10 +356,11 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
     data->proto.width_channels.push_back({});
     data->proto.full_width = 0;
     data->n_members = n_models;
-    const size_t region = p0.blob.size() - (size_t)member_base(p0, family);
+    const bool init_states = kBankFamily[family].init_states;
+    const size_t region = p0.blob.size() - (size_t)bank_blob_base(p0, family);
     data->blob_stride = (long)((region + 3) / 4 * 4);
     data->blobs.assign((size_t)n_models * (size_t)data->blob_stride, 0.f);
-    if (family == BANK_LSTM)
+    if (init_states)
     {
       data->n_init = (int)p0.lstm.init_state.size();
       data->init.assign((size_t)n_models * (size_t)data->n_init, 0.f);
@@ -337,8 +370,8 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
     for (int i = 0; i < n_models; i++)
     {
       const Plan& p = member_plan(*models[i]);
-      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + member_base(p, family), region * sizeof(float));
-      if (family == BANK_LSTM)
+      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + bank_blob_base(p, family), region * sizeof(float));
+      if (init_states)
       {
         std::copy(p.lstm.init_state.begin(), p.lstm.init_state.end(), data->init.begin() + (size_t)i * (size_t)data->n_init);
         continue;

@@ -4,7 +4,8 @@
 //   api_launch.cpp    model -> plans -> device blobs; which kernel a launch runs and its arguments; Reset / prewarm
 //   api_session.cpp   persistent block mode: the resident launch, its command ring, completion, the watchdog
 //   api_host_io.cpp   host buffers: the windows both sides can reach, blocking calls through a session, tickets
-//   api_bank.cpp      model banks: which models may share a batch, the bank's device image, per-stream member binding
+//   api_bank.cpp      model banks: the families' rules (kBankFamily), which models may share a batch, the bank's device image,
+//                     per-stream member binding
 // No exception leaves these files (guarded); errors are codes + nam_hip_last_error.
 #pragma once
 #include "../../include/nam_hip.h"
@@ -101,7 +102,8 @@ enum BankFamily : int
 {
   BANK_A1_IL = 0, // the official WaveNet topology at (padded) 16 / 8 channels
   BANK_A2 = 1, // the A2 topology (kp_table.h)
-  BANK_LSTM = 2 // LSTMs of one shape on the gate-row kernels (hidden <= 32, one or two layers, one or two inputs)
+  BANK_LSTM = 2, // LSTMs of one shape on the gate-row kernels (hidden <= 32, one or two layers, one or two inputs)
+  BANK_FAMILY_COUNT
 };
 struct nam_hip_bank_data
 {
@@ -111,9 +113,10 @@ struct nam_hip_bank_data
   int n_members = 0;
   long blob_stride = 0; // floats per member in `blobs`: the kept part of the plan's blob (api_bank.cpp) rounded up to a multiple of four (16-byte records)
   std::vector<float> blobs; // [n_members][blob_stride]
-  std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal); BANK_LSTM: empty (no kernel of it reads any)
-  int n_init = 0; // BANK_LSTM: floats of a member's initial state (LSTMPlan::init_state: h0 / c0 from ITS weight stream)
-  std::vector<float> init; // BANK_LSTM: [n_members][n_init]
+  // per member besides the blob, one of the two (BankFamilyRules::init_states says which; the other stays empty):
+  std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal)
+  int n_init = 0; // floats of a member's initial state (LSTMPlan::init_state: h0 / c0 from ITS weight stream)
+  std::vector<float> init; // [n_members][n_init]
 };
 struct nam_hip_bank
 {
@@ -151,7 +154,7 @@ struct WidthGroup
   // a bank batch's one group (api_bank.cpp): d_blob holds [members][bank_stride] floats, and the kernels pick a stream's member
   // through d_bank_member[stream] (indexed by STREAM, not by launch position) and its scalars from d_bank_scal[2 member].
   // No prewarm cache: a member's prewarmed state depends on its weights, so a Reset runs the silence for every stream.
-  // BANK_LSTM: no d_a1 and no d_bank_scal; d_init holds [members][n_init] floats, a stream's h0 / c0 are its member's row.
+  // BankFamilyRules::init_states: no d_a1 and no d_bank_scal; d_init holds [members][n_init] floats, a stream's h0 / c0 its member's row.
   int* d_bank_member = nullptr;
   float* d_bank_scal = nullptr;
   long bank_stride = 0;
@@ -346,6 +349,29 @@ enum KernelFn : int
   FN_LSTM, FN_LSTM_MFMA, FN_LSTM_MFMA_REG, FN_LSTM_ROW, FN_LSTM_WIDE,
   KERNEL_FN_COUNT
 };
+// A bank family's rules: kBankFamily[BankFamily] (api_bank.cpp), asked by pick_kernel, launch_a1_family and
+// nam_hip_batch_set_kernel. A new family adds an enumerator, a row, its branch of member_refusal and its comparison (api_bank.cpp);
+// no other file names a family. Plain data: a const table is compiled for the device too, where no host function can be pointed at.
+struct BankFamilyRules
+{
+  const char* name; // as refusals print it
+  // the kernel class (NAM_HIP_KERNEL_*) pick_kernel answers for a bank group, which is also the one explicit choice
+  // nam_hip_batch_set_kernel admits besides AUTO; NAM_HIP_KERNEL_AUTO: neither (no WaveNet group: select_kernel answers for it)
+  int kernel_class;
+  const char* set_kernel_refusal; // nam_hip_batch_set_kernel's answer to any other choice
+  unsigned fns; // bit per KernelFn that may run a bank group
+  const char* launch_refusal; // launch_a1_family's answer to any other function
+  bool kernel_region_only; // the bank keeps a member's blob from A1Plan::ws_tiles_off on (bank_blob_base), else whole blobs
+  bool init_states; // per member besides the blob: its initial state (nam_hip_bank_data::init), else two scalars (scal)
+};
+extern const BankFamilyRules kBankFamily[BANK_FAMILY_COUNT];
+inline const BankFamilyRules& bank_rules(const nam_hip_batch* b) // (b->bank is set: a bank batch)
+{
+  return kBankFamily[b->bank->family];
+}
+// first float of a member's blob the bank keeps (the single copy: nam_hip_bank_create cuts there, launch_a1_family rebases on it)
+int bank_blob_base(const Plan& p, int family);
+
 // What select_kernel needs to know about a launch besides the batch and the group
 struct LaunchQuestion
 {

@@ -101,9 +101,9 @@ int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
 {
   // a model bank runs its family's kernels for every launch shape (the other kernels know no banks): the interleaved-frame family,
   // or what a one-model A2 batch runs under AUTO (select_kernel: nam_kq_kernel / nam_kt_mfma_kernel). An LSTM bank's group is no
-  // WaveNet group: select_kernel answers for it (the gate-row kernels), nobody asks here.
-  if (g.d_bank_member && b->bank->family != BANK_LSTM)
-    return b->bank->family == BANK_A2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL;
+  // WaveNet group: select_kernel answers for it (the gate-row kernels), nobody asks here. (api_bank.cpp: kBankFamily)
+  if (g.d_bank_member && bank_rules(b).kernel_class != NAM_HIP_KERNEL_AUTO)
+    return bank_rules(b).kernel_class;
   const bool a1 = g.plan->a1.valid && g.d_a1;
   const bool mfma = a1 && (g.plan->a1.ws_ok || g.plan->a1.kt_ok);
   const bool il = a1 && g.plan->a1.il_ok && g.plan->a1.p2_ok; // the interleaved-frame kernels: the official topologies (compile-time job tables)
@@ -459,8 +459,8 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const
     // AUTO: small cells (hidden <= 4) one gate row per lane and four streams per wavefront, cells of 5 .. 32 units two
     // gate rows per lane and one stream per wavefront, else the matrix-core kernel (16 streams per wavefront);
     // NAM_HIP_KERNEL_A1_MFMA forces the matrix-core kernel; NAM_HIP_KERNEL_GENERIC: lanes = streams
-    // A model bank (BANK_LSTM) runs the first two whatever b->kernel says: the other LSTM kernels share one wavefront's weights
-    // among their streams and know no banks (api_bank.cpp admits only cells one of the two takes)
+    // A model bank runs the first two whatever b->kernel says (kBankFamily: the LSTM family's functions): the other LSTM kernels
+    // share one wavefront's weights among their streams and know no banks (api_bank.cpp admits only cells one of the two takes)
     const bool small = g.d_bank_member || (b->kernel != NAM_HIP_KERNEL_GENERIC && b->kernel != NAM_HIP_KERNEL_A1_MFMA);
     if (small && lstm_row_eligible(p.lstm))
       return FN_LSTM_ROW;
@@ -553,17 +553,13 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
   a.bank_scal = g.d_bank_scal;
   a.bank_stride = g.bank_stride;
   const bool il = fn == FN_A1_P2 || fn == FN_A1_P4 || fn == FN_A1_Q;
-  if (g.d_bank_member && !(b->bank->family == BANK_A2 ? (fn == FN_KQ || fn == FN_KT_MFMA) : il))
-    return fail(NAM_HIP_ERR_UNSUPPORTED,
-                b->bank->family == BANK_A2
-                  ? "model bank (A2 family): only nam_kq_kernel and nam_kt_mfma_kernel run it; a launch beyond 2^28 frames would take "
-                    "nam_a1_kernel, which knows no banks: split the launch"
-                  : "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank");
+  if (g.d_bank_member && !((bank_rules(b).fns >> fn) & 1u))
+    return fail(NAM_HIP_ERR_UNSUPPORTED, bank_rules(b).launch_refusal);
   if (il)
   {
     const int act = uniform_act(p.a1);
     // a bank's rows start at the kernels' region of the blob (api_bank.cpp): offsets from there
-    const int base = g.d_bank_member ? p.a1.ws_tiles_off : 0;
+    const int base = g.d_bank_member ? bank_blob_base(p, b->bank->family) : 0;
     a.tiles_off = p.a1.ws_tiles_off - base;
     a.consts_off = p.a1.ws_consts_off - base;
     a.xt_off = p.a1.ws_xt_off - base;

@@ -850,18 +850,9 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
 {
   if (!batch || kernel < NAM_HIP_KERNEL_AUTO || kernel > NAM_HIP_KERNEL_WN_REG)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_kernel: bad argument");
-  if (batch->bank)
-  {
-    // a bank batch runs its family's kernels only (api_bank.cpp)
-    const bool a2 = batch->bank->family == BANK_A2;
-    if (batch->bank->family == BANK_LSTM && kernel != NAM_HIP_KERNEL_AUTO)
-      return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_batch_set_kernel: an LSTM bank batch runs nam_lstm_row_kernel / nam_lstm_wide_kernel only "
-                                           "(NAM_HIP_KERNEL_AUTO); the matrix-core and lanes kernels know no banks");
-    if (batch->bank->family != BANK_LSTM && kernel != NAM_HIP_KERNEL_AUTO && kernel != (a2 ? NAM_HIP_KERNEL_A1_MFMA : NAM_HIP_KERNEL_A1_IL))
-      return fail(NAM_HIP_ERR_UNSUPPORTED,
-                  a2 ? "nam_hip_batch_set_kernel: an A2 bank batch runs nam_kq_kernel / nam_kt_mfma_kernel only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_MFMA)"
-                     : "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)");
-  }
+  // a bank batch runs its family's kernels only (api_bank.cpp: kBankFamily)
+  if (batch->bank && kernel != NAM_HIP_KERNEL_AUTO && kernel != bank_rules(batch).kernel_class)
+    return fail(NAM_HIP_ERR_UNSUPPORTED, bank_rules(batch).set_kernel_refusal);
   NAM_HIP_CHECK(hipSetDevice(batch->device)); // (ending a session may relaunch: the launchers configure the current device)
   if (batch->ps.active)
   {

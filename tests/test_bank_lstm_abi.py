@@ -2,12 +2,10 @@
 nam_lstm_row_kernel (hidden <= 4) or nam_lstm_wide_kernel (5 .. 32 units) takes share a batch; what is refused and how the
 refusal names its member and the field; that such a bank owns what it needs. The WaveNet families' sides are
 tests/test_bank_abi.py and tests/test_bank_a2_abi.py."""
-import ctypes
-import gc
-
 import pytest
 
-from bank_models_lstm import lstm_weights, write_lstm
+from bank_harness import fixture, refused, survives_its_models
+from bank_models import lstm_weights, write_lstm
 from conftest import model_path
 
 
@@ -16,18 +14,6 @@ def _seeded(nam, tmp_path, seed, fast_tanh=True, **kw):
     p = str(tmp_path / f"lstm_bank_{seed}_{tag}.nam")
     write_lstm(p, seed, **kw)
     return nam.get_dsp(p, fast_tanh=fast_tanh)
-
-
-def _fixture(nam, name, fast_tanh=True):
-    return nam.get_dsp(model_path(name), fast_tanh=fast_tanh)
-
-
-def _refused(nam, models, member):
-    with pytest.raises(nam.NamHipError) as e:
-        nam.ModelBank(models)
-    assert e.value.code == nam.ERR_UNSUPPORTED, str(e.value)
-    assert f"member {member}" in str(e.value), str(e.value)
-    return str(e.value)
 
 
 def test_generator_seeds_differ_in_weights_and_initial_state():
@@ -45,66 +31,45 @@ def test_lstm_bank_accepts_the_fixtures_and_seeded_members(nam_lib, tmp_path, fa
     """The gate-row kernel's shape (lstm.nam: 1 x 3) and the wide kernel's (synth_lstm_h18x2: 2 x 18), with fast_tanh on and off
     (both kernels are instantiated on it). Before the LSTM family existed member 0 was refused."""
     nam = nam_lib
-    row = [_fixture(nam, "lstm", fast_tanh), _seeded(nam, tmp_path, 511, fast_tanh), _seeded(nam, tmp_path, 512, fast_tanh)]
+    row = [fixture(nam, "lstm", fast_tanh), _seeded(nam, tmp_path, 511, fast_tanh), _seeded(nam, tmp_path, 512, fast_tanh)]
     assert len(nam.ModelBank(row)) == 3
     assert len(nam.ModelBank(row[::-1])) == 3
     assert len(nam.ModelBank(row[:1])) == 1  # a bank of one model is legal
-    wide = [_fixture(nam, "synth_lstm_h18x2", fast_tanh), _seeded(nam, tmp_path, 513, fast_tanh, num_layers=2, hidden=18)]
+    wide = [fixture(nam, "synth_lstm_h18x2", fast_tanh), _seeded(nam, tmp_path, 513, fast_tanh, num_layers=2, hidden=18)]
     assert len(nam.ModelBank(wide)) == 2
     assert len(nam.ModelBank(wide[1:])) == 1
 
 
 def test_lstm_bank_refusals_name_the_member_and_the_field(nam_lib, tmp_path):
     nam = nam_lib
-    lstm = _fixture(nam, "lstm")
+    lstm = fixture(nam, "lstm")
     seeded = _seeded(nam, tmp_path, 520)
-    assert "hidden" in _refused(nam, [lstm, seeded, _seeded(nam, tmp_path, 521, hidden=4)], 2)
-    assert "n_layers" in _refused(nam, [lstm, _seeded(nam, tmp_path, 522, num_layers=2)], 1)
-    assert "hidden" in _refused(nam, [_fixture(nam, "synth_lstm_h18x2"), _seeded(nam, tmp_path, 523, num_layers=2, hidden=20)], 1)  # (both pad to 20)
-    assert "fast_tanh" in _refused(nam, [lstm, _seeded(nam, tmp_path, 524, fast_tanh=False)], 1)
-    assert "fast_tanh" in _refused(nam, [_fixture(nam, "lstm", False), seeded], 1)
+    assert "hidden" in refused(nam, [lstm, seeded, _seeded(nam, tmp_path, 521, hidden=4)], 2)
+    assert "n_layers" in refused(nam, [lstm, _seeded(nam, tmp_path, 522, num_layers=2)], 1)
+    assert "hidden" in refused(nam, [fixture(nam, "synth_lstm_h18x2"), _seeded(nam, tmp_path, 523, num_layers=2, hidden=20)], 1)  # (both pad to 20)
+    assert "fast_tanh" in refused(nam, [lstm, _seeded(nam, tmp_path, 524, fast_tanh=False)], 1)
+    assert "fast_tanh" in refused(nam, [fixture(nam, "lstm", False), seeded], 1)
     # half a second of prewarm at the FILE's sample rate
-    assert "prewarm_samples" in _refused(nam, [lstm, _seeded(nam, tmp_path, 525, sample_rate=44100)], 1)
+    assert "prewarm_samples" in refused(nam, [lstm, _seeded(nam, tmp_path, 525, sample_rate=44100)], 1)
     # 40 hidden units: the matrix-core / lanes kernels, which know no banks
-    msg = _refused(nam, [lstm, _seeded(nam, tmp_path, 526, hidden=40)], 1)
+    msg = refused(nam, [lstm, _seeded(nam, tmp_path, 526, hidden=40)], 1)
     assert "nam_lstm_mfma_kernel" in msg and "hidden 40" in msg, msg
-    msg = _refused(nam, [_seeded(nam, tmp_path, 526, hidden=40)], 0)
+    msg = refused(nam, [_seeded(nam, tmp_path, 526, hidden=40)], 0)
     assert "nam_lstm_mfma_kernel" in msg, msg
     # one family per bank, in either order: the LATER member is the one that differs
-    std = _fixture(nam, "wavenet_a1_standard")
-    assert "family" in _refused(nam, [lstm, std], 1)
-    assert "family" in _refused(nam, [std, lstm], 1)
-    assert "family" in _refused(nam, [_fixture(nam, "A2"), lstm], 1)
-    assert "family" in _refused(nam, [lstm, seeded, _fixture(nam, "A2")], 2)
+    std = fixture(nam, "wavenet_a1_standard")
+    assert "family" in refused(nam, [lstm, std], 1)
+    assert "family" in refused(nam, [std, lstm], 1)
+    assert "family" in refused(nam, [fixture(nam, "A2"), lstm], 1)
+    assert "family" in refused(nam, [lstm, seeded, fixture(nam, "A2")], 2)
 
 
 def test_lstm_bank_survives_its_models(nam_lib, tmp_path):
     """The bank copies what it needs (blobs AND initial states): the member models are freed (their handles through
     nam_hip_model_free) before the bank is asked anything."""
-    nam = nam_lib
-    L = nam.load_library()
     seeded = str(tmp_path / "lstm_survivor.nam")
     write_lstm(seeded, 530)
-    handles = []
-    for path in (model_path("lstm"), seeded):
-        h = ctypes.c_void_p()
-        assert L.nam_hip_model_load(path.encode(), 1, ctypes.byref(h)) == 0
-        handles.append(h)
-    arr = (ctypes.c_void_p * 2)(*[h.value for h in handles])
-    bank = ctypes.c_void_p()
-    assert L.nam_hip_bank_create(arr, 2, ctypes.byref(bank)) == 0, L.nam_hip_last_error()
-    for h in handles:
-        L.nam_hip_model_free(h)
-    junk = [_seeded(nam, tmp_path, 531 + i) for i in range(3)]  # (allocations over the freed models' memory)
-    assert L.nam_hip_bank_n_models(bank) == 2
-    # a stream_model entry outside the bank is refused before any device call
-    out = ctypes.c_void_p()
-    bad = (ctypes.c_int * 4)(0, 1, 2, 0)
-    assert L.nam_hip_batch_create_bank(bank, 0, 4, 64, bad, ctypes.byref(out)) == nam.ERR_INVALID_ARGUMENT
-    assert b"member 2" in L.nam_hip_last_error() and out.value is None
-    L.nam_hip_bank_free(bank)
-    del junk
-    gc.collect()
+    survives_its_models(nam_lib, [model_path("lstm"), seeded], lambda: [_seeded(nam_lib, tmp_path, 531 + i) for i in range(3)])
 
 
 def test_version_says_lstm_banks(nam_lib):

@@ -24,8 +24,7 @@ import numpy as np
 import pytest
 
 import ring_phase as rp
-from bank_models import write_standard
-from bank_models_a2 import write_a2
+from bank_models import write_a2, write_standard
 from conftest import model_path
 from signals import stream_bank
 
@@ -64,7 +63,7 @@ CASES = {
 
 @pytest.fixture(scope="module")
 def members(tmp_path_factory):
-    """the banks' members: the committed fixture and two seeded models of its topology (tests/bank_models.py, bank_models_a2.py)"""
+    """the banks' members: the committed fixture and two seeded models of its topology (tests/bank_models.py)"""
     d = tmp_path_factory.mktemp("ring_phase_members")
     a1 = [model_path("wavenet_a1_standard")]
     a2 = [model_path("A2")]

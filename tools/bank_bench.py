@@ -5,7 +5,7 @@ regions of 500 commands — for
   (a) a one-model batch (wavenet_a1_standard; --family a2: A2.nam),
   (b) a bank batch with every stream on member 0,
   (c) a bank of 256 distinct members (standard-topology models with seeded weights, tests/bank_models.py; --family a2:
-      A2-topology models with seeded weights, head_scale and LeakyReLU slope, tests/bank_models_a2.py), one per stream;
+      A2-topology models with seeded weights, head_scale and LeakyReLU slope), one per stream;
 and the case a bank replaces: N captures as N one-stream batches called in turn with blocking 64-frame calls (N = 16 by
 default: enough to extrapolate per-capture cost, and it keeps memory and session count small).
 Every figure is the median of --runs repetitions (each a fresh timing of --regions regions); one JSON line per case.
@@ -14,7 +14,7 @@ Every figure is the median of --runs repetitions (each a fresh timing of --regio
 
 --family lstm: the LSTM family's two kernels in their bench shapes — one layer of 3 units at 1,024 streams (config 3's shape:
 nam_lstm_row_kernel, four streams per wavefront) and one layer of 24 units at 256 streams (nam_lstm_wide_kernel, one stream
-per wavefront); members from tests/bank_models_lstm.py, (a) is member 0 as a one-model batch. The three cases are INTERLEAVED:
+per wavefront); members from tests/bank_models.py, (a) is member 0 as a one-model batch. The three cases are INTERLEAVED:
 run r times (a), (b), (c) one after the other before run r + 1 starts, so that a drift of the box lands on all three.
 
     python tools/bank_bench.py --family lstm [--runs 7] [--singles 16]
@@ -93,7 +93,7 @@ def time_sessions_interleaved(batches, n_streams, in_ch, region, regions, runs):
 
 
 def main_lstm(args, nam):
-    from bank_models_lstm import write_lstm
+    from bank_models import write_lstm
     for shape, hidden, n in (("row_1x3", 3, 1024), ("wide_1x24", 24, 256)):
         with tempfile.TemporaryDirectory() as d:
             members = []
@@ -134,7 +134,7 @@ def main():
     if args.family == "lstm":
         return main_lstm(args, nam)
     if args.family == "a2":
-        from bank_models_a2 import write_a2 as write_standard
+        from bank_models import write_a2 as write_standard
     else:
         from bank_models import write_standard
     n = args.streams
