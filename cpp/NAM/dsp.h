@@ -268,7 +268,9 @@ protected:
 // (standard, lite, feather; all loaded with the same fast tanh setting), or the A2 topology (A2-Full-shaped WaveNets and
 // containers such as A2.nam, which stand for their largest submodel; one activation type, the LeakyReLU slope and head_scale
 // per member; nam_kq_kernel / nam_kt_mfma_kernel), or LSTMs of one shape with up to 32 hidden units (weights and the initial
-// state h0 / c0 per member; nam_lstm_row_kernel / nam_lstm_wide_kernel). A value type: copies share the immutable bank.
+// state h0 / c0 per member; nam_lstm_row_kernel / nam_lstm_wide_kernel), or narrow WaveNets of one topology that run on
+// nam_wn_reg_kernel (the official nano size, FiLM / gated models, a nested condition_dsp, a post-stack head; weights and
+// head_scale per member). A value type: copies share the immutable bank.
 // Construction throws std::runtime_error (naming the member) when the models cannot share a launch.
 class ModelBank
 {

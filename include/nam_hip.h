@@ -207,9 +207,14 @@ NAM_HIP_API void nam_hip_batch_destroy(nam_hip_batch* batch);
  *    size (1 or 2), hidden size (<= 32) and output channels —, loaded with the same fast_tanh, from files of one sample rate
  *    (the prewarm is half a second of it). A member's initial state (h0 / c0, part of an LSTM's weight stream) is its own.
  *    Larger cells run on kernels whose streams share one wavefront's weights: they are refused.
- * The plans are compared field by field; the first difference — a member of another family, or of another kind: nano,
- * A2-Lite, FiLM / gated models, another activation type, a
- * slimmable model — is refused with NAM_HIP_ERR_UNSUPPORTED and a message naming the member index and the field. n_models <= 0
+ *  - the nam_wn_reg_kernel family: non-slimmable WaveNets whose one-model batch runs on nam_wn_reg_kernel under AUTO — the
+ *    official nano size (4 -> 2 channels), FiLM / gated models, a nested condition_dsp, a post-stack head, narrow plain
+ *    stacks — of ONE program: the same topology (arrays, channels, kernel sizes, dilations, FiLM sets, activation types),
+ *    loaded with the same fast_tanh. Weights, head_scale and a nested condition's head scale are per member (a per-model code
+ *    object has the scales compiled in; a bank launch runs member 0's and reads each member's own from its weights).
+ *    (A plain A2-Lite-shaped WaveNet is of this family too; a SlimmableContainer never is: it stands for its largest submodel.)
+ * The plans are compared field by field; the first difference — a member of another family, or of another kind: another
+ * topology or activation type, a lookup-table activation, a slimmable model — is refused with NAM_HIP_ERR_UNSUPPORTED and a message naming the member index and the field. n_models <= 0
  * or a NULL member: NAM_HIP_ERR_INVALID_ARGUMENT. A bank of one model is legal. The bank copies what it needs: the models may
  * be freed right after, and the bank may be freed while batches created from it live. */
 NAM_HIP_API int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hip_bank** out_bank);
@@ -230,7 +235,10 @@ NAM_HIP_API int nam_hip_bank_n_models(const nam_hip_bank* bank);
  * anything else is NAM_HIP_ERR_UNSUPPORTED; one launch of more than 2^28 frames (which a one-model batch hands to
  * nam_a1_kernel) is NAM_HIP_ERR_UNSUPPORTED: split it. Kernels of an LSTM bank: nam_lstm_row_kernel (hidden <= 4) or
  * nam_lstm_wide_kernel for every launch shape and in sessions; nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO only
- * (the matrix-core and lanes kernels know no banks), anything else is NAM_HIP_ERR_UNSUPPORTED.
+ * (the matrix-core and lanes kernels know no banks), anything else is NAM_HIP_ERR_UNSUPPORTED. Kernels of a nam_wn_reg_kernel
+ * bank: that kernel for every launch shape, in sessions, and at EVERY stream count (a one-model batch of a plain narrow model
+ * beyond 8 x workgroups-per-CU x CUs streams flips to nam_a1_kernel; the bank does not, it then has no session);
+ * nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_WN_REG, anything else is NAM_HIP_ERR_UNSUPPORTED.
  * Reset with prewarm runs the silence through every stream with its own member's weights (no cached image: it depends on the
  * weights); the state equals, bit for bit, what a one-model batch of that member holds after the same Reset. */
 NAM_HIP_API int nam_hip_batch_create_bank(const nam_hip_bank* bank, int device, int n_streams, int max_frames,

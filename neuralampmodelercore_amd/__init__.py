@@ -292,10 +292,14 @@ class ModelBank:
     (standard, lite, feather), all loaded with the same ``fast_tanh``; or the A2 topology (A2-Full-shaped WaveNets, and
     containers such as ``A2.nam``, which stand for their largest submodel), all with the same activation type — the LeakyReLU
     slope and ``head_scale`` are per member; or LSTMs of one shape (layers, input size, hidden size <= 32, outputs), all loaded
-    with the same ``fast_tanh`` — weights and the initial state (h0 / c0) are per member. Anything else, mixed families included,
+    with the same ``fast_tanh`` — weights and the initial state (h0 / c0) are per member; or non-slimmable WaveNets that a
+    one-model batch runs on ``nam_wn_reg_kernel`` (the official nano size, FiLM / gated models, a nested ``condition_dsp``, a
+    post-stack head, narrow plain stacks), all of one topology and loaded with the same ``fast_tanh`` — weights and
+    ``head_scale`` are per member. Anything else, mixed families included,
     raises NamHipError(ERR_UNSUPPORTED) naming the member. An A2 bank batch runs ``nam_kq_kernel`` / ``nam_kt_mfma_kernel``; its
     ``set_kernel`` takes ``KERNEL_AUTO`` and ``KERNEL_A1_MFMA``. An LSTM bank batch runs ``nam_lstm_row_kernel`` /
-    ``nam_lstm_wide_kernel``; its ``set_kernel`` takes ``KERNEL_AUTO`` only."""
+    ``nam_lstm_wide_kernel``; its ``set_kernel`` takes ``KERNEL_AUTO`` only. A ``nam_wn_reg_kernel`` bank batch runs that kernel
+    at every stream count; its ``set_kernel`` takes ``KERNEL_AUTO`` and ``KERNEL_WN_REG``."""
 
     def __init__(self, models: Sequence[Model]):
         self._L = load_library()

@@ -14,12 +14,22 @@
 //  * BANK_LSTM: LSTMs of one shape on nam_lstm_row_kernel (hidden <= 4) / nam_lstm_wide_kernel (5 .. 32 units). Whole blobs again
 //    (base offset 0): LSTMPlan's absolute offsets (layer_w[], layer_b[], head_w, head_b) hold against any member's row. No A1Plan,
 //    no scalars; instead every member's initial state (h0 / c0 are part of an LSTM's weight stream: LSTMPlan::init_state).
-// Per member besides the blob, WaveNet families: the two scalars the kernels take by value (head_scale, act_p0 — on the A2
+//  * BANK_WN_REG: WaveNets that a one-model batch runs on nam_wn_reg_kernel under AUTO — the official nano size, FiLM, gating, a
+//    nested condition_dsp, a post-stack head, narrow plain stacks — of ONE program: equal WrPlan::structure_key. The bank keeps
+//    WrPlan::blob whole (weights | tables | op program; base offset 0), and nothing besides: head_scale and a nested condition's
+//    scale are in the member's own op table, where a bank launch reads them (kernel_wn_reg.hip: wr_scales) — a per-model code
+//    object has them compiled in, so two captures of one topology have two code objects; the launch runs member 0's (the proto
+//    plan's) and a member's own, which its load compiled, stays unused. Such a bank runs nam_wn_reg_kernel at EVERY stream count:
+//    a one-model batch of a plain narrow model beyond kPersistTurns x per_cu x CUs streams flips to nam_a1_kernel and another
+//    state layout (pick_kernel), the bank does not (beyond that count it has no session: a launch per buffer).
+// Per member besides the blob, the two A1Plan families: the two scalars the kernels take by value (head_scale, act_p0 — on the A2
 // topology the LeakyReLU slope, 0 for ReLU as in launch_kq).
 //
 // A family's rules are its row of kBankFamily below (api_internal.h: BankFamilyRules); the other files ask that row and name no
 // family. Here a family is named by member_refusal (which family a model is of), by its comparison function and by its row.
 #include "api_internal.h"
+
+#include <cstdio>
 
 namespace namhip
 {
@@ -71,8 +81,16 @@ std::string member_refusal(const nam_hip_model& m, int* family)
     return "a slimmable WaveNet (its widths are separate plans; banks hold one plan per member)";
   const Plan& p = member_plan(m);
   const A1Plan& a = p.a1;
+  // pick_kernel's AUTO answer for a one-model batch (below the stream count at which a plain narrow model flips to nam_a1_kernel)
+  if (p.wr.ok && !(a.valid && (a.ws_ok || a.kt_ok)))
+  {
+    *family = BANK_WN_REG;
+    return "";
+  }
   if (!a.valid)
-    return "outside the A1 kernel family (FiLM / gating / groups / a lookup-table or per-channel activation / a post-stack head ...)";
+    return "outside the A1 kernel family (FiLM / gating / groups / a lookup-table or per-channel activation / a post-stack head ...) and "
+           "without a nam_wn_reg_kernel plan ("
+           + (p.wr.jit_failed.empty() ? p.wr.why : p.wr.why + "; per-model compile: " + p.wr.jit_failed) + ")";
   if (a2_member(a))
   {
     *family = BANK_A2;
@@ -202,9 +220,47 @@ void lstm_difference(FirstDifference& cmp, const nam_hip_model& m0, const nam_hi
   cmp("state_floats", p.state_floats, q.state_floats);
 }
 
+void wr_difference(FirstDifference& cmp, const nam_hip_model& m0, const nam_hip_model& m)
+{
+  const Plan &p = member_plan(m), &q = member_plan(m0);
+  const WrPlan &x = p.wr, &y = q.wr;
+  cmp("fast_tanh", m.spec->fast_tanh ? 1 : 0, m0.spec->fast_tanh ? 1 : 0);
+  cmp("in_channels", p.in_channels, q.in_channels);
+  cmp("out_channels", p.out_channels, q.out_channels);
+  cmp("prewarm_samples", p.prewarm_samples, q.prewarm_samples);
+  cmp("state_floats", p.state_floats, q.state_floats);
+  // the program: op types, shapes, weight offsets, rings, dilations, flags, activations, the tables, the cuts — everything of
+  // the plan but the weights and the scales (plan.h). NOT jit_module: another head_scale is another file; the launch runs member 0's
+  if (cmp.text.empty() && x.structure_key != y.structure_key)
+  {
+    char t[96];
+    std::snprintf(t, sizeof(t), "wr.structure_key (the program: %016llx vs %016llx)", x.structure_key, y.structure_key);
+    cmp.text = t;
+  }
+  // what launch_wr takes from the plan (member 0's), field by field
+  cmp("wr.blob floats", (long long)x.blob.size(), (long long)y.blob.size());
+  cmp("wr.n_layers", x.n_layers, y.n_layers);
+  cmp("wr.hist_floats", x.hist_floats, y.hist_floats);
+  cmp("wr.lds_bytes", x.lds_bytes, y.lds_bytes);
+  cmp("wr.tab_rows", x.tab_rows, y.tab_rows);
+  cmp("wr.n_rows", x.n_rows, y.n_rows);
+  cmp("wr.tab_pf", x.tab_pf, y.tab_pf);
+  cmp("wr.n_pf", x.n_pf, y.n_pf);
+  cmp("wr.tab_ring", x.tab_ring, y.tab_ring);
+  cmp("wr.tab_ops", x.tab_ops, y.tab_ops);
+  cmp("wr.n_ops", (long long)x.ops.size(), (long long)y.ops.size());
+  for (int i = 0; i < 4; i++)
+    cmp("wr.split_op", x.split_op[i], y.split_op[i]);
+  cmp("wr.has_layers", x.has_layers ? 1 : 0, y.has_layers ? 1 : 0);
+  cmp("wr.has_runs", x.has_runs ? 1 : 0, y.has_runs ? 1 : 0);
+  cmp("wr.has_rt_layers", x.has_rt_layers ? 1 : 0, y.has_rt_layers ? 1 : 0);
+  cmp("wr.program", x.program, y.program);
+  cmp("wr per-model code object (1) / ahead-of-time kernel (0)", x.jit_module.empty() ? 0 : 1, y.jit_module.empty() ? 0 : 1);
+}
+
 // ... by family, in kBankFamily's order
 void (*const kFirstDifference[BANK_FAMILY_COUNT])(FirstDifference&, const nam_hip_model& m0, const nam_hip_model& m) = {
-  a1_il_difference, a2_difference, lstm_difference};
+  a1_il_difference, a2_difference, lstm_difference, wr_difference};
 } // namespace
 
 // The families' rules, indexed by BankFamily (api_internal.h: BankFamilyRules); the texts are what a caller reads in nam_hip_last_error
@@ -213,23 +269,31 @@ const BankFamilyRules kBankFamily[BANK_FAMILY_COUNT] = {
    "nam_hip_batch_set_kernel: a bank batch runs the interleaved-frame kernels only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_IL)",
    1u << FN_A1_P2 | 1u << FN_A1_P4 | 1u << FN_A1_Q,
    "model bank: only the interleaved-frame kernels (NAM_HIP_KERNEL_A1_IL) run a bank",
-   /*kernel_region_only*/ true, /*init_states*/ false},
+   BANK_BLOB_KERNEL_REGION, BANK_MEMBER_SCALARS},
   {"A2 (nam_kq_kernel)", NAM_HIP_KERNEL_A1_MFMA,
    "nam_hip_batch_set_kernel: an A2 bank batch runs nam_kq_kernel / nam_kt_mfma_kernel only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_A1_MFMA)",
    1u << FN_KQ | 1u << FN_KT_MFMA,
    "model bank (A2 family): only nam_kq_kernel and nam_kt_mfma_kernel run it; a launch beyond 2^28 frames would take "
    "nam_a1_kernel, which knows no banks: split the launch",
-   /*kernel_region_only*/ false, /*init_states*/ false},
+   BANK_BLOB_WHOLE, BANK_MEMBER_SCALARS},
   // (no WaveNet group: pick_kernel is not asked and launch_a1_family not reached; select_kernel answers one of the two functions)
   {"LSTM (nam_lstm_row_kernel / nam_lstm_wide_kernel)", NAM_HIP_KERNEL_AUTO,
    "nam_hip_batch_set_kernel: an LSTM bank batch runs nam_lstm_row_kernel / nam_lstm_wide_kernel only "
    "(NAM_HIP_KERNEL_AUTO); the matrix-core and lanes kernels know no banks",
-   1u << FN_LSTM_ROW | 1u << FN_LSTM_WIDE, "", /*kernel_region_only*/ false, /*init_states*/ true},
+   1u << FN_LSTM_ROW | 1u << FN_LSTM_WIDE, "", BANK_BLOB_WHOLE, BANK_MEMBER_INIT_STATES},
+  // (launch_wr takes the group whatever the stream count: pick_kernel answers the class before the one-model rules)
+  {"WN_REG (nam_wn_reg_kernel)", NAM_HIP_KERNEL_WN_REG,
+   "nam_hip_batch_set_kernel: a nam_wn_reg_kernel bank batch runs that kernel only (NAM_HIP_KERNEL_AUTO / NAM_HIP_KERNEL_WN_REG)",
+   1u << FN_WN_REG, "model bank (nam_wn_reg_kernel family): only nam_wn_reg_kernel runs it", BANK_BLOB_WR, BANK_MEMBER_NOTHING},
 };
 
 int bank_blob_base(const Plan& p, int family)
 {
-  return kBankFamily[family].kernel_region_only ? p.a1.ws_tiles_off : 0;
+  return kBankFamily[family].blob_source == BANK_BLOB_KERNEL_REGION ? p.a1.ws_tiles_off : 0;
+}
+const std::vector<float>& bank_blob(const Plan& p, int family)
+{
+  return kBankFamily[family].blob_source == BANK_BLOB_WR ? p.wr.blob : p.blob;
 }
 
 // The device image of a bank batch's one group (instead of upload_group): every member's kernel region in ONE allocation, the
@@ -238,14 +302,15 @@ int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
 {
   const nam_hip_bank_data& bank = *b->bank;
   const Plan& p = *g.plan;
-  NAM_HIP_CHECK(hipMalloc(&g.d_blob, bank.blobs.size() * sizeof(float)));
-  NAM_HIP_CHECK(hipMemcpy(g.d_blob, bank.blobs.data(), bank.blobs.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (kBankFamily[bank.family].init_states)
+  float*& d_blobs = kBankFamily[bank.family].blob_source == BANK_BLOB_WR ? g.d_wr_blob : g.d_blob;
+  NAM_HIP_CHECK(hipMalloc(&d_blobs, bank.blobs.size() * sizeof(float)));
+  NAM_HIP_CHECK(hipMemcpy(d_blobs, bank.blobs.data(), bank.blobs.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (kBankFamily[bank.family].per_member == BANK_MEMBER_INIT_STATES)
   {
     NAM_HIP_CHECK(hipMalloc(&g.d_init, std::max<size_t>(bank.init.size(), 1) * sizeof(float)));
     NAM_HIP_CHECK(hipMemcpy(g.d_init, bank.init.data(), bank.init.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  else
+  else if (kBankFamily[bank.family].per_member == BANK_MEMBER_SCALARS)
   {
     NAM_HIP_CHECK(hipMalloc(&g.d_a1, sizeof(A1Plan)));
     NAM_HIP_CHECK(hipMemcpy(g.d_a1, &p.a1, sizeof(A1Plan), hipMemcpyHostToDevice));
@@ -304,7 +369,7 @@ int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, in
   NAM_HIP_CHECK(hipMemcpy(d_moved, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice));
   // An LSTM's Reset clears nothing (the reference's has nothing to clear: its state is h / c, born from the weight stream), so the
   // moved streams would keep the OLD member's h / c: they get the new member's h0 / c0 here, as a newly created batch's streams do
-  int rc = kBankFamily[b->bank->family].init_states ? bank_fill_initial_state(b, g, d_moved, (int)moved.size()) : NAM_HIP_OK;
+  int rc = kBankFamily[b->bank->family].per_member == BANK_MEMBER_INIT_STATES ? bank_fill_initial_state(b, g, d_moved, (int)moved.size()) : NAM_HIP_OK;
   if (rc == NAM_HIP_OK)
     rc = reset_streams(b, g, d_moved, (int)moved.size(), b->was_reset && b->reset_with_prewarm, -1);
   const hipError_t e = hipStreamSynchronize(b->stream);
@@ -356,26 +421,26 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
     data->proto.width_channels.push_back({});
     data->proto.full_width = 0;
     data->n_members = n_models;
-    const bool init_states = kBankFamily[family].init_states;
-    const size_t region = p0.blob.size() - (size_t)bank_blob_base(p0, family);
+    const BankPerMember per_member = kBankFamily[family].per_member;
+    const size_t region = bank_blob(p0, family).size() - (size_t)bank_blob_base(p0, family);
     data->blob_stride = (long)((region + 3) / 4 * 4);
     data->blobs.assign((size_t)n_models * (size_t)data->blob_stride, 0.f);
-    if (init_states)
+    if (per_member == BANK_MEMBER_INIT_STATES)
     {
       data->n_init = (int)p0.lstm.init_state.size();
       data->init.assign((size_t)n_models * (size_t)data->n_init, 0.f);
     }
-    else
+    else if (per_member == BANK_MEMBER_SCALARS)
       data->scal.resize((size_t)n_models * 2);
     for (int i = 0; i < n_models; i++)
     {
       const Plan& p = member_plan(*models[i]);
-      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, p.blob.data() + bank_blob_base(p, family), region * sizeof(float));
-      if (init_states)
-      {
+      std::memcpy(data->blobs.data() + (size_t)i * (size_t)data->blob_stride, bank_blob(p, family).data() + bank_blob_base(p, family),
+                  region * sizeof(float));
+      if (per_member == BANK_MEMBER_INIT_STATES)
         std::copy(p.lstm.init_state.begin(), p.lstm.init_state.end(), data->init.begin() + (size_t)i * (size_t)data->n_init);
+      if (per_member != BANK_MEMBER_SCALARS)
         continue;
-      }
       data->scal[2 * (size_t)i] = p.blob[(size_t)p.a1.head_scale_off];
       // nam_kq_kernel runs ReLU as LeakyReLU with slope 0 (launch_kq does the same for one model)
       data->scal[2 * (size_t)i + 1] = (family == BANK_A2 && p.a1.arr[0].act == ACT_RELU) ? 0.0f : p.a1.arr[0].act_p0;

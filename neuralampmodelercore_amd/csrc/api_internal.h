@@ -94,8 +94,9 @@ struct nam_hip_model
 };
 
 // A model bank (nam_hip_bank_create): models that plan onto ONE instantiation of a kernel family — the interleaved-frame kernels
-// (nam_a1_q_kernel and its siblings: BANK_A1_IL), the A2 topology's (nam_kq_kernel, nam_kt_mfma_kernel: BANK_A2) or the small
-// LSTM cells' (nam_lstm_row_kernel, nam_lstm_wide_kernel: BANK_LSTM) — with the same blob layout, so that one launch can run
+// (nam_a1_q_kernel and its siblings: BANK_A1_IL), the A2 topology's (nam_kq_kernel, nam_kt_mfma_kernel: BANK_A2), the small
+// LSTM cells' (nam_lstm_row_kernel, nam_lstm_wide_kernel: BANK_LSTM) or nam_wn_reg_kernel with one program (BANK_WN_REG) — with
+// the same blob layout, so that one launch can run
 // them side by side, each workgroup on its stream's member. Immutable host data, self-contained (nothing of the member models is
 // referenced after creation); a batch created from it shares ownership of `data`, so the handle may be freed while batches live.
 enum BankFamily : int
@@ -103,6 +104,8 @@ enum BankFamily : int
   BANK_A1_IL = 0, // the official WaveNet topology at (padded) 16 / 8 channels
   BANK_A2 = 1, // the A2 topology (kp_table.h)
   BANK_LSTM = 2, // LSTMs of one shape on the gate-row kernels (hidden <= 32, one or two layers, one or two inputs)
+  BANK_WN_REG = 3, // WaveNets a one-model batch runs on nam_wn_reg_kernel under AUTO (the official nano size, FiLM, gating, a nested
+                   // condition_dsp, a post-stack head, narrow plain stacks), of ONE program (WrPlan::structure_key)
   BANK_FAMILY_COUNT
 };
 struct nam_hip_bank_data
@@ -113,7 +116,7 @@ struct nam_hip_bank_data
   int n_members = 0;
   long blob_stride = 0; // floats per member in `blobs`: the kept part of the plan's blob (api_bank.cpp) rounded up to a multiple of four (16-byte records)
   std::vector<float> blobs; // [n_members][blob_stride]
-  // per member besides the blob, one of the two (BankFamilyRules::init_states says which; the other stays empty):
+  // per member besides the blob, at most one of the two (BankFamilyRules::per_member says which; what it does not name stays empty):
   std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal)
   int n_init = 0; // floats of a member's initial state (LSTMPlan::init_state: h0 / c0 from ITS weight stream)
   std::vector<float> init; // [n_members][n_init]
@@ -154,7 +157,8 @@ struct WidthGroup
   // a bank batch's one group (api_bank.cpp): d_blob holds [members][bank_stride] floats, and the kernels pick a stream's member
   // through d_bank_member[stream] (indexed by STREAM, not by launch position) and its scalars from d_bank_scal[2 member].
   // No prewarm cache: a member's prewarmed state depends on its weights, so a Reset runs the silence for every stream.
-  // BankFamilyRules::init_states: no d_a1 and no d_bank_scal; d_init holds [members][n_init] floats, a stream's h0 / c0 its member's row.
+  // BANK_MEMBER_INIT_STATES: no d_a1 and no d_bank_scal; d_init holds [members][n_init] floats, a stream's h0 / c0 its member's row.
+  // BANK_BLOB_WR: the members' blobs are in d_wr_blob (where pick_kernel and wr_groups look), d_blob stays empty.
   int* d_bank_member = nullptr;
   float* d_bank_scal = nullptr;
   long bank_stride = 0;
@@ -352,6 +356,18 @@ enum KernelFn : int
 // A bank family's rules: kBankFamily[BankFamily] (api_bank.cpp), asked by pick_kernel, launch_a1_family and
 // nam_hip_batch_set_kernel. A new family adds an enumerator, a row, its branch of member_refusal and its comparison (api_bank.cpp);
 // no other file names a family. Plain data: a const table is compiled for the device too, where no host function can be pointed at.
+enum BankBlobSource : int // which part of which of a member's blobs the bank keeps
+{
+  BANK_BLOB_KERNEL_REGION, // Plan::blob from A1Plan::ws_tiles_off on (bank_blob_base)
+  BANK_BLOB_WHOLE, // Plan::blob whole, base offset 0
+  BANK_BLOB_WR // Plan::wr.blob whole, base offset 0 (nam_wn_reg_kernel's weights, tables and program)
+};
+enum BankPerMember : int // what a member carries besides its blob
+{
+  BANK_MEMBER_SCALARS, // two scalars (nam_hip_bank_data::scal: head_scale, act_p0) and the device A1Plan of member 0
+  BANK_MEMBER_INIT_STATES, // its initial state (nam_hip_bank_data::init)
+  BANK_MEMBER_NOTHING // everything is in the blob
+};
 struct BankFamilyRules
 {
   const char* name; // as refusals print it
@@ -361,8 +377,8 @@ struct BankFamilyRules
   const char* set_kernel_refusal; // nam_hip_batch_set_kernel's answer to any other choice
   unsigned fns; // bit per KernelFn that may run a bank group
   const char* launch_refusal; // launch_a1_family's answer to any other function
-  bool kernel_region_only; // the bank keeps a member's blob from A1Plan::ws_tiles_off on (bank_blob_base), else whole blobs
-  bool init_states; // per member besides the blob: its initial state (nam_hip_bank_data::init), else two scalars (scal)
+  BankBlobSource blob_source; // what the bank keeps of a member (bank_blob, bank_blob_base)
+  BankPerMember per_member;
 };
 extern const BankFamilyRules kBankFamily[BANK_FAMILY_COUNT];
 inline const BankFamilyRules& bank_rules(const nam_hip_batch* b) // (b->bank is set: a bank batch)
@@ -371,6 +387,8 @@ inline const BankFamilyRules& bank_rules(const nam_hip_batch* b) // (b->bank is 
 }
 // first float of a member's blob the bank keeps (the single copy: nam_hip_bank_create cuts there, launch_a1_family rebases on it)
 int bank_blob_base(const Plan& p, int family);
+// the blob of a member's plan the family's kernels read (BankFamilyRules::blob_source)
+const std::vector<float>& bank_blob(const Plan& p, int family);
 
 // What select_kernel needs to know about a launch besides the batch and the group
 struct LaunchQuestion

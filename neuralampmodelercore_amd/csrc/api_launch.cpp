@@ -100,8 +100,10 @@ constexpr size_t kKtAutoMaxStreams = 1024;
 int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
 {
   // a model bank runs its family's kernels for every launch shape (the other kernels know no banks): the interleaved-frame family,
-  // or what a one-model A2 batch runs under AUTO (select_kernel: nam_kq_kernel / nam_kt_mfma_kernel). An LSTM bank's group is no
-  // WaveNet group: select_kernel answers for it (the gate-row kernels), nobody asks here. (api_bank.cpp: kBankFamily)
+  // what a one-model A2 batch runs under AUTO (select_kernel: nam_kq_kernel / nam_kt_mfma_kernel), or nam_wn_reg_kernel — at EVERY
+  // stream count: the one-model rule below that hands a plain narrow model to nam_a1_kernel beyond kPersistTurns x per_cu x CUs
+  // streams (another state layout) does not apply to a bank. An LSTM bank's group is no WaveNet group: select_kernel answers for
+  // it (the gate-row kernels), nobody asks here. (api_bank.cpp: kBankFamily)
   if (g.d_bank_member && bank_rules(b).kernel_class != NAM_HIP_KERNEL_AUTO)
     return bank_rules(b).kernel_class;
   const bool a1 = g.plan->a1.valid && g.d_a1;
@@ -369,6 +371,8 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
   a.in_ch = groups[0]->plan->in_channels;
   a.out_ch = groups[0]->plan->out_channels;
   a.ps = persist_args(b);
+  a.bank_member = groups[0]->d_bank_member; // (a bank batch has one group: groups[0]->d_wr_blob is [members][bank_stride])
+  a.bank_stride = groups[0]->bank_stride;
   // every group on the model's own code object (they share one: build_model), or every group on the ahead-of-time kernel
   if (stages == 2) // (the kernels read a two-wave launch's cut from [1]: WrGroup::split_op)
     for (int k = 0; k < n_groups; k++)
@@ -843,13 +847,17 @@ int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out)
   {
     std::string why;
     const std::string module = wr_jit_build(jit_shapes, why);
+    const std::string masked = jit_shapes.header_text(true); // (WrPlan::structure_key: the code object's text but for the scales)
     for (size_t i = 0; i < m->plans.size(); i++)
     {
       Plan& p = m->plans[i];
       if (!(p.wr.ok && p.wr.jit))
         continue;
       if (!module.empty())
+      {
         p.wr.jit_module = module;
+        p.wr.structure_key = wr_hash(masked.data(), masked.size(), p.wr.structure_key);
+      }
       else
       {
         // no compiler / sources here: plan again without the model's own shapes (run-time-flag instantiations if the

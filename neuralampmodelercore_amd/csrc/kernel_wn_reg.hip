@@ -873,14 +873,13 @@ __device__ __forceinline__ void wr_array_end_k(WrRegs& r, const WrOpS& op, char*
 // Conv1D(kernel KH, dilation 1, bias) whose history is of the ACTIVATED input (the reference activates in place before
 // Conv1D::Process). W^T = [KH * HI][pad4(HS)] | bias | activation parameters.
 template <int HI, int HS, int KH, int ACT>
-__device__ __forceinline__ void wr_post_head(WrRegs& r, const WrOpS& op, char* lds, int lane, int posv)
+__device__ __forceinline__ void wr_post_head(WrRegs& r, const WrOpS& op, const float sc, char* lds, int lane, int posv)
 {
   WrMat<HS, KH * HI> m;
   const unsigned wb = (unsigned)op.w * 4u, bb = wb + (unsigned)(KH * HI * wr_pad4(HS)) * 4u;
   wr_ld(m, lds, wb, true, bb);
   WrActP<HI> ap;
   wr_ld(ap, lds, bb + (unsigned)wr_pad4(HS) * 4u);
-  const float sc = op.scale();
   float v[kWrRegs];
 #pragma unroll
   for (int i = 0; i < HI; i++)
@@ -969,9 +968,70 @@ __device__ __forceinline__ void wr_run_by_id(WrRegs& r, char* lds, int lane, int
   WR_RUN_SHAPES(X)
 #undef X
 }
+// The two scales of a program that are a MODEL's and not its topology's (plan_wr.cpp): the nested condition_dsp's head_scale on
+// WR_SET_COND (at most one: no condition_dsp inside a condition_dsp), and the model's head_scale on the first WR_POST_HEAD of a
+// post-stack head, else on WR_OUTPUT (every other WR_POST_HEAD, and WR_OUTPUT behind a post-stack head, carry the planner's 1).
+// One model: the constants of the header. A bank launch runs member 0's code object on every member's weights, and these two
+// are per member: read ONCE per launch, behind the prologue's copy, from the member's own op table in the LDS copy of its blob
+// (WrGroup::tab_ops: the program as planned, 16 ints per op, the scale at byte 44) — WrScales. The ops then multiply by a scalar
+// register where the one-model code had a literal.
+struct WrScales
+{
+  float cond, head;
+};
+template <int P>
+constexpr int wr_planned_op(int type) // first op of that type in the program as planned, -1 = none
+{
+  for (int j = 0; j < kWrProgCount[0][P]; j++)
+    if (kWrProgOps[0][P][j].type == type)
+      return j;
+  return -1;
+}
+template <int P>
+constexpr int wr_head_scale_op()
+{
+  return wr_planned_op<P>(WR_POST_HEAD) >= 0 ? wr_planned_op<P>(WR_POST_HEAD) : wr_planned_op<P>(WR_OUTPUT);
+}
+template <int CUT, int P, int I>
+constexpr bool wr_first_of_its_type() // (the cut form splits WR_RUNs only: every other op keeps its place among its own type)
+{
+  for (int i = 0; i < I; i++)
+    if (kWrProgOps[CUT][P][i].type == kWrProgOps[CUT][P][I].type)
+      return false;
+  return true;
+}
+template <int P>
+__device__ __forceinline__ WrScales wr_scales(const char* lds, unsigned ops_b, bool bank)
+{
+  constexpr int jc = wr_planned_op<P>(WR_SET_COND), jh = wr_head_scale_op<P>();
+  static_assert(jh >= 0, "a program ends in WR_OUTPUT");
+  auto member = [&](int j) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(lds + ops_b + (unsigned)j * 64u + 44u)));
+  };
+  WrScales sc{jc >= 0 ? kWrProgOps[0][P][jc].scale() : 0.0f, kWrProgOps[0][P][jh].scale()};
+  if (bank)
+  {
+    if constexpr (jc >= 0)
+      sc.cond = member(jc);
+    sc.head = member(jh);
+  }
+  return sc;
+}
+// the scale op I of program P multiplies by
+template <int CUT, int P, int I>
+__device__ __forceinline__ float wr_op_scale(const WrScales& sc)
+{
+  constexpr WrOpS cur = kWrProgOps[CUT][P][I];
+  if constexpr (cur.type == WR_SET_COND)
+    return sc.cond;
+  else if constexpr (cur.type == kWrProgOps[0][P][wr_head_scale_op<P>()].type && wr_first_of_its_type<CUT, P, I>())
+    return sc.head;
+  else
+    return cur.scale();
+}
 // op I of program P (everything but WR_OUTPUT, which needs the launch's windows: the caller's)
 template <int CUT, int P, int I>
-__device__ __forceinline__ void wr_exec_op(WrRegs& r, char* lds, int lane, int posv)
+__device__ __forceinline__ void wr_exec_op(WrRegs& r, char* lds, int lane, int posv, const WrScales& scales)
 {
   constexpr WrOpS cur = kWrProgOps[CUT][P][I];
   if constexpr (cur.type == WR_LAYER)
@@ -1006,15 +1066,16 @@ __device__ __forceinline__ void wr_exec_op(WrRegs& r, char* lds, int lane, int p
   {
 #define X(ID, IN, OUT, KH, ACT) \
   if constexpr (cur.shape == ID) \
-    wr_post_head<IN, OUT, KH, ACT>(r, cur, lds, lane, posv);
+    wr_post_head<IN, OUT, KH, ACT>(r, cur, wr_op_scale<CUT, P, I>(scales), lds, lane, posv);
     WR_POSTHEAD_SHAPES(X)
 #undef X
   }
   else if constexpr (cur.type == WR_SET_COND)
   {
+    const float sc = wr_op_scale<CUT, P, I>(scales);
 #pragma unroll
     for (int c = 0; c < kWrRegs; c++)
-      r.cond[c] = cur.scale() * r.hout[c];
+      r.cond[c] = sc * r.hout[c];
   }
 }
 #endif
@@ -1046,6 +1107,10 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
   const WrGroup& G = a.g[gi];
   const int member = (int)blockIdx.x - G.first;
   const int stream = G.stream_map ? G.stream_map[member] : member;
+  // model bank (WrArgs::bank_member; a run-time test, wavefront-uniform: every wave of the workgroup finds the same base): the
+  // stream's member's blob instead of the group's one. The prologue below reads it; everything behind reads the LDS copy.
+  const bool bank = a.bank_member != nullptr;
+  const float* const blob = bank ? G.blob + (long)__builtin_amdgcn_readfirstlane(a.bank_member[stream]) * a.bank_stride : G.blob;
   // persistent session (persist_wave.h): blocks come from commands, not from a frame count
   const bool pers = a.ps.ring != nullptr;
   PersistWave pw;
@@ -1101,8 +1166,8 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
   // (wavefront-uniform: scalar loads), lane j <-> ring index wrap(position - o + j) — before the weights, so that both
   // travel together; everything lands in LDS afterwards: [blob (weights, tables, program)][rings].
   const int pos_in = sti[lane];
-  const int ring_len = lane < G.n_slots ? reinterpret_cast<const int*>(G.blob + G.tab_ring)[lane] : 0; // R of slot `lane`
-  const i4* const tab_pf = reinterpret_cast<const i4*>(G.blob + G.tab_pf);
+  const int ring_len = lane < G.n_slots ? reinterpret_cast<const int*>(blob + G.tab_ring)[lane] : 0; // R of slot `lane`
+  const i4* const tab_pf = reinterpret_cast<const i4*>(blob + G.tab_pf);
   const int n_pf = whole ? 0 : G.n_pf;
   constexpr int kWin = 64;
   float win[kWin];
@@ -1130,7 +1195,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
     for (int u = 0; u < 8; u++)
     {
       const int i = base + u * 256 * NST + t4;
-      v[u] = i < blob_floats ? *reinterpret_cast<const f4*>(G.blob + i) : f4{0.f, 0.f, 0.f, 0.f};
+      v[u] = i < blob_floats ? *reinterpret_cast<const f4*>(blob + i) : f4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int u = 0; u < 8; u++)
@@ -1286,6 +1351,13 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
   };
   if constexpr (NST > 1)
     __syncthreads(); // the blob and the rings are in LDS (every wave copied its share)
+#ifdef NAM_WR_PROGRAMS
+  WrScales scales{0.0f, 0.0f}; // (behind the copy: a bank launch reads its member's)
+  wr_static_for<0, NAM_WR_N_PROGRAMS>([&](auto p_tag) {
+    if (G.prog == decltype(p_tag)::value)
+      scales = wr_scales<decltype(p_tag)::value>(lds, ops_b, bank);
+  });
+#endif
   const int pf_at = (oi0 + oi1) >> 1;
   int kbuf = 0; // NST > 1: buffers this wave has handed over / taken
   for (int f0 = pers ? (int)cmd_off : 0;;)
@@ -1362,14 +1434,15 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
           {
             if (out)
             {
+              const float sc = wr_op_scale<CUT, P, I>(scales);
 #pragma unroll
               for (int c = 0; c < kWrRegs; c++)
                 if (c < cur.n_out && lane < n)
-                  out[(long)c * a.io_stride + f0 + lane] = cur.scale() * r.hout[c];
+                  out[(long)c * a.io_stride + f0 + lane] = sc * r.hout[c];
             }
           }
           else
-            wr_exec_op<CUT, P, I>(r, lds, lane, posv);
+            wr_exec_op<CUT, P, I>(r, lds, lane, posv, scales);
         });
       };
       using std::integral_constant;
@@ -1414,7 +1487,6 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
 #ifdef NAM_WR_MARKERS
     asm volatile("; nam_op program -1 op -1 type -1 stages %0" ::"i"(NST)); // (behind the program: the per-buffer remainder)
 #endif
-    (void)ops_b;
     (void)n_ops;
     (void)oi0;
     (void)oi1;
@@ -1514,7 +1586,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
           switch (cur.shape)
           {
 #define X(ID, IN, OUT, KH, ACT) \
-  case ID: wr_post_head<IN, OUT, KH, ACT>(r, cur, lds, lane, posv); break;
+  case ID: wr_post_head<IN, OUT, KH, ACT>(r, cur, cur.scale(), lds, lane, posv); break;
             WR_POSTHEAD_SHAPES(X)
 #undef X
             default: __builtin_trap();

@@ -291,6 +291,13 @@ struct WrArgs
   int n_frames;
   int in_ch, out_ch;
   PersistArgs ps;
+  // model bank (nam_hip_batch_create_bank; nullptr = one model): a bank launch has ONE group, and stream s runs member
+  // m = bank_member[s] (indexed by STREAM, not by launch position) of g[0].blob = [members][bank_stride] floats — whole WrPlan
+  // blobs (a multiple of four floats), one layout for every member (api_bank.cpp compares the plans). Read in the prologue, which
+  // copies the member's blob to LDS; behind it only the scales of WR_OUTPUT / WR_SET_COND / WR_POST_HEAD ask again (a per-model
+  // code object has member 0's compiled in: kernel_wn_reg.hip, wr_op_scale). Behind every other field, as in LSTMArgs.
+  const int* bank_member;
+  long bank_stride;
 };
 
 // stages = 2 / 4: that many wavefronts per stream (the op program cut at WrGroup::split_op), lds_bytes including the

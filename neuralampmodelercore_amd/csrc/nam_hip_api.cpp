@@ -49,7 +49,7 @@ int nam_hip_version_support(const char* nam_file_version)
 
 const char* nam_hip_version(void)
 {
-  return "nam_hip 0.2.4 gfx950"; // 0.2.4: nam_hip_bank_create accepts the LSTM family (cells nam_lstm_row_kernel / nam_lstm_wide_kernel take); 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
+  return "nam_hip 0.2.5 gfx950"; // 0.2.5: nam_hip_bank_create accepts the nam_wn_reg_kernel family (the official nano size, FiLM / gated / nested condition_dsp / post-stack head models, narrow plain stacks: members of one program); 0.2.4: nam_hip_bank_create accepts the LSTM family (cells nam_lstm_row_kernel / nam_lstm_wide_kernel take); 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
 }
 
 int nam_hip_model_load(const char* nam_path, int fast_tanh, nam_hip_model** out_model)

@@ -454,6 +454,12 @@ struct WrPlan
   // object compiled for it ("" until api_launch.cpp: build_model has prepared it — the plan is not runnable before)
   bool jit = false;
   std::string jit_module;
+  // What a model bank compares (api_bank.cpp: wr_difference): two plans with equal keys can run as ONE launch, on either plan's
+  // code object, each stream on its own plan's blob. The hash of the walked program — the ops without their `scale`, the `rows` /
+  // `pf` / `ring` tables, run_recs, the cuts — and, once a per-model code object is in play (api_launch.cpp: build_model), of its
+  // header text with every scale_bits field masked as well (WrShapeSet::header_text(true)). head_scale and a nested condition's
+  // scale stay per member: a bank launch reads them from the member's own op table.
+  unsigned long long structure_key = 0;
 };
 
 // The layer shapes kernel_wn_reg.hip instantiates AHEAD OF TIME — (id, condition size, channels, bottleneck, gating,
@@ -549,7 +555,9 @@ struct WrShapeSet
   std::vector<Program> programs;
   std::vector<std::array<int32_t, 4>> run_recs; // {w, ring area offset, R, dilation | slot << 24} of every layer of every WR_RUN
   bool empty() const { return layers.empty() && runs.empty() && pairs.empty() && heads.empty() && posts.empty(); }
-  std::string header_text() const; // the generated tables: "#define NAM_WR_JIT_SHAPES 1 / #define WR_LAYER_SHAPES(X) ..."
+  // the generated tables: "#define NAM_WR_JIT_SHAPES 1 / #define WR_LAYER_SHAPES(X) ..."; `mask_scales`: every scale_bits field
+  // written as 0 — not a header to compile, the text WrPlan::structure_key hashes
+  std::string header_text(bool mask_scales = false) const;
 };
 // id of a shape in the ahead-of-time tables, -1 = not instantiated
 int wr_layer_shape(int cond, int channels, int bottleneck, bool gating, int kernel, int head_out, int flags, int act,
@@ -557,6 +565,8 @@ int wr_layer_shape(int cond, int channels, int bottleneck, bool gating, int kern
 int wr_pair_shape(int n_in, int n_out);
 bool wr_layer_shape_is_exact(int id); // FiLM set, blend and activations compiled in
 int wr_run_shape(int channels, int act);
+unsigned long long wr_hash(const void* data, size_t bytes, unsigned long long h); // FNV-1a, 64 bit (structure keys; start from wr_hash_seed)
+constexpr unsigned long long wr_hash_seed = 1469598103934665603ull;
 // float count / offsets of a layer's weight block (shared by the planner and the kernel)
 struct WrLayerLayout
 {

@@ -533,7 +533,18 @@ int WrShapeSet::pair(int n_in, int n_out)
   pairs.push_back({n_in, n_out});
   return (int)pairs.size() - 1;
 }
-std::string WrShapeSet::header_text() const
+unsigned long long wr_hash(const void* data, size_t bytes, unsigned long long h)
+{
+  const unsigned char* p = static_cast<const unsigned char*>(data);
+  for (size_t i = 0; i < bytes; i++)
+  {
+    h ^= p[i];
+    h *= 1099511628211ull;
+  }
+  return h;
+}
+
+std::string WrShapeSet::header_text(bool mask_scales) const
 {
   // the tables of plan.h, generated: every layer fully described (FiLM set, blend, activation types compiled in)
   std::stringstream ss;
@@ -590,6 +601,8 @@ std::string WrShapeSet::header_text() const
             o = ops[k];
           int32_t scale_bits;
           std::memcpy(&scale_bits, &o.scale, sizeof(scale_bits));
+          if (mask_scales)
+            scale_bits = 0;
           // {type, shape, w, hist, ring, dil, flags, act, act2, n_in, n_out, scale_bits, slot}; a WR_RUN's slot = its first record
           const int32_t slot = o.type == WR_RUN ? programs[i].first_rec + o.pad[0] : o.slot;
           ss << (k ? ", " : "") << "{" << o.type << ", " << o.shape << ", " << o.w << ", " << o.hist << ", " << o.ring << ", " << o.dil << ", "
@@ -753,6 +766,20 @@ static void build_wr_with(const WaveNetSpec& wn, WrPlan& wr, WrBuilder::Policy p
     }
     std::memcpy(&wr.blob[(size_t)wr.tab_ops], wr.ops.data(), wr.ops.size() * sizeof(WrOp));
     wr_program_cuts(wr.ops, wr.tab_rows, wr.split_op);
+    {
+      // WrPlan::structure_key: the walked program without its scales, the int tables behind the weights (rows | pf | ring), the
+      // WR_RUN records, the cuts
+      unsigned long long h = wr_hash_seed;
+      for (WrOp o : wr.ops)
+      {
+        o.scale = 0.0f;
+        h = wr_hash(&o, sizeof(o), h);
+      }
+      h = wr_hash(&wr.blob[(size_t)wr.tab_rows], (size_t)(wr.tab_ops - wr.tab_rows) * sizeof(float), h);
+      if (!wr.run_recs.empty())
+        h = wr_hash(wr.run_recs.data(), wr.run_recs.size() * sizeof(wr.run_recs[0]), h);
+      wr.structure_key = wr_hash(wr.split_op, sizeof(wr.split_op), h);
+    }
     wr.hist_floats = b.hist;
     wr.state_floats = (kWrPosInts + b.hist + 63) / 64 * 64;
     wr.lds_bytes = (hist_base + wr.hist_floats) * 4;

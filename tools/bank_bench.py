@@ -10,7 +10,10 @@ and the case a bank replaces: N captures as N one-stream batches called in turn 
 default: enough to extrapolate per-capture cost, and it keeps memory and session count small).
 Every figure is the median of --runs repetitions (each a fresh timing of --regions regions); one JSON line per case.
 
-    python tools/bank_bench.py [--family a1|a2] [--streams 256] [--runs 7] [--singles 16]
+    python tools/bank_bench.py [--family a1|a2|nano] [--streams 256] [--runs 7] [--singles 16]
+
+--family nano: the nam_wn_reg_kernel family on the official nano size (synth_a1_nano.nam; members from tests/bank_wr_models.py with
+the fixture's head_scale, so every member's per-model code object is the fixture's: one compile, found by hash afterwards).
 
 --family lstm: the LSTM family's two kernels in their bench shapes — one layer of 3 units at 1,024 streams (config 3's shape:
 nam_lstm_row_kernel, four streams per wavefront) and one layer of 24 units at 256 streams (nam_lstm_wide_kernel, one stream
@@ -126,8 +129,9 @@ def main():
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--singles", type=int, default=16)
-    ap.add_argument("--family", choices=["a1", "a2", "lstm"], default="a1",
+    ap.add_argument("--family", choices=["a1", "a2", "nano", "lstm"], default="a1",
                     help="a1: the official topology (nam_a1_q_kernel); a2: the A2 topology (nam_kq_kernel); "
+                         "nano: the official nano size (nam_wn_reg_kernel); "
                          "lstm: nam_lstm_row_kernel / nam_lstm_wide_kernel in their own shapes (--streams is not read)")
     args = ap.parse_args()
     import neuralampmodelercore_amd as nam
@@ -135,10 +139,12 @@ def main():
         return main_lstm(args, nam)
     if args.family == "a2":
         from bank_models import write_a2 as write_standard
+    elif args.family == "nano":
+        from bank_wr_models import write_nano as write_standard
     else:
         from bank_models import write_standard
     n = args.streams
-    std_path = os.path.join(ROOT, "tests", "golden", "models", ("A2" if args.family == "a2" else "wavenet_a1_standard") + ".nam")
+    std_path = os.path.join(ROOT, "tests", "golden", "models", dict(a2="A2", nano="synth_a1_nano").get(args.family, "wavenet_a1_standard") + ".nam")
     std = nam.get_dsp(std_path, fast_tanh=True)
     with tempfile.TemporaryDirectory() as d:
         members = []

@@ -9,9 +9,10 @@ code objects of exactly those models (both tanh modes) into lib/jit/ (or $NAM_HI
 the serving hosts need neither a compiler nor the kernel sources ("Kernel selection")."""
 import glob, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests", "golden")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import neuralampmodelercore_amd as nam
 import make_synthetic_models as msm
+import bank_wr_models
 
 
 def _load(job):
@@ -46,6 +47,12 @@ def main():
             p = os.path.join(tmp, f"featured_{seed}.nam")
             msm.write_featured(p, 7000 + seed, wr_shapes=bool(seed % 2), post_head=seed >= 40)
             jobs.append((p, seed % 3 == 0))
+        # tests/test_bank_wr_abi.py, tests/test_gpu_bank_wr.py: the bank members they write (the same files: the cache key is the
+        # generated header's text — shapes, offsets, head scales —, not the path)
+        written = bank_wr_models.write_all(tmp)
+        for p in written["nano"] + written["cond"] + written["head"] + [written["nano_dil"], written["nano_nobias"]]:
+            for ft in (False, True):
+                jobs.append((p, ft))
         workers = max(1, min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 8))
         with mp.get_context("spawn").Pool(workers) as pool:
             res = pool.map(_load, jobs)
