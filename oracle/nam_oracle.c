@@ -20,8 +20,10 @@
  *
  * Data layout mirrors the reference: matrices are column-major
  * (rows = channels, cols = frames): element (c, f) lives at data[f * C + c].
- * All arithmetic is float32; build with -ffp-contract=off so that every
- * multiply and add is individually rounded (no FMA contraction).
+ * All arithmetic is float32 (orc_real, below; -DORC_REAL_DOUBLE is the float64
+ * evaluation of the same function that the accuracy tests measure float32 against);
+ * build with -ffp-contract=off so that every multiply and add is individually
+ * rounded (no FMA contraction).
  *
  * Each function cites the reference file:line (relative to /root/reference) it
  * follows.
@@ -33,6 +35,32 @@
 #include <string.h>
 
 #define ORC_API __attribute__((visibility("default")))
+
+/* ------------------------------------------------------------------------- */
+/* The real type. The default build is the float32 oracle. -DORC_REAL_DOUBLE  */
+/* evaluates THE SAME FUNCTION in float64: every stored value and intermediate */
+/* is a double, every literal keeps its f suffix (the constants are the        */
+/* float-rounded ones), and whatever comes from the model file — weights,      */
+/* activation parameters, PReLU slopes, head_scale, LSTM initial state —       */
+/* crosses the API as float32 and is widened, never re-read at more digits.    */
+/* Lookup tables are built in float32 in both builds (they are data of the     */
+/* function, FastLUTActivation stores floats). What comes out is the           */
+/* exact-arithmetic value the float32 build and the kernels approximate.       */
+/* Audio in / out is orc_real.                                                 */
+/* ------------------------------------------------------------------------- */
+#ifdef ORC_REAL_DOUBLE
+typedef double orc_real;
+#define ORC_TANH tanh
+#define ORC_EXP exp
+#define ORC_EXP2 exp2
+#define ORC_FABS fabs
+#else
+typedef float orc_real;
+#define ORC_TANH tanhf
+#define ORC_EXP expf
+#define ORC_EXP2 exp2f
+#define ORC_FABS fabsf
+#endif
 
 /* ------------------------------------------------------------------------- */
 /* Activations — NAM/activations.h:59-133 (scalar fns), :182-369 (classes)    */
@@ -59,62 +87,78 @@ enum
 typedef struct
 {
   int type;
-  float p[4]; /* LeakyReLU: p[0]=slope; LeakyHardtanh: min_val,max_val,min_slope,max_slope */
+  orc_real p[4]; /* LeakyReLU: p[0]=slope; LeakyHardtanh: min_val,max_val,min_slope,max_slope */
   int n_slopes; /* PReLU */
-  float slopes[ORC_MAX_SLOPES];
+  orc_real slopes[ORC_MAX_SLOPES];
   /* ORC_ACT_LUT: p[0] = min_x, p[1] = max_x, p[2] = base function (TANH / SIGMOID / SILU), p[3] = n points */
-  float lut_step, lut_inv_step;
+  orc_real lut_step, lut_inv_step;
   int lut_n;
-  float* lut; /* owned by the process (test infrastructure: never freed) */
+  orc_real* lut; /* owned by the process (test infrastructure: never freed) */
 } orc_act;
 
 /* activations.h:91-98 */
-static inline float orc_fast_tanh(const float x)
+static inline orc_real orc_fast_tanh(const orc_real x)
 {
-  const float ax = fabsf(x);
-  const float x2 = x * x;
+  const orc_real ax = ORC_FABS(x);
+  const orc_real x2 = x * x;
   return (x * (2.45550750702956f + 2.45550750702956f * ax + (0.893229853513558f + 0.821226666969744f * ax) * x2)
-          / (2.44506634652299f + (2.44506634652299f + x2) * fabsf(x + 0.814642734961073f * x * ax)));
+          / (2.44506634652299f + (2.44506634652299f + x2) * ORC_FABS(x + 0.814642734961073f * x * ax)));
 }
 /* activations.h:100-103 */
-static inline float orc_fast_sigmoid(const float x)
+static inline orc_real orc_fast_sigmoid(const orc_real x)
 {
   return 0.5f * (orc_fast_tanh(x * 0.5f) + 1.0f);
 }
-/* activations.h:64-67 */
-static inline float orc_sigmoid(float x)
+/* -DORC_EXP2_FORMS: tanh and sigmoid in the form the HIP kernels document (neuralampmodelercore_amd/csrc/device_common.h: tanh_hw, sigmoid_hw) —
+ * 1 - 2 / (exp2(x * 2 log2 e) + 1) and 1 / (1 + exp2(-log2 e * x)), every operation correctly rounded, libm's exp2 where
+ * the device has its exp2 unit. The float32 build with this macro is the yardstick of the libm-mode GPU cases whose error
+ * is the form's (absolute ~6e-8 near 0, where tanhf's is relative), never the GPU's own; see profiles/accuracy/README.md. */
+static inline orc_real orc_tanh(orc_real x)
 {
-  return 1.0f / (1.0f + expf(-x));
+#ifdef ORC_EXP2_FORMS
+  return 1.0f - 2.0f / (ORC_EXP2(x * 2.885390081777927f) + 1.0f);
+#else
+  return ORC_TANH(x); /* std::tanh(float) activations.h:188 */
+#endif
+}
+/* activations.h:64-67 */
+static inline orc_real orc_sigmoid(orc_real x)
+{
+#ifdef ORC_EXP2_FORMS
+  return 1.0f / (1.0f + ORC_EXP2(-1.4426950408889634f * x));
+#else
+  return 1.0f / (1.0f + ORC_EXP(-x));
+#endif
 }
 /* activations.h:105-108 */
-static inline float orc_leaky_relu(float x, float ns)
+static inline orc_real orc_leaky_relu(orc_real x, orc_real ns)
 {
   return x > 0.0f ? x : ns * x;
 }
 
 /* FastLUTActivation::lookup, activations.h:391-409 */
-static inline float orc_lut_lookup(const orc_act* a, float x)
+static inline orc_real orc_lut_lookup(const orc_act* a, orc_real x)
 {
-  const float min_x = a->p[0], max_x = a->p[1];
+  const orc_real min_x = a->p[0], max_x = a->p[1];
   x = x < min_x ? min_x : (x > max_x ? max_x : x);
-  const float f_idx = (x - min_x) * a->lut_inv_step;
+  const orc_real f_idx = (x - min_x) * a->lut_inv_step;
   const size_t i = (size_t)f_idx;
   if (i >= (size_t)a->lut_n - 1)
     return a->lut[a->lut_n - 1];
-  const float frac = f_idx - (float)i;
+  const orc_real frac = f_idx - (orc_real)i;
   return a->lut[i] + (a->lut[i + 1] - a->lut[i]) * frac;
 }
 
-static inline float orc_act_scalar(const orc_act* a, float x, float slope)
+static inline orc_real orc_act_scalar(const orc_act* a, orc_real x, orc_real slope)
 {
   switch (a->type)
   {
     case ORC_ACT_LUT: return orc_lut_lookup(a, x);
     case ORC_ACT_IDENTITY: return x;
-    case ORC_ACT_TANH: return tanhf(x); /* std::tanh(float) activations.h:188 */
+    case ORC_ACT_TANH: return orc_tanh(x);
     case ORC_ACT_HARDTANH: /* activations.h:69-73 */
     {
-      const float t = x < -1 ? -1 : x;
+      const orc_real t = x < -1 ? -1 : x;
       return t > 1 ? 1 : t;
     }
     case ORC_ACT_FASTTANH: return orc_fast_tanh(x);
@@ -125,46 +169,46 @@ static inline float orc_act_scalar(const orc_act* a, float x, float slope)
     case ORC_ACT_SILU: return x * orc_sigmoid(x); /* activations.h:115-118 */
     case ORC_ACT_HARDSWISH: /* activations.h:120-128 */
     {
-      const float t = x + 3.0f;
-      const float clamped = t < 0.0f ? 0.0f : (t > 6.0f ? 6.0f : t);
+      const orc_real t = x + 3.0f;
+      const orc_real clamped = t < 0.0f ? 0.0f : (t > 6.0f ? 6.0f : t);
       return x * clamped * (1.0f / 6.0f);
     }
     case ORC_ACT_LEAKYHARDTANH: /* activations.h:75-89 */
     {
-      const float min_val = a->p[0], max_val = a->p[1], min_slope = a->p[2], max_slope = a->p[3];
+      const orc_real min_val = a->p[0], max_val = a->p[1], min_slope = a->p[2], max_slope = a->p[3];
       if (x < min_val)
         return (x - min_val) * min_slope + min_val;
       else if (x > max_val)
         return (x - max_val) * max_slope + max_val;
       return x;
     }
-    case ORC_ACT_SOFTSIGN: return x / (1.0f + fabsf(x)); /* activations.h:130-133 */
+    case ORC_ACT_SOFTSIGN: return x / (1.0f + ORC_FABS(x)); /* activations.h:130-133 */
   }
   return x;
 }
 
-/* Activation::apply(float* data, long size) — flat; PReLU indexes pos % n_slopes
+/* Activation::apply(orc_real* data, long size) — flat; PReLU indexes pos % n_slopes
  * on column-major data (activations.h:283-297). */
-static void orc_act_apply_flat(const orc_act* a, float* data, long size)
+static void orc_act_apply_flat(const orc_act* a, orc_real* data, long size)
 {
   if (a->type == ORC_ACT_IDENTITY)
     return;
   for (long pos = 0; pos < size; pos++)
   {
-    const float slope = (a->type == ORC_ACT_PRELU) ? a->slopes[pos % a->n_slopes] : 0.0f;
+    const orc_real slope = (a->type == ORC_ACT_PRELU) ? a->slopes[pos % a->n_slopes] : 0.0f;
     data[pos] = orc_act_scalar(a, data[pos], slope);
   }
 }
 
 /* Activation::apply(MatrixXf&) on a (rows x 1) column, as used by the gating /
  * blending activations: PReLU uses slopes[row] (activations.h:299-322). */
-static void orc_act_apply_column(const orc_act* a, float* col, int rows)
+static void orc_act_apply_column(const orc_act* a, orc_real* col, int rows)
 {
   if (a->type == ORC_ACT_IDENTITY)
     return;
   for (int r = 0; r < rows; r++)
   {
-    const float slope = (a->type == ORC_ACT_PRELU) ? a->slopes[r % a->n_slopes] : 0.0f;
+    const orc_real slope = (a->type == ORC_ACT_PRELU) ? a->slopes[r % a->n_slopes] : 0.0f;
     col[r] = orc_act_scalar(a, col[r], slope);
   }
 }
@@ -216,23 +260,23 @@ static void orc_arena_free(orc_arena* ar)
 /* accumulate != 0 adds the finished product to Y (per-tap "out += W[k] * in").       */
 /* ------------------------------------------------------------------------- */
 #define ORC_GEMM_FIXED(N)                                                                                   \
-  static void orc_gemm_##N(const float* restrict wt, const float* restrict x, int x_stride, int in_ch,       \
-                           int n_frames, float* restrict y, int accumulate)                                 \
+  static void orc_gemm_##N(const orc_real* restrict wt, const orc_real* restrict x, int x_stride, int in_ch,       \
+                           int n_frames, orc_real* restrict y, int accumulate)                                 \
   {                                                                                                         \
     int f = 0;                                                                                              \
     for (; f + 4 <= n_frames; f += 4)                                                                       \
     {                                                                                                       \
-      float a0[N], a1[N], a2[N], a3[N];                                                                     \
+      orc_real a0[N], a1[N], a2[N], a3[N];                                                                     \
       for (int o = 0; o < N; o++)                                                                           \
         a0[o] = a1[o] = a2[o] = a3[o] = 0.0f;                                                               \
-      const float* x0 = x + (size_t)f * x_stride;                                                           \
-      const float* x1 = x0 + x_stride;                                                                      \
-      const float* x2 = x1 + x_stride;                                                                      \
-      const float* x3 = x2 + x_stride;                                                                      \
+      const orc_real* x0 = x + (size_t)f * x_stride;                                                           \
+      const orc_real* x1 = x0 + x_stride;                                                                      \
+      const orc_real* x2 = x1 + x_stride;                                                                      \
+      const orc_real* x3 = x2 + x_stride;                                                                      \
       for (int i = 0; i < in_ch; i++)                                                                       \
       {                                                                                                     \
-        const float* restrict wc = wt + (size_t)i * N;                                                      \
-        const float v0 = x0[i], v1 = x1[i], v2 = x2[i], v3 = x3[i];                                         \
+        const orc_real* restrict wc = wt + (size_t)i * N;                                                      \
+        const orc_real v0 = x0[i], v1 = x1[i], v2 = x2[i], v3 = x3[i];                                         \
         for (int o = 0; o < N; o++)                                                                         \
         {                                                                                                   \
           a0[o] += wc[o] * v0;                                                                              \
@@ -241,7 +285,7 @@ static void orc_arena_free(orc_arena* ar)
           a3[o] += wc[o] * v3;                                                                              \
         }                                                                                                   \
       }                                                                                                     \
-      float* y0 = y + (size_t)f * N;                                                                        \
+      orc_real* y0 = y + (size_t)f * N;                                                                        \
       if (accumulate)                                                                                       \
         for (int o = 0; o < N; o++)                                                                         \
         {                                                                                                   \
@@ -261,18 +305,18 @@ static void orc_arena_free(orc_arena* ar)
     }                                                                                                       \
     for (; f < n_frames; f++)                                                                               \
     {                                                                                                       \
-      float a0[N];                                                                                          \
+      orc_real a0[N];                                                                                          \
       for (int o = 0; o < N; o++)                                                                           \
         a0[o] = 0.0f;                                                                                       \
-      const float* x0 = x + (size_t)f * x_stride;                                                           \
+      const orc_real* x0 = x + (size_t)f * x_stride;                                                           \
       for (int i = 0; i < in_ch; i++)                                                                       \
       {                                                                                                     \
-        const float* restrict wc = wt + (size_t)i * N;                                                      \
-        const float v0 = x0[i];                                                                             \
+        const orc_real* restrict wc = wt + (size_t)i * N;                                                      \
+        const orc_real v0 = x0[i];                                                                             \
         for (int o = 0; o < N; o++)                                                                         \
           a0[o] += wc[o] * v0;                                                                              \
       }                                                                                                     \
-      float* y0 = y + (size_t)f * N;                                                                        \
+      orc_real* y0 = y + (size_t)f * N;                                                                        \
       for (int o = 0; o < N; o++)                                                                           \
         y0[o] = accumulate ? y0[o] + a0[o] : a0[o];                                                         \
     }                                                                                                       \
@@ -286,8 +330,8 @@ ORC_GEMM_FIXED(8)
 ORC_GEMM_FIXED(12)
 ORC_GEMM_FIXED(16)
 
-static void orc_gemm(const float* restrict wt, const float* restrict x, int x_stride, int in_ch, int oc, int n_frames,
-                     float* restrict y, int accumulate)
+static void orc_gemm(const orc_real* restrict wt, const orc_real* restrict x, int x_stride, int in_ch, int oc, int n_frames,
+                     orc_real* restrict y, int accumulate)
 {
   switch (oc)
   {
@@ -303,11 +347,11 @@ static void orc_gemm(const float* restrict wt, const float* restrict x, int x_st
   }
   for (int f = 0; f < n_frames; f++)
   {
-    const float* x0 = x + (size_t)f * x_stride;
-    float* y0 = y + (size_t)f * oc;
+    const orc_real* x0 = x + (size_t)f * x_stride;
+    orc_real* y0 = y + (size_t)f * oc;
     for (int o = 0; o < oc; o++)
     {
-      float sum = 0.0f;
+      orc_real sum = 0.0f;
       for (int i = 0; i < in_ch; i++)
         sum += wt[(size_t)i * oc + o] * x0[i];
       y0[o] = accumulate ? y0[o] + sum : sum;
@@ -321,10 +365,10 @@ static void orc_gemm(const float* restrict wt, const float* restrict x, int x_st
 typedef struct
 {
   int in_ch, out_ch, groups, has_bias;
-  float* w; /* dense [out][in] row-major; block-diagonal for grouped */
-  float* wt; /* the same matrix stored [in][out] (so the per-frame update vectorises over outputs) */
-  float* bias;
-  float* out; /* [out_ch x max_buf] column-major */
+  orc_real* w; /* dense [out][in] row-major; block-diagonal for grouped */
+  orc_real* wt; /* the same matrix stored [in][out] (so the per-frame update vectorises over outputs) */
+  orc_real* bias;
+  orc_real* out; /* [out_ch x max_buf] column-major */
 } orc_conv1x1;
 
 static void orc_conv1x1_init(orc_arena* ar, orc_conv1x1* c, int in_ch, int out_ch, int has_bias, int groups)
@@ -333,9 +377,9 @@ static void orc_conv1x1_init(orc_arena* ar, orc_conv1x1* c, int in_ch, int out_c
   c->out_ch = out_ch;
   c->groups = groups;
   c->has_bias = has_bias;
-  c->w = (float*)orc_alloc(ar, sizeof(float) * (size_t)in_ch * out_ch);
-  c->wt = (float*)orc_alloc(ar, sizeof(float) * (size_t)in_ch * out_ch);
-  c->bias = has_bias ? (float*)orc_alloc(ar, sizeof(float) * out_ch) : NULL;
+  c->w = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)in_ch * out_ch);
+  c->wt = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)in_ch * out_ch);
+  c->bias = has_bias ? (orc_real*)orc_alloc(ar, sizeof(orc_real) * out_ch) : NULL;
   c->out = NULL;
 }
 
@@ -349,7 +393,7 @@ static long orc_conv1x1_num_weights(const orc_conv1x1* c)
 static const float* orc_conv1x1_set_weights(orc_conv1x1* c, const float* w)
 {
   const int opg = c->out_ch / c->groups, ipg = c->in_ch / c->groups;
-  memset(c->w, 0, sizeof(float) * (size_t)c->in_ch * c->out_ch);
+  memset(c->w, 0, sizeof(orc_real) * (size_t)c->in_ch * c->out_ch);
   for (int g = 0; g < c->groups; g++)
     for (int i = 0; i < opg; i++)
       for (int j = 0; j < ipg; j++)
@@ -365,18 +409,18 @@ static const float* orc_conv1x1_set_weights(orc_conv1x1* c, const float* w)
 
 static void orc_conv1x1_set_max_buffer(orc_arena* ar, orc_conv1x1* c, int max_buf)
 {
-  c->out = (float*)orc_alloc(ar, sizeof(float) * (size_t)c->out_ch * max_buf);
+  c->out = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)c->out_ch * max_buf);
 }
 
 /* dsp.cpp:436-449,770-836 (Eigen path): out = W * in (+ bias column-wise).
  * `in` is column-major with column stride in_stride (>= in_ch). */
-static void orc_conv1x1_process(orc_conv1x1* c, const float* in, int in_stride, int num_frames)
+static void orc_conv1x1_process(orc_conv1x1* c, const orc_real* in, int in_stride, int num_frames)
 {
   orc_gemm(c->wt, in, in_stride, c->in_ch, c->out_ch, num_frames, c->out, 0);
   if (c->has_bias)
     for (int f = 0; f < num_frames; f++)
     {
-      float* y = c->out + (size_t)f * c->out_ch;
+      orc_real* y = c->out + (size_t)f * c->out_ch;
       for (int o = 0; o < c->out_ch; o++)
         y[o] += c->bias[o];
     }
@@ -392,7 +436,7 @@ typedef struct
   long max_lookback;
   long write_pos;
   int max_buf;
-  float* storage; /* [channels x cols] column-major */
+  orc_real* storage; /* [channels x cols] column-major */
 } orc_ring;
 
 /* ring_buffer.cpp:7-27 */
@@ -402,7 +446,7 @@ static void orc_ring_reset(orc_arena* ar, orc_ring* r, int channels, long max_lo
   r->max_lookback = max_lookback;
   r->max_buf = max_buf;
   r->cols = 2 * max_lookback + max_buf;
-  r->storage = (float*)orc_alloc(ar, sizeof(float) * (size_t)channels * r->cols); /* zeroed */
+  r->storage = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)channels * r->cols); /* zeroed */
   r->write_pos = max_lookback;
 }
 
@@ -416,25 +460,25 @@ static void orc_ring_rewind(orc_ring* r)
   }
   const long copy_start = r->write_pos - r->max_lookback;
   memmove(r->storage, r->storage + (size_t)copy_start * r->channels,
-          sizeof(float) * (size_t)r->max_lookback * r->channels);
+          sizeof(orc_real) * (size_t)r->max_lookback * r->channels);
   r->write_pos = r->max_lookback;
 }
 
 /* ring_buffer.cpp:29-42 */
-static void orc_ring_write(orc_ring* r, const float* in, int in_stride, int num_frames)
+static void orc_ring_write(orc_ring* r, const orc_real* in, int in_stride, int num_frames)
 {
   if (r->write_pos + num_frames > r->cols)
     orc_ring_rewind(r);
   if (in_stride == r->channels)
-    memcpy(r->storage + (size_t)r->write_pos * r->channels, in, sizeof(float) * (size_t)num_frames * r->channels);
+    memcpy(r->storage + (size_t)r->write_pos * r->channels, in, sizeof(orc_real) * (size_t)num_frames * r->channels);
   else
     for (int f = 0; f < num_frames; f++)
       memcpy(r->storage + (size_t)(r->write_pos + f) * r->channels, in + (size_t)f * in_stride,
-             sizeof(float) * r->channels);
+             sizeof(orc_real) * r->channels);
 }
 
 /* ring_buffer.cpp:44-57 */
-static const float* orc_ring_read(const orc_ring* r, long lookback)
+static const orc_real* orc_ring_read(const orc_ring* r, long lookback)
 {
   return r->storage + (size_t)(r->write_pos - lookback) * r->channels;
 }
@@ -446,12 +490,12 @@ static const float* orc_ring_read(const orc_ring* r, long lookback)
 typedef struct
 {
   int in_ch, out_ch, K, dilation, groups, has_bias;
-  float* w; /* dense [K][out][in] */
-  float* wt; /* dense [K][in][out] */
-  float* bias;
+  orc_real* w; /* dense [K][out][in] */
+  orc_real* wt; /* dense [K][in][out] */
+  orc_real* bias;
   orc_ring ring;
-  float* out; /* [out_ch x max_buf] */
-  float* cached_col; /* in_ch */
+  orc_real* out; /* [out_ch x max_buf] */
+  orc_real* cached_col; /* in_ch */
   int has_cached;
 } orc_conv1d;
 
@@ -465,10 +509,10 @@ static void orc_conv1d_init(orc_arena* ar, orc_conv1d* c, int in_ch, int out_ch,
   c->dilation = dilation;
   c->groups = groups;
   c->has_bias = has_bias;
-  c->w = (float*)orc_alloc(ar, sizeof(float) * (size_t)K * in_ch * out_ch);
-  c->wt = (float*)orc_alloc(ar, sizeof(float) * (size_t)K * in_ch * out_ch);
-  c->bias = has_bias ? (float*)orc_alloc(ar, sizeof(float) * out_ch) : NULL;
-  c->cached_col = (float*)orc_alloc(ar, sizeof(float) * in_ch);
+  c->w = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)K * in_ch * out_ch);
+  c->wt = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)K * in_ch * out_ch);
+  c->bias = has_bias ? (orc_real*)orc_alloc(ar, sizeof(orc_real) * out_ch) : NULL;
+  c->cached_col = (orc_real*)orc_alloc(ar, sizeof(orc_real) * in_ch);
 }
 
 static long orc_conv1d_num_weights(const orc_conv1d* c)
@@ -480,7 +524,7 @@ static long orc_conv1d_num_weights(const orc_conv1d* c)
 static const float* orc_conv1d_set_weights(orc_conv1d* c, const float* w)
 {
   const int opg = c->out_ch / c->groups, ipg = c->in_ch / c->groups;
-  memset(c->w, 0, sizeof(float) * (size_t)c->K * c->in_ch * c->out_ch);
+  memset(c->w, 0, sizeof(orc_real) * (size_t)c->K * c->in_ch * c->out_ch);
   c->has_cached = 0;
   for (int g = 0; g < c->groups; g++)
     for (int i = 0; i < opg; i++)
@@ -502,19 +546,19 @@ static void orc_conv1d_set_max_buffer(orc_arena* ar, orc_conv1d* c, int max_buf)
 {
   const long rf = c->K > 0 ? (long)(c->K - 1) * c->dilation : 0;
   orc_ring_reset(ar, &c->ring, c->in_ch, rf, max_buf);
-  c->out = (float*)orc_alloc(ar, sizeof(float) * (size_t)c->out_ch * max_buf);
+  c->out = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)c->out_ch * max_buf);
 }
 
 /* conv1d.cpp:163-183, 666-685, 768-775 */
-static void orc_conv1d_process(orc_conv1d* c, const float* in, int in_stride, int num_frames)
+static void orc_conv1d_process(orc_conv1d* c, const orc_real* in, int in_stride, int num_frames)
 {
   orc_ring_write(&c->ring, in, in_stride, num_frames);
   /* out = 0; for each tap k: out += W[k] * ring.Read(n, lookback_k) — conv1d.cpp:672-682 */
   for (int k = 0; k < c->K; k++)
   {
     const long lookback = (long)c->dilation * (c->K - 1 - k);
-    const float* blk = orc_ring_read(&c->ring, lookback);
-    const float* wk = c->wt + (size_t)k * c->out_ch * c->in_ch;
+    const orc_real* blk = orc_ring_read(&c->ring, lookback);
+    const orc_real* wk = c->wt + (size_t)k * c->out_ch * c->in_ch;
     if (k == 0)
     {
       /* 0 + (W[0] x) == W[0] x exactly, so the first tap can store instead of accumulate */
@@ -524,11 +568,11 @@ static void orc_conv1d_process(orc_conv1d* c, const float* in, int in_stride, in
       orc_gemm(wk, blk, c->in_ch, c->in_ch, c->out_ch, num_frames, c->out, 1);
   }
   if (c->K == 0)
-    memset(c->out, 0, sizeof(float) * (size_t)c->out_ch * num_frames);
+    memset(c->out, 0, sizeof(orc_real) * (size_t)c->out_ch * num_frames);
   if (c->has_bias)
     for (int f = 0; f < num_frames; f++)
     {
-      float* y = c->out + (size_t)f * c->out_ch;
+      orc_real* y = c->out + (size_t)f * c->out_ch;
       for (int o = 0; o < c->out_ch; o++)
         y[o] += c->bias[o];
     }
@@ -538,7 +582,7 @@ static void orc_conv1d_process(orc_conv1d* c, const float* in, int in_stride, in
 /* conv1d.cpp:157-161 + ring_buffer.cpp:64-69 */
 static void orc_conv1d_cache_prewarm(orc_conv1d* c)
 {
-  memcpy(c->cached_col, c->ring.storage + (size_t)(c->ring.write_pos - 1) * c->in_ch, sizeof(float) * c->in_ch);
+  memcpy(c->cached_col, c->ring.storage + (size_t)(c->ring.write_pos - 1) * c->in_ch, sizeof(orc_real) * c->in_ch);
   c->has_cached = 1;
 }
 
@@ -546,7 +590,7 @@ static void orc_conv1d_cache_prewarm(orc_conv1d* c)
 static void orc_conv1d_prewarm_from_cache(orc_conv1d* c)
 {
   for (long col = 0; col < c->ring.cols; col++)
-    memcpy(c->ring.storage + (size_t)col * c->in_ch, c->cached_col, sizeof(float) * c->in_ch);
+    memcpy(c->ring.storage + (size_t)col * c->in_ch, c->cached_col, sizeof(orc_real) * c->in_ch);
   c->ring.write_pos = c->ring.max_lookback;
 }
 
@@ -557,7 +601,7 @@ typedef struct
 {
   int active, do_shift, input_dim;
   orc_conv1x1 css; /* cond -> (shift?2:1)*input_dim, bias */
-  float* out; /* [input_dim x max_buf] */
+  orc_real* out; /* [input_dim x max_buf] */
 } orc_film;
 
 static void orc_film_init(orc_arena* ar, orc_film* f, int active, int cond_dim, int input_dim, int shift, int groups)
@@ -572,7 +616,7 @@ static void orc_film_init(orc_arena* ar, orc_film* f, int active, int cond_dim, 
 }
 
 /* film.h:76-190: out = in * scale (+ shift); scale = top rows, shift = bottom rows */
-static void orc_film_process(orc_film* fl, const float* in, int in_stride, const float* cond, int cond_stride,
+static void orc_film_process(orc_film* fl, const orc_real* in, int in_stride, const orc_real* cond, int cond_stride,
                              int num_frames)
 {
   orc_conv1x1_process(&fl->css, cond, cond_stride, num_frames);
@@ -580,9 +624,9 @@ static void orc_film_process(orc_film* fl, const float* in, int in_stride, const
   const int ss_rows = fl->css.out_ch;
   for (int f = 0; f < num_frames; f++)
   {
-    const float* x = in + (size_t)f * in_stride;
-    const float* sc = fl->css.out + (size_t)f * ss_rows;
-    float* y = fl->out + (size_t)f * D;
+    const orc_real* x = in + (size_t)f * in_stride;
+    const orc_real* sc = fl->css.out + (size_t)f * ss_rows;
+    orc_real* y = fl->out + (size_t)f * D;
     if (fl->do_shift)
       for (int i = 0; i < D; i++)
         y[i] = x[i] * sc[i] + sc[D + i];
@@ -593,12 +637,12 @@ static void orc_film_process(orc_film* fl, const float* in, int in_stride, const
 }
 
 /* film.h:199-204: in-place variant (copy result back into `io`) */
-static void orc_film_process_inplace(orc_film* fl, float* io, int io_stride, const float* cond, int cond_stride,
+static void orc_film_process_inplace(orc_film* fl, orc_real* io, int io_stride, const orc_real* cond, int cond_stride,
                                      int num_frames)
 {
   orc_film_process(fl, io, io_stride, cond, cond_stride, num_frames);
   for (int f = 0; f < num_frames; f++)
-    memcpy(io + (size_t)f * io_stride, fl->out + (size_t)f * fl->input_dim, sizeof(float) * fl->input_dim);
+    memcpy(io + (size_t)f * io_stride, fl->out + (size_t)f * fl->input_dim, sizeof(orc_real) * fl->input_dim);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -634,9 +678,9 @@ typedef struct
   orc_conv1x1 head1x1;
   orc_act act, act2;
   orc_film film[FILM_COUNT];
-  float* z; /* [zc x max_buf] */
-  float* out_next; /* [channels x max_buf] */
-  float* out_head; /* [head_out x max_buf] */
+  orc_real* z; /* [zc x max_buf] */
+  orc_real* out_next; /* [channels x max_buf] */
+  orc_real* out_head; /* [head_out x max_buf] */
   int head_out_ch;
   int zc;
 } orc_layer;
@@ -652,8 +696,8 @@ typedef struct
   orc_conv1x1 rechannel;
   orc_conv1d head_rechannel;
   int head_output_size;
-  float* layer_outputs; /* [channels x max_buf] */
-  float* head_inputs; /* [head_output_size x max_buf] */
+  orc_real* layer_outputs; /* [channels x max_buf] */
+  orc_real* head_inputs; /* [head_output_size x max_buf] */
 } orc_array;
 
 #define ORC_MAX_ARRAYS 16
@@ -666,19 +710,19 @@ typedef struct orc_wavenet
   int in_channels, out_channels;
   int n_arrays;
   orc_array arrays[ORC_MAX_ARRAYS];
-  float head_scale;
+  orc_real head_scale;
   struct orc_wavenet* condition_dsp; /* owned */
   /* post-stack head — model.cpp:21-103 */
   int with_head, head_n;
   orc_conv1d head_convs[ORC_MAX_HEAD_CONVS];
   orc_act head_act;
-  float* scaled_head;
+  orc_real* scaled_head;
   int max_buf;
   int prewarm_samples;
   int finalized;
-  float* cond_in; /* [in_channels x max_buf] */
-  float* cond_out; /* [cond_dim x max_buf] */
-  float* tmp_io; /* scratch for nested process */
+  orc_real* cond_in; /* [in_channels x max_buf] */
+  orc_real* cond_out; /* [cond_dim x max_buf] */
+  orc_real* tmp_io; /* scratch for nested process */
 } orc_wavenet;
 
 static void orc_layer_build(orc_arena* ar, orc_layer* L, const orc_array* A, int kernel, int dilation,
@@ -750,28 +794,28 @@ static void orc_layer_set_max_buffer(orc_arena* ar, orc_layer* L, int max_buf)
 {
   orc_conv1d_set_max_buffer(ar, &L->conv, max_buf);
   orc_conv1x1_set_max_buffer(ar, &L->mixin, max_buf);
-  L->z = (float*)orc_alloc(ar, sizeof(float) * (size_t)L->zc * max_buf);
+  L->z = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)L->zc * max_buf);
   if (L->has_layer1x1)
     orc_conv1x1_set_max_buffer(ar, &L->layer1x1, max_buf);
-  L->out_next = (float*)orc_alloc(ar, sizeof(float) * (size_t)L->channels * max_buf);
-  L->out_head = (float*)orc_alloc(ar, sizeof(float) * (size_t)L->head_out_ch * max_buf);
+  L->out_next = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)L->channels * max_buf);
+  L->out_head = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)L->head_out_ch * max_buf);
   if (L->has_head1x1)
     orc_conv1x1_set_max_buffer(ar, &L->head1x1, max_buf);
   for (int i = 0; i < FILM_COUNT; i++)
     if (L->film[i].active)
     {
       orc_conv1x1_set_max_buffer(ar, &L->film[i].css, max_buf);
-      L->film[i].out = (float*)orc_alloc(ar, sizeof(float) * (size_t)L->film[i].input_dim * max_buf);
+      L->film[i].out = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)L->film[i].input_dim * max_buf);
     }
 }
 
 /* gating_activations.h:59-114 (GatingActivation::apply) */
-static void orc_gating_apply(const orc_layer* L, float* z, int zc, int B, int num_frames)
+static void orc_gating_apply(const orc_layer* L, orc_real* z, int zc, int B, int num_frames)
 {
-  float a[256], g[256];
+  orc_real a[256], g[256];
   for (int f = 0; f < num_frames; f++)
   {
-    float* col = z + (size_t)f * zc;
+    orc_real* col = z + (size_t)f * zc;
     for (int c = 0; c < B; c++)
     {
       a[c] = col[c];
@@ -785,12 +829,12 @@ static void orc_gating_apply(const orc_layer* L, float* z, int zc, int B, int nu
 }
 
 /* gating_activations.h:165-228 (BlendingActivation::apply) */
-static void orc_blending_apply(const orc_layer* L, float* z, int zc, int B, int num_frames)
+static void orc_blending_apply(const orc_layer* L, orc_real* z, int zc, int B, int num_frames)
 {
-  float pre[256], a[256], bl[256];
+  orc_real pre[256], a[256], bl[256];
   for (int f = 0; f < num_frames; f++)
   {
-    float* col = z + (size_t)f * zc;
+    orc_real* col = z + (size_t)f * zc;
     for (int c = 0; c < B; c++)
     {
       pre[c] = col[c];
@@ -801,14 +845,14 @@ static void orc_blending_apply(const orc_layer* L, float* z, int zc, int B, int 
     orc_act_apply_column(&L->act2, bl, B);
     for (int c = 0; c < B; c++)
     {
-      const float alpha = bl[c];
+      const orc_real alpha = bl[c];
       col[c] = alpha * a[c] + (1.0f - alpha) * pre[c];
     }
   }
 }
 
 /* model.cpp:183-393 */
-static void orc_layer_process(orc_layer* L, const float* input, const float* cond, int n)
+static void orc_layer_process(orc_layer* L, const orc_real* input, const orc_real* cond, int n)
 {
   const int C = L->channels, B = L->bottleneck, zc = L->zc, cs = L->cond_size;
   /* Step 1: input convolution (+ pre/post FiLM) — model.cpp:189-203 */
@@ -869,12 +913,12 @@ static void orc_layer_process(orc_layer* L, const float* input, const float* con
     orc_conv1x1_process(&L->head1x1, L->z, zc, n);
     if (L->film[FILM_HEAD1X1_POST].active)
       orc_film_process_inplace(&L->film[FILM_HEAD1X1_POST], L->head1x1.out, L->head_out_ch, cond, cs, n);
-    memcpy(L->out_head, L->head1x1.out, sizeof(float) * (size_t)L->head_out_ch * n);
+    memcpy(L->out_head, L->head1x1.out, sizeof(orc_real) * (size_t)L->head_out_ch * n);
   }
   else
   {
     for (int f = 0; f < n; f++)
-      memcpy(L->out_head + (size_t)f * B, L->z + (size_t)f * zc, sizeof(float) * B);
+      memcpy(L->out_head + (size_t)f * B, L->z + (size_t)f * zc, sizeof(orc_real) * B);
   }
 
   /* residual — model.cpp:354-392 */
@@ -882,7 +926,7 @@ static void orc_layer_process(orc_layer* L, const float* input, const float* con
     for (long i = 0; i < (long)C * n; i++)
       L->out_next[i] = input[i] + L->layer1x1.out[i];
   else
-    memcpy(L->out_next, input, sizeof(float) * (size_t)C * n);
+    memcpy(L->out_next, input, sizeof(orc_real) * (size_t)C * n);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -894,8 +938,8 @@ static void orc_array_set_max_buffer(orc_arena* ar, orc_array* A, int max_buf)
   orc_conv1d_set_max_buffer(ar, &A->head_rechannel, max_buf);
   for (int i = 0; i < A->n_layers; i++)
     orc_layer_set_max_buffer(ar, &A->layers[i], max_buf);
-  A->layer_outputs = (float*)orc_alloc(ar, sizeof(float) * (size_t)A->channels * max_buf);
-  A->head_inputs = (float*)orc_alloc(ar, sizeof(float) * (size_t)A->head_output_size * max_buf);
+  A->layer_outputs = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)A->channels * max_buf);
+  A->head_inputs = (orc_real*)orc_alloc(ar, sizeof(orc_real) * (size_t)A->head_output_size * max_buf);
 }
 
 /* model.cpp:433-440 */
@@ -909,15 +953,15 @@ static long orc_array_receptive_field(const orc_array* A)
 }
 
 /* model.cpp:463-549. head_in == NULL -> zero the accumulator (first array). */
-static void orc_array_process(orc_array* A, const float* layer_inputs, const float* cond, const float* head_in, int n)
+static void orc_array_process(orc_array* A, const orc_real* layer_inputs, const orc_real* cond, const orc_real* head_in, int n)
 {
   const size_t hn = (size_t)A->head_output_size * n;
   if (head_in == NULL)
-    memset(A->head_inputs, 0, sizeof(float) * hn);
+    memset(A->head_inputs, 0, sizeof(orc_real) * hn);
   else
-    memcpy(A->head_inputs, head_in, sizeof(float) * hn);
+    memcpy(A->head_inputs, head_in, sizeof(orc_real) * hn);
   orc_conv1x1_process(&A->rechannel, layer_inputs, A->input_size, n);
-  const float* x = A->rechannel.out;
+  const orc_real* x = A->rechannel.out;
   for (int i = 0; i < A->n_layers; i++)
   {
     orc_layer_process(&A->layers[i], x, cond, n);
@@ -925,7 +969,7 @@ static void orc_array_process(orc_array* A, const float* layer_inputs, const flo
       A->head_inputs[j] += A->layers[i].out_head[j];
     x = A->layers[i].out_next;
   }
-  memcpy(A->layer_outputs, x, sizeof(float) * (size_t)A->channels * n);
+  memcpy(A->layer_outputs, x, sizeof(orc_real) * (size_t)A->channels * n);
   orc_conv1d_process(&A->head_rechannel, A->head_inputs, A->head_output_size, n);
 }
 
@@ -999,13 +1043,16 @@ static void orc_act_from_cfg(orc_act* a, const float* cfg)
     /* FastLUTActivation's constructor, activations.h:374-388: step = (max - min) / (size - 1); table[i] = f(min + i * step) */
     const int base = (int)a->p[2];
     a->lut_n = (int)a->p[3];
-    a->lut_step = (a->p[1] - a->p[0]) / (float)(a->lut_n - 1);
+    a->lut_step = (a->p[1] - a->p[0]) / (orc_real)(a->lut_n - 1);
     a->lut_inv_step = 1.0f / a->lut_step;
-    a->lut = (float*)malloc(sizeof(float) * (size_t)a->lut_n);
+    a->lut = (orc_real*)malloc(sizeof(orc_real) * (size_t)a->lut_n);
+    /* the table is data of the function: float32 entries at float32 abscissae in either build */
+    const float lo = (float)a->p[0], step = ((float)a->p[1] - lo) / (float)(a->lut_n - 1);
     for (int i = 0; i < a->lut_n; i++)
     {
-      const float x = a->p[0] + (float)i * a->lut_step;
-      a->lut[i] = base == ORC_ACT_TANH ? tanhf(x) : base == ORC_ACT_SIGMOID ? orc_sigmoid(x) : x * orc_sigmoid(x);
+      const float x = lo + (float)i * step;
+      const float sg = 1.0f / (1.0f + expf(-x));
+      a->lut[i] = base == ORC_ACT_TANH ? tanhf(x) : base == ORC_ACT_SIGMOID ? sg : x * sg;
     }
   }
 }
@@ -1117,7 +1164,7 @@ ORC_API int orc_wavenet_prewarm_samples(void* h)
 }
 ORC_API float orc_wavenet_head_scale(void* h)
 {
-  return ((orc_wavenet*)h)->head_scale;
+  return (float)((orc_wavenet*)h)->head_scale; /* a value of the file: float32 in either build */
 }
 
 static int orc_wavenet_cond_dim(const orc_wavenet* wn)
@@ -1131,29 +1178,29 @@ static void orc_wavenet_set_max_buffer(orc_wavenet* wn, int max_buf)
   orc_arena_free(&wn->buf_arena);
   wn->max_buf = max_buf;
   const int cd = orc_wavenet_cond_dim(wn);
-  wn->cond_in = (float*)orc_alloc(&wn->buf_arena, sizeof(float) * (size_t)cd * max_buf);
+  wn->cond_in = (orc_real*)orc_alloc(&wn->buf_arena, sizeof(orc_real) * (size_t)cd * max_buf);
   int cout = cd;
   if (wn->condition_dsp)
   {
     orc_wavenet_set_max_buffer(wn->condition_dsp, max_buf);
     cout = wn->condition_dsp->out_channels;
   }
-  wn->cond_out = (float*)orc_alloc(&wn->buf_arena, sizeof(float) * (size_t)cout * max_buf);
-  wn->tmp_io = (float*)orc_alloc(&wn->buf_arena, sizeof(float) * (size_t)(cd + cout + wn->out_channels) * max_buf);
+  wn->cond_out = (orc_real*)orc_alloc(&wn->buf_arena, sizeof(orc_real) * (size_t)cout * max_buf);
+  wn->tmp_io = (orc_real*)orc_alloc(&wn->buf_arena, sizeof(orc_real) * (size_t)(cd + cout + wn->out_channels) * max_buf);
   for (int a = 0; a < wn->n_arrays; a++)
     orc_array_set_max_buffer(&wn->buf_arena, &wn->arrays[a], max_buf);
   if (wn->with_head)
   {
     for (int i = 0; i < wn->head_n; i++)
       orc_conv1d_set_max_buffer(&wn->buf_arena, &wn->head_convs[i], max_buf);
-    wn->scaled_head = (float*)orc_alloc(&wn->buf_arena, sizeof(float) * (size_t)wn->head_convs[0].in_ch * max_buf);
+    wn->scaled_head = (orc_real*)orc_alloc(&wn->buf_arena, sizeof(orc_real) * (size_t)wn->head_convs[0].in_ch * max_buf);
   }
 }
 
 /* `in`  : [in_channels][n]  planar (channel-major, like NAM_SAMPLE** input[ch][frame])
  * `out` : [out_channels][n] planar
  * model.cpp:822-910 */
-ORC_API void orc_wavenet_process(void* h, const float* in, float* out, int n)
+ORC_API void orc_wavenet_process(void* h, const orc_real* in, orc_real* out, int n)
 {
   orc_wavenet* wn = (orc_wavenet*)h;
   const int cd = orc_wavenet_cond_dim(wn);
@@ -1164,15 +1211,15 @@ ORC_API void orc_wavenet_process(void* h, const float* in, float* out, int n)
   /* _process_condition — model.cpp:777-807 */
   int cdim_out = cd;
   if (!wn->condition_dsp)
-    memcpy(wn->cond_out, wn->cond_in, sizeof(float) * (size_t)cd * n);
+    memcpy(wn->cond_out, wn->cond_in, sizeof(orc_real) * (size_t)cd * n);
   else
   {
     orc_wavenet* c = wn->condition_dsp;
     cdim_out = c->out_channels;
-    float* tin = wn->tmp_io;
-    float* tout = wn->tmp_io + (size_t)cd * n;
-    /* float -> NAM_SAMPLE(double) -> float round trips are exact, so planar float copies suffice */
-    memcpy(tin, in, sizeof(float) * (size_t)cd * n);
+    orc_real* tin = wn->tmp_io;
+    orc_real* tout = wn->tmp_io + (size_t)cd * n;
+    /* float -> NAM_SAMPLE(double) -> float round trips are exact, so planar copies suffice */
+    memcpy(tin, in, sizeof(orc_real) * (size_t)cd * n);
     orc_wavenet_process(c, tin, tout, n);
     for (int ch = 0; ch < cdim_out; ch++)
       for (int j = 0; j < n; j++)
@@ -1188,14 +1235,14 @@ ORC_API void orc_wavenet_process(void* h, const float* in, float* out, int n)
                         wn->arrays[a - 1].head_rechannel.out, n);
   }
   const orc_array* last = &wn->arrays[wn->n_arrays - 1];
-  const float* fh = last->head_rechannel.out;
+  const orc_real* fh = last->head_rechannel.out;
   const int hs = last->head_size;
   if (wn->with_head)
   {
     /* model.cpp:854-883 + Head::process :86-103 */
     for (long i = 0; i < (long)hs * n; i++)
       wn->scaled_head[i] = wn->head_scale * fh[i];
-    float* work = wn->scaled_head;
+    orc_real* work = wn->scaled_head;
     for (int i = 0; i < wn->head_n; i++)
     {
       orc_conv1d* cv = &wn->head_convs[i];
@@ -1217,20 +1264,20 @@ ORC_API void orc_wavenet_process(void* h, const float* in, float* out, int n)
 
 /* A long signal fed in `block`-frame process() calls, as tools/benchmodel.cpp:129-132 and
  * tools/render.cpp:146-197 do; the loop lives in C so timing it excludes any Python overhead. */
-ORC_API void orc_wavenet_process_blocks(void* h, const float* in, float* out, long n_total, int block)
+ORC_API void orc_wavenet_process_blocks(void* h, const orc_real* in, orc_real* out, long n_total, int block)
 {
   orc_wavenet* wn = (orc_wavenet*)h;
   const int ic = wn->in_channels, oc = wn->out_channels;
-  float* tin = (float*)malloc(sizeof(float) * (size_t)ic * block);
-  float* tout = (float*)malloc(sizeof(float) * (size_t)oc * block);
+  orc_real* tin = (orc_real*)malloc(sizeof(orc_real) * (size_t)ic * block);
+  orc_real* tout = (orc_real*)malloc(sizeof(orc_real) * (size_t)oc * block);
   for (long s = 0; s < n_total; s += block)
   {
     const int n = (int)((n_total - s) < block ? (n_total - s) : block);
     for (int c = 0; c < ic; c++)
-      memcpy(tin + (size_t)c * n, in + (size_t)c * n_total + s, sizeof(float) * n);
+      memcpy(tin + (size_t)c * n, in + (size_t)c * n_total + s, sizeof(orc_real) * n);
     orc_wavenet_process(wn, tin, tout, n);
     for (int c = 0; c < oc; c++)
-      memcpy(out + (size_t)c * n_total + s, tout + (size_t)c * n, sizeof(float) * n);
+      memcpy(out + (size_t)c * n_total + s, tout + (size_t)c * n, sizeof(orc_real) * n);
   }
   free(tin);
   free(tout);
@@ -1273,8 +1320,8 @@ static void orc_wavenet_prewarm(orc_wavenet* wn)
     return;
   }
   const int bs = wn->max_buf > 0 ? wn->max_buf : 1;
-  float* zin = (float*)calloc((size_t)wn->in_channels * bs, sizeof(float));
-  float* zout = (float*)calloc((size_t)wn->out_channels * bs, sizeof(float));
+  orc_real* zin = (orc_real*)calloc((size_t)wn->in_channels * bs, sizeof(orc_real));
+  orc_real* zout = (orc_real*)calloc((size_t)wn->out_channels * bs, sizeof(orc_real));
   int done = 0;
   while (done < wn->prewarm_samples)
   {
@@ -1324,11 +1371,11 @@ ORC_API void orc_wavenet_free(void* h)
 typedef struct
 {
   int input_size, hidden;
-  float* w; /* [4H][I+H] row-major */
-  float* b; /* 4H */
-  float* xh; /* I+H */
-  float* ifgo; /* 4H */
-  float* c; /* H */
+  orc_real* w; /* [4H][I+H] row-major */
+  orc_real* b; /* 4H */
+  orc_real* xh; /* I+H */
+  orc_real* ifgo; /* 4H */
+  orc_real* c; /* H */
 } orc_lstm_cell;
 
 typedef struct
@@ -1338,10 +1385,10 @@ typedef struct
   int fast; /* activations::Activation::using_fast_tanh */
   double sample_rate;
   orc_lstm_cell* cells;
-  float* head_w; /* [out][H] */
-  float* head_b;
-  float* input;
-  float* output;
+  orc_real* head_w; /* [out][H] */
+  orc_real* head_b;
+  orc_real* input;
+  orc_real* output;
   int max_buf;
 } orc_lstm;
 
@@ -1378,11 +1425,11 @@ ORC_API void* orc_lstm_new(int in_ch, int out_ch, int n_layers, int input_size, 
     const int I = l == 0 ? input_size : hidden, H = hidden;
     c->input_size = I;
     c->hidden = H;
-    c->w = (float*)orc_alloc(&m->arena, sizeof(float) * (size_t)4 * H * (I + H));
-    c->b = (float*)orc_alloc(&m->arena, sizeof(float) * 4 * H);
-    c->xh = (float*)orc_alloc(&m->arena, sizeof(float) * (I + H));
-    c->ifgo = (float*)orc_alloc(&m->arena, sizeof(float) * 4 * H);
-    c->c = (float*)orc_alloc(&m->arena, sizeof(float) * H);
+    c->w = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * (size_t)4 * H * (I + H));
+    c->b = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * 4 * H);
+    c->xh = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * (I + H));
+    c->ifgo = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * 4 * H);
+    c->c = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * H);
     for (int i = 0; i < 4 * H; i++)
       for (int j = 0; j < I + H; j++)
         c->w[(size_t)i * (I + H) + j] = *(w++);
@@ -1393,28 +1440,28 @@ ORC_API void* orc_lstm_new(int in_ch, int out_ch, int n_layers, int input_size, 
     for (int i = 0; i < H; i++)
       c->c[i] = *(w++); /* initial cell state */
   }
-  m->head_w = (float*)orc_alloc(&m->arena, sizeof(float) * (size_t)out_ch * hidden);
-  m->head_b = (float*)orc_alloc(&m->arena, sizeof(float) * out_ch);
+  m->head_w = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * (size_t)out_ch * hidden);
+  m->head_b = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * out_ch);
   for (int o = 0; o < out_ch; o++)
     for (int hh = 0; hh < hidden; hh++)
       m->head_w[(size_t)o * hidden + hh] = *(w++);
   for (int o = 0; o < out_ch; o++)
     m->head_b[o] = *(w++);
-  m->input = (float*)orc_alloc(&m->arena, sizeof(float) * (input_size > in_ch ? input_size : in_ch));
-  m->output = (float*)orc_alloc(&m->arena, sizeof(float) * out_ch);
+  m->input = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * (input_size > in_ch ? input_size : in_ch));
+  m->output = (orc_real*)orc_alloc(&m->arena, sizeof(orc_real) * out_ch);
   return m;
 }
 
 /* lstm.cpp:31-68 */
-static void orc_lstm_cell_process(orc_lstm_cell* c, const float* x, int fast)
+static void orc_lstm_cell_process(orc_lstm_cell* c, const orc_real* x, int fast)
 {
   const int H = c->hidden, I = c->input_size;
   for (int i = 0; i < I; i++)
     c->xh[i] = x[i];
   for (int r = 0; r < 4 * H; r++)
   {
-    const float* wr = c->w + (size_t)r * (I + H);
-    float sum = 0.0f;
+    const orc_real* wr = c->w + (size_t)r * (I + H);
+    orc_real sum = 0.0f;
     for (int j = 0; j < I + H; j++)
       sum += wr[j] * c->xh[j];
     c->ifgo[r] = sum + c->b[r];
@@ -1431,14 +1478,14 @@ static void orc_lstm_cell_process(orc_lstm_cell* c, const float* x, int fast)
   else
   {
     for (int i = 0; i < H; i++)
-      c->c[i] = orc_sigmoid(c->ifgo[i + fo]) * c->c[i] + orc_sigmoid(c->ifgo[i + io]) * tanhf(c->ifgo[i + go]);
+      c->c[i] = orc_sigmoid(c->ifgo[i + fo]) * c->c[i] + orc_sigmoid(c->ifgo[i + io]) * orc_tanh(c->ifgo[i + go]);
     for (int i = 0; i < H; i++)
-      c->xh[I + i] = orc_sigmoid(c->ifgo[i + oo]) * tanhf(c->c[i]);
+      c->xh[I + i] = orc_sigmoid(c->ifgo[i + oo]) * orc_tanh(c->c[i]);
   }
 }
 
 /* lstm.cpp:103-125, 136-168 */
-ORC_API void orc_lstm_process(void* h, const float* in, float* out, int n)
+ORC_API void orc_lstm_process(void* h, const orc_real* in, orc_real* out, int n)
 {
   orc_lstm* m = (orc_lstm*)h;
   for (int f = 0; f < n; f++)
@@ -1459,10 +1506,10 @@ ORC_API void orc_lstm_process(void* h, const float* in, float* out, int n)
       for (int l = 1; l < m->n_layers; l++)
         orc_lstm_cell_process(&m->cells[l], m->cells[l - 1].xh + m->cells[l - 1].input_size, m->fast);
       const orc_lstm_cell* last = &m->cells[m->n_layers - 1];
-      const float* hs = last->xh + last->input_size;
+      const orc_real* hs = last->xh + last->input_size;
       for (int o = 0; o < m->out_ch; o++)
       {
-        float sum = 0.0f;
+        orc_real sum = 0.0f;
         for (int j = 0; j < m->hidden; j++)
           sum += m->head_w[(size_t)o * m->hidden + j] * hs[j];
         m->output[o] = sum + m->head_b[o];
@@ -1473,20 +1520,20 @@ ORC_API void orc_lstm_process(void* h, const float* in, float* out, int n)
   }
 }
 
-ORC_API void orc_lstm_process_blocks(void* h, const float* in, float* out, long n_total, int block)
+ORC_API void orc_lstm_process_blocks(void* h, const orc_real* in, orc_real* out, long n_total, int block)
 {
   orc_lstm* m = (orc_lstm*)h;
   const int ic = m->in_ch, oc = m->out_ch;
-  float* tin = (float*)malloc(sizeof(float) * (size_t)ic * block);
-  float* tout = (float*)malloc(sizeof(float) * (size_t)oc * block);
+  orc_real* tin = (orc_real*)malloc(sizeof(orc_real) * (size_t)ic * block);
+  orc_real* tout = (orc_real*)malloc(sizeof(orc_real) * (size_t)oc * block);
   for (long s = 0; s < n_total; s += block)
   {
     const int n = (int)((n_total - s) < block ? (n_total - s) : block);
     for (int c = 0; c < ic; c++)
-      memcpy(tin + (size_t)c * n, in + (size_t)c * n_total + s, sizeof(float) * n);
+      memcpy(tin + (size_t)c * n, in + (size_t)c * n_total + s, sizeof(orc_real) * n);
     orc_lstm_process(m, tin, tout, n);
     for (int c = 0; c < oc; c++)
-      memcpy(out + (size_t)c * n_total + s, tout + (size_t)c * n, sizeof(float) * n);
+      memcpy(out + (size_t)c * n_total + s, tout + (size_t)c * n, sizeof(orc_real) * n);
   }
   free(tin);
   free(tout);
@@ -1508,8 +1555,8 @@ ORC_API void orc_lstm_reset(void* h, int max_buf, int prewarm)
   if (!prewarm)
     return;
   const int bs = max_buf > 0 ? max_buf : 1;
-  float* zin = (float*)calloc((size_t)m->in_ch * bs, sizeof(float));
-  float* zout = (float*)calloc((size_t)m->out_ch * bs, sizeof(float));
+  orc_real* zin = (orc_real*)calloc((size_t)m->in_ch * bs, sizeof(orc_real));
+  orc_real* zout = (orc_real*)calloc((size_t)m->out_ch * bs, sizeof(orc_real));
   const int target = orc_lstm_prewarm_samples(m);
   int done = 0;
   while (done < target)
@@ -1537,7 +1584,7 @@ ORC_API void orc_lstm_free(void* h)
 /* Conv1D on a fresh (zero-history) instance, processing `n_calls` consecutive
  * blocks of `num_frames` frames each. in/out column-major [ch][total_frames]. */
 ORC_API int orc_kat_conv1d(int in_ch, int out_ch, int K, int has_bias, int dilation, int groups, const float* weights,
-                           long n_weights, const float* in, float* out, int num_frames, int n_calls, int max_buf)
+                           long n_weights, const orc_real* in, orc_real* out, int num_frames, int n_calls, int max_buf)
 {
   orc_arena ar = {0};
   orc_conv1d c;
@@ -1552,14 +1599,14 @@ ORC_API int orc_kat_conv1d(int in_ch, int out_ch, int K, int has_bias, int dilat
   for (int i = 0; i < n_calls; i++)
   {
     orc_conv1d_process(&c, in + (size_t)i * num_frames * in_ch, in_ch, num_frames);
-    memcpy(out + (size_t)i * num_frames * out_ch, c.out, sizeof(float) * (size_t)out_ch * num_frames);
+    memcpy(out + (size_t)i * num_frames * out_ch, c.out, sizeof(orc_real) * (size_t)out_ch * num_frames);
   }
   orc_arena_free(&ar);
   return 0;
 }
 
 ORC_API int orc_kat_conv1x1(int in_ch, int out_ch, int has_bias, int groups, const float* weights, long n_weights,
-                            const float* in, float* out, int num_frames)
+                            const orc_real* in, orc_real* out, int num_frames)
 {
   orc_arena ar = {0};
   orc_conv1x1 c;
@@ -1572,13 +1619,13 @@ ORC_API int orc_kat_conv1x1(int in_ch, int out_ch, int has_bias, int groups, con
   orc_conv1x1_set_weights(&c, weights);
   orc_conv1x1_set_max_buffer(&ar, &c, num_frames);
   orc_conv1x1_process(&c, in, in_ch, num_frames);
-  memcpy(out, c.out, sizeof(float) * (size_t)out_ch * num_frames);
+  memcpy(out, c.out, sizeof(orc_real) * (size_t)out_ch * num_frames);
   orc_arena_free(&ar);
   return 0;
 }
 
 ORC_API int orc_kat_film(int cond_dim, int input_dim, int shift, int groups, const float* weights, long n_weights,
-                         const float* in, const float* cond, float* out, int num_frames)
+                         const orc_real* in, const orc_real* cond, orc_real* out, int num_frames)
 {
   orc_arena ar = {0};
   orc_film f;
@@ -1590,14 +1637,14 @@ ORC_API int orc_kat_film(int cond_dim, int input_dim, int shift, int groups, con
   }
   orc_conv1x1_set_weights(&f.css, weights);
   orc_conv1x1_set_max_buffer(&ar, &f.css, num_frames);
-  f.out = (float*)orc_alloc(&ar, sizeof(float) * (size_t)input_dim * num_frames);
+  f.out = (orc_real*)orc_alloc(&ar, sizeof(orc_real) * (size_t)input_dim * num_frames);
   orc_film_process(&f, in, input_dim, cond, cond_dim, num_frames);
-  memcpy(out, f.out, sizeof(float) * (size_t)input_dim * num_frames);
+  memcpy(out, f.out, sizeof(orc_real) * (size_t)input_dim * num_frames);
   orc_arena_free(&ar);
   return 0;
 }
 
-ORC_API void orc_kat_activation(const float* act_cfg, float* data, long size)
+ORC_API void orc_kat_activation(const float* act_cfg, orc_real* data, long size)
 {
   orc_act a;
   orc_act_from_cfg(&a, act_cfg);
@@ -1605,7 +1652,7 @@ ORC_API void orc_kat_activation(const float* act_cfg, float* data, long size)
 }
 
 /* mode: 1 = gated, 2 = blended. z is [2B x n] column-major; result in top B rows. */
-ORC_API void orc_kat_gating(int mode, const float* act_cfg, const float* act2_cfg, int B, float* z, int num_frames)
+ORC_API void orc_kat_gating(int mode, const float* act_cfg, const float* act2_cfg, int B, orc_real* z, int num_frames)
 {
   orc_layer L;
   memset(&L, 0, sizeof(L));
@@ -1620,8 +1667,8 @@ ORC_API void orc_kat_gating(int mode, const float* act_cfg, const float* act2_cf
 /* One WaveNet Layer in isolation (tools/test/test_wavenet/test_layer.cpp). Uses a
  * single-array single-layer wavenet handle built by the caller; exposes the
  * layer's next-layer output and head output for one Process call. */
-ORC_API int orc_kat_layer(void* h, const float* weights, long n_weights, const float* input, const float* cond,
-                          float* out_next, float* out_head, int num_frames)
+ORC_API int orc_kat_layer(void* h, const float* weights, long n_weights, const orc_real* input, const orc_real* cond,
+                          orc_real* out_next, orc_real* out_head, int num_frames)
 {
   orc_wavenet* wn = (orc_wavenet*)h;
   orc_array* A = &wn->arrays[0];
@@ -1632,8 +1679,8 @@ ORC_API int orc_kat_layer(void* h, const float* weights, long n_weights, const f
   orc_arena ar = {0};
   orc_layer_set_max_buffer(&ar, L, num_frames);
   orc_layer_process(L, input, cond, num_frames);
-  memcpy(out_next, L->out_next, sizeof(float) * (size_t)L->channels * num_frames);
-  memcpy(out_head, L->out_head, sizeof(float) * (size_t)L->head_out_ch * num_frames);
+  memcpy(out_next, L->out_next, sizeof(orc_real) * (size_t)L->channels * num_frames);
+  memcpy(out_head, L->out_head, sizeof(orc_real) * (size_t)L->head_out_ch * num_frames);
   orc_arena_free(&ar);
   return L->head_out_ch;
 }

@@ -2,7 +2,7 @@
 nam_oracle.py — CPU ORACLE front end (test infrastructure, NOT product code).
 
 Interprets a ``.nam`` file (JSON) the way the reference's loaders do and drives
-the plain-C float32 numerics in ``nam_oracle.c`` through ctypes.  Only
+the plain-C float32 numerics in ``nam_oracle.c`` (and their float64 build, ``real="f64"``) through ctypes.  Only
 ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg
 may import this module; the product package never does.
 
@@ -30,7 +30,17 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_HERE, "libnam_oracle.so")
+# one C source, one library per real type (nam_oracle.c: orc_real): "f32" is the oracle, "f64" the float64 evaluation of
+# the same function (float32-rounded weights and constants, exact-to-double arithmetic) that tests/accuracy.py measures
+# float32 against; "f32x2" is the float32 oracle with tanh / sigmoid in the kernels' documented exp2 forms (ORC_EXP2_FORMS)
+_BUILDS = {
+    "f32": ("libnam_oracle.so", []),
+    "f64": ("libnam_oracle_f64.so", ["-DORC_REAL_DOUBLE"]),
+    "f32x2": ("libnam_oracle_exp2.so", ["-DORC_EXP2_FORMS"]),
+}
+_LIB_PATHS = {real: os.path.join(_HERE, name) for real, (name, _) in _BUILDS.items()}
+_LIB_PATH = _LIB_PATHS["f32"]
+_NP = {"f32": np.float32, "f64": np.float64, "f32x2": np.float32}
 
 LATEST_FULLY_SUPPORTED_NAM_FILE_VERSION = "0.7.0"  # get_dsp.h:66
 EARLIEST_SUPPORTED_NAM_FILE_VERSION = "0.5.0"  # get_dsp.h:67
@@ -68,15 +78,18 @@ class NamFileValidationError(Exception):
 
 
 def build(force: bool = False) -> str:
-    """Compile nam_oracle.c -> libnam_oracle.so (gcc, no FMA contraction)."""
+    """Compile nam_oracle.c -> libnam_oracle.so and, with the same strict flags, its float64 and exp2-form builds next to it
+    (gcc, no FMA contraction). Returns the float32 library's path."""
     src = os.path.join(_HERE, "nam_oracle.c")
-    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
-        # -ffp-contract=off: every multiply/add individually rounded; -O3 vectorises across output
-        # channels only (no -ffast-math), so results do not depend on the host's SIMD width.
-        cmd = ["gcc", "-O3", "-march=x86-64-v3", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden",
-               "-std=c99", "-o", _LIB_PATH, src, "-lm"]
-        subprocess.check_call(cmd)
-    return _LIB_PATH
+    for real, (name, defines) in _BUILDS.items():
+        out = os.path.join(_HERE, name)
+        if force or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
+            # -ffp-contract=off: every multiply/add individually rounded; -O3 vectorises across output
+            # channels only (no -ffast-math), so results do not depend on the host's SIMD width.
+            cmd = ["gcc", "-O3", "-march=x86-64-v3", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden",
+                   "-std=c99"] + defines + ["-o", out, src, "-lm"]
+            subprocess.check_call(cmd)
+    return os.path.join(_HERE, _BUILDS["f32"][0])
 
 
 def build_fast(out_path: str, opt: str = "-Ofast") -> str:
@@ -89,24 +102,29 @@ def build_fast(out_path: str, opt: str = "-Ofast") -> str:
     return out_path
 
 
-_lib = None
+_libs = {}  # real -> loaded library: the builds live side by side in one process
 
 
 def use_library(path: str) -> None:
-    """Point the module at another build of the same C source (bench.py's -Ofast timing build)."""
-    global _lib, _LIB_PATH
-    _LIB_PATH = path
-    _lib = None
+    """Point the float32 oracle at another build of the same C source (bench.py's -Ofast timing build)."""
+    global _LIB_PATH
+    _LIB_PATH = _LIB_PATHS["f32"] = path
+    _libs.pop("f32", None)
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if _LIB_PATH == os.path.join(_HERE, "libnam_oracle.so"):
+def lib(real: str = "f32"):
+    """The library of one real type. Weights and activation configs are float32 in every build (``fp``); audio and the
+    KAT entry points' matrices are the build's real type (``rp``)."""
+    if real not in _BUILDS:
+        raise ValueError(f"real must be one of {sorted(_BUILDS)}, not {real!r}")
+    if real not in _libs:
+        if _LIB_PATHS[real] == os.path.join(_HERE, _BUILDS[real][0]):
             build()
-        L = ctypes.CDLL(_LIB_PATH)
+        L = ctypes.CDLL(_LIB_PATHS[real])
+        L.real = real
         vp, ci, cf, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
         fp = ctypes.POINTER(ctypes.c_float)
+        rp = ctypes.POINTER(ctypes.c_double if real == "f64" else ctypes.c_float)
         ip = ctypes.POINTER(ctypes.c_int)
         L.orc_wavenet_new.restype = vp
         L.orc_wavenet_new.argtypes = [ci, ci]
@@ -129,11 +147,11 @@ def lib():
         L.orc_wavenet_head_scale.restype = cf
         L.orc_wavenet_head_scale.argtypes = [vp]
         L.orc_wavenet_process.restype = None
-        L.orc_wavenet_process.argtypes = [vp, fp, fp, ci]
+        L.orc_wavenet_process.argtypes = [vp, rp, rp, ci]
         L.orc_wavenet_process_blocks.restype = None
-        L.orc_wavenet_process_blocks.argtypes = [vp, fp, fp, cl, ci]
+        L.orc_wavenet_process_blocks.argtypes = [vp, rp, rp, cl, ci]
         L.orc_lstm_process_blocks.restype = None
-        L.orc_lstm_process_blocks.argtypes = [vp, fp, fp, cl, ci]
+        L.orc_lstm_process_blocks.argtypes = [vp, rp, rp, cl, ci]
         L.orc_wavenet_reset.restype = None
         L.orc_wavenet_reset.argtypes = [vp, ci, ci]
         L.orc_wavenet_free.restype = None
@@ -143,7 +161,7 @@ def lib():
         L.orc_lstm_new.restype = vp
         L.orc_lstm_new.argtypes = [ci, ci, ci, ci, ci, fp, cl, ctypes.c_double, ci]
         L.orc_lstm_process.restype = None
-        L.orc_lstm_process.argtypes = [vp, fp, fp, ci]
+        L.orc_lstm_process.argtypes = [vp, rp, rp, ci]
         L.orc_lstm_prewarm_samples.restype = ci
         L.orc_lstm_prewarm_samples.argtypes = [vp]
         L.orc_lstm_reset.restype = None
@@ -151,24 +169,30 @@ def lib():
         L.orc_lstm_free.restype = None
         L.orc_lstm_free.argtypes = [vp]
         L.orc_kat_conv1d.restype = ci
-        L.orc_kat_conv1d.argtypes = [ci, ci, ci, ci, ci, ci, fp, cl, fp, fp, ci, ci, ci]
+        L.orc_kat_conv1d.argtypes = [ci, ci, ci, ci, ci, ci, fp, cl, rp, rp, ci, ci, ci]
         L.orc_kat_conv1x1.restype = ci
-        L.orc_kat_conv1x1.argtypes = [ci, ci, ci, ci, fp, cl, fp, fp, ci]
+        L.orc_kat_conv1x1.argtypes = [ci, ci, ci, ci, fp, cl, rp, rp, ci]
         L.orc_kat_film.restype = ci
-        L.orc_kat_film.argtypes = [ci, ci, ci, ci, fp, cl, fp, fp, fp, ci]
+        L.orc_kat_film.argtypes = [ci, ci, ci, ci, fp, cl, rp, rp, rp, ci]
         L.orc_kat_activation.restype = None
-        L.orc_kat_activation.argtypes = [fp, fp, cl]
+        L.orc_kat_activation.argtypes = [fp, rp, cl]
         L.orc_kat_gating.restype = None
-        L.orc_kat_gating.argtypes = [ci, fp, fp, ci, fp, ci]
+        L.orc_kat_gating.argtypes = [ci, fp, fp, ci, rp, ci]
         L.orc_kat_layer.restype = ci
-        L.orc_kat_layer.argtypes = [vp, fp, cl, fp, fp, fp, fp, ci]
-        _lib = L
-    return _lib
+        L.orc_kat_layer.argtypes = [vp, fp, cl, rp, rp, rp, rp, ci]
+        _libs[real] = L
+    return _libs[real]
 
 
 def _fptr(a: np.ndarray):
     assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _rptr(a: np.ndarray, real: str):
+    """Audio of a library's real type."""
+    assert a.dtype == _NP[real] and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double if real == "f64" else ctypes.c_float))
 
 
 def _iptr(a: np.ndarray):
@@ -594,8 +618,10 @@ def modify_params_for_channels(arrays: List[LayerArrayParams], new_channels: Lis
 # Model objects
 # ---------------------------------------------------------------------------
 class OracleDSP:
-    """Common surface, shaped like nam::DSP (NAM/dsp.h:70-231) but planar float32 numpy I/O."""
+    """Common surface, shaped like nam::DSP (NAM/dsp.h:70-231) but planar numpy I/O: float32, or float64 for an object
+    loaded with real="f64"."""
 
+    real = "f32"
     expected_sample_rate = -1.0
     loudness: Optional[float] = None
     input_level: Optional[float] = None
@@ -620,9 +646,9 @@ class OracleDSP:
 
     def process_stream(self, x: np.ndarray, block: int) -> np.ndarray:
         """Run a long signal through in `block`-frame calls (what benchmodel/render do)."""
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_NP[self.real])
         n = x.shape[1]
-        out = np.zeros((self.NumOutputChannels(), n), dtype=np.float32)
+        out = np.zeros((self.NumOutputChannels(), n), dtype=_NP[self.real])
         for s in range(0, n, block):
             e = min(n, s + block)
             out[:, s:e] = self.process(x[:, s:e])
@@ -631,9 +657,10 @@ class OracleDSP:
 
 class OracleWaveNet(OracleDSP):
     def __init__(self, wc: WaveNetConfig, weights: np.ndarray, sample_rate: float, fast_tanh: bool,
-                 arrays: Optional[List[LayerArrayParams]] = None):
-        L = lib()
+                 arrays: Optional[List[LayerArrayParams]] = None, real: str = "f32"):
+        L = lib(real)
         self._L = L
+        self.real = real
         self.expected_sample_rate = sample_rate
         self.fast_tanh = fast_tanh
         arrays = arrays if arrays is not None else wc.arrays
@@ -643,7 +670,7 @@ class OracleWaveNet(OracleDSP):
         self._cond = None
         if wc.condition_dsp_json is not None:
             # nam::get_dsp(condition_dsp_json) — model.cpp:919-930
-            cond = load_nam_json(wc.condition_dsp_json, fast_tanh=fast_tanh)
+            cond = load_nam_json(wc.condition_dsp_json, fast_tanh=fast_tanh, real=real)
             if not isinstance(cond, OracleWaveNet):
                 raise RuntimeError("oracle: condition_dsp must be a WaveNet")
             if cond.expected_sample_rate != sample_rate:
@@ -708,26 +735,27 @@ class OracleWaveNet(OracleDSP):
         self._L.orc_wavenet_reset(self._h, max_buffer_size, 1 if prewarm else 0)
 
     def process(self, x):
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_NP[self.real])
         assert x.shape[0] == self.NumInputChannels()
         n = x.shape[1]
         assert n <= self.max_buffer_size, "num_frames must be <= max buffer size (model.cpp:824)"
-        out = np.zeros((self.NumOutputChannels(), n), dtype=np.float32)
-        self._L.orc_wavenet_process(self._h, _fptr(x), _fptr(out), n)
+        out = np.zeros((self.NumOutputChannels(), n), dtype=_NP[self.real])
+        self._L.orc_wavenet_process(self._h, _rptr(x, self.real), _rptr(out, self.real), n)
         return out
 
     def process_stream(self, x, block):
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_NP[self.real])
         assert x.shape[0] == self.NumInputChannels() and block <= self.max_buffer_size
-        out = np.zeros((self.NumOutputChannels(), x.shape[1]), dtype=np.float32)
-        self._L.orc_wavenet_process_blocks(self._h, _fptr(x), _fptr(out), x.shape[1], block)
+        out = np.zeros((self.NumOutputChannels(), x.shape[1]), dtype=_NP[self.real])
+        self._L.orc_wavenet_process_blocks(self._h, _rptr(x, self.real), _rptr(out, self.real), x.shape[1], block)
         return out
 
 
 class OracleSlimmableWaveNet(OracleDSP):
     """slimmable.cpp:352-530 — rebuilds a plain WaveNet of the selected width."""
 
-    def __init__(self, config: dict, weights: np.ndarray, sample_rate: float, fast_tanh: bool):
+    def __init__(self, config: dict, weights: np.ndarray, sample_rate: float, fast_tanh: bool, real: str = "f32"):
+        self.real = real
         model_json = config["model"] if "model" in config else config
         self._wc = parse_wavenet_config(model_json)
         if self._wc.with_head:
@@ -779,7 +807,7 @@ class OracleSlimmableWaveNet(OracleDSP):
         else:
             w = extract_slimmed_weights(self._wc.arrays, self._full, channels)
             arrays = modify_params_for_channels(self._wc.arrays, channels)
-        self._active = OracleWaveNet(self._wc, w, self.expected_sample_rate, self.fast_tanh, arrays=arrays)
+        self._active = OracleWaveNet(self._wc, w, self.expected_sample_rate, self.fast_tanh, arrays=arrays, real=self.real)
         self._channels = channels
         if self._reset_args is not None:
             self._active.Reset(*self._reset_args)
@@ -816,9 +844,10 @@ class OracleSlimmableWaveNet(OracleDSP):
 
 
 class OracleLSTM(OracleDSP):
-    def __init__(self, config: dict, weights: np.ndarray, sample_rate: float, fast_tanh: bool):
-        L = lib()
+    def __init__(self, config: dict, weights: np.ndarray, sample_rate: float, fast_tanh: bool, real: str = "f32"):
+        L = lib(real)
         self._L = L
+        self.real = real
         self.expected_sample_rate = sample_rate
         self.num_layers = int(config["num_layers"])
         self.input_size = int(config["input_size"])
@@ -850,16 +879,16 @@ class OracleLSTM(OracleDSP):
         self._L.orc_lstm_reset(self._h, max_buffer_size, 1 if prewarm else 0)
 
     def process(self, x):
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_NP[self.real])
         n = x.shape[1]
-        out = np.zeros((self.out_channels, n), dtype=np.float32)
-        self._L.orc_lstm_process(self._h, _fptr(x), _fptr(out), n)
+        out = np.zeros((self.out_channels, n), dtype=_NP[self.real])
+        self._L.orc_lstm_process(self._h, _rptr(x, self.real), _rptr(out, self.real), n)
         return out
 
     def process_stream(self, x, block):
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float32)
-        out = np.zeros((self.out_channels, x.shape[1]), dtype=np.float32)
-        self._L.orc_lstm_process_blocks(self._h, _fptr(x), _fptr(out), x.shape[1], block)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=_NP[self.real])
+        out = np.zeros((self.out_channels, x.shape[1]), dtype=_NP[self.real])
+        self._L.orc_lstm_process_blocks(self._h, _rptr(x, self.real), _rptr(out, self.real), x.shape[1], block)
         return out
 
 
@@ -867,13 +896,14 @@ class OracleContainer(OracleDSP):
     """SlimmableContainer — NAM/container.cpp:17-144. Submodels are whole .nam documents; one is active at a time
     (the last one on construction), chosen by SetSlimmableSize: first max_value with val < max_value, else last."""
 
-    def __init__(self, config: dict, sample_rate: float, fast_tanh: bool):
+    def __init__(self, config: dict, sample_rate: float, fast_tanh: bool, real: str = "f32"):
+        self.real = real
         subs = config.get("submodels")
         if not isinstance(subs, list) or not subs:
             raise RuntimeError("SlimmableContainer: 'submodels' must be a non-empty array")
         self.expected_sample_rate = sample_rate
         self._max = [float(e["max_value"]) for e in subs]
-        self._models = [load_nam_json(e["model"], fast_tanh=fast_tanh) for e in subs]
+        self._models = [load_nam_json(e["model"], fast_tanh=fast_tanh, real=real) for e in subs]
         for i in range(1, len(self._max)):  # container.cpp:26-30
             if self._max[i] <= self._max[i - 1]:
                 raise RuntimeError("ContainerModel: submodels must be sorted by ascending max_value")
@@ -927,7 +957,7 @@ class OracleContainer(OracleDSP):
 # ---------------------------------------------------------------------------
 # get_dsp — get_dsp.cpp:141-273
 # ---------------------------------------------------------------------------
-def load_nam_json(j: dict, fast_tanh: bool = False) -> OracleDSP:
+def load_nam_json(j: dict, fast_tanh: bool = False, real: str = "f32") -> OracleDSP:
     verify_config_version(j["version"])
     if "weights" not in j:
         raise RuntimeError("Corrupted model file is missing weights.")
@@ -938,13 +968,13 @@ def load_nam_json(j: dict, fast_tanh: bool = False) -> OracleDSP:
     if arch == "WaveNet":
         # dispatch order: slimmable -> (a2_fast: same math as generic) -> generic — model.cpp:1312-1326
         if _is_slimmable(config):
-            dsp = OracleSlimmableWaveNet(config, weights, sample_rate, fast_tanh)
+            dsp = OracleSlimmableWaveNet(config, weights, sample_rate, fast_tanh, real=real)
         else:
-            dsp = OracleWaveNet(parse_wavenet_config(config), weights, sample_rate, fast_tanh)
+            dsp = OracleWaveNet(parse_wavenet_config(config), weights, sample_rate, fast_tanh, real=real)
     elif arch == "LSTM":
-        dsp = OracleLSTM(config, weights, sample_rate, fast_tanh)
+        dsp = OracleLSTM(config, weights, sample_rate, fast_tanh, real=real)
     elif arch == "SlimmableContainer":
-        dsp = OracleContainer(config, sample_rate, fast_tanh)
+        dsp = OracleContainer(config, sample_rate, fast_tanh, real=real)
     else:
         raise RuntimeError("No config parser registered for architecture: " + str(arch))
     md = j.get("metadata")
@@ -975,6 +1005,7 @@ def validate_nam_file(path: str) -> dict:
     return j
 
 
-def get_dsp(path: str, fast_tanh: bool = False, luts=None) -> OracleDSP:
-    """``luts``: see LoadMode (Activation::enable_lut before get_dsp)."""
-    return load_nam_json(validate_nam_file(path), fast_tanh=LoadMode(fast_tanh, luts) if luts else fast_tanh)
+def get_dsp(path: str, fast_tanh: bool = False, luts=None, real: str = "f32") -> OracleDSP:
+    """``luts``: see LoadMode (Activation::enable_lut before get_dsp). ``real``: "f32" (the oracle) or "f64" (the same
+    function in float64: takes and returns float64 arrays); "f32x2" is float32 with the kernels' exp2 forms of tanh / sigmoid."""
+    return load_nam_json(validate_nam_file(path), fast_tanh=LoadMode(fast_tanh, luts) if luts else fast_tanh, real=real)

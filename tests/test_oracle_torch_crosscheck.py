@@ -13,11 +13,12 @@ torch = pytest.importorskip("torch")
 Fn = torch.nn.functional
 
 
-def torch_wavenet(path, x, use_tanh=torch.tanh):
-    """Whole-signal evaluation with zero history (== Reset without prewarm, then process)."""
+def torch_wavenet(path, x, use_tanh=torch.tanh, dtype=torch.float32):
+    """Whole-signal evaluation with zero history (== Reset without prewarm, then process). `dtype`: the arithmetic; the
+    weights are the file's float32 values in either case (tests/test_oracle_truth.py runs it in float64)."""
     j = json.load(open(path))
     cfg = j["config"]
-    w = torch.tensor(j["weights"], dtype=torch.float32)
+    w = torch.tensor(j["weights"], dtype=torch.float32).to(dtype)
     p = 0
 
     def take(n):
@@ -26,14 +27,14 @@ def torch_wavenet(path, x, use_tanh=torch.tanh):
         p += n
         return v
 
-    xin = torch.tensor(x, dtype=torch.float32)[None, None, :]  # [1, 1, T]
+    xin = torch.tensor(x, dtype=dtype)[None, None, :]  # [1, 1, T]
     cond = xin
     layer_in, head_in = xin, None
     for lc in cfg["layers"]:
         C, K, cs, ins, H = lc["channels"], lc["kernel_size"], lc["condition_size"], lc["input_size"], lc["head_size"]
         act = {"Tanh": use_tanh, "ReLU": torch.relu}[lc["activation"]]
         h = Fn.conv1d(layer_in, take(C * ins).view(C, ins, 1))
-        head = torch.zeros(1, C, h.shape[2]) if head_in is None else head_in
+        head = torch.zeros(1, C, h.shape[2], dtype=dtype) if head_in is None else head_in
         for d in lc["dilations"]:
             cw, cb = take(C * C * K).view(C, C, K), take(C)
             mw = take(C * cs).view(C, cs, 1)
