@@ -302,23 +302,16 @@ int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
 {
   const nam_hip_bank_data& bank = *b->bank;
   const Plan& p = *g.plan;
-  float*& d_blobs = kBankFamily[bank.family].blob_source == BANK_BLOB_WR ? g.d_wr_blob : g.d_blob;
-  NAM_HIP_CHECK(hipMalloc(&d_blobs, bank.blobs.size() * sizeof(float)));
-  NAM_HIP_CHECK(hipMemcpy(d_blobs, bank.blobs.data(), bank.blobs.size() * sizeof(float), hipMemcpyHostToDevice));
+  DeviceBuf<float>& d_blobs = kBankFamily[bank.family].blob_source == BANK_BLOB_WR ? g.d_wr_blob : g.d_blob;
+  NAM_HIP_CHECK(upload(d_blobs, bank.blobs.data(), bank.blobs.size()));
   if (kBankFamily[bank.family].per_member == BANK_MEMBER_INIT_STATES)
-  {
-    NAM_HIP_CHECK(hipMalloc(&g.d_init, std::max<size_t>(bank.init.size(), 1) * sizeof(float)));
-    NAM_HIP_CHECK(hipMemcpy(g.d_init, bank.init.data(), bank.init.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+    NAM_HIP_CHECK(upload(g.d_init, bank.init.data(), bank.init.size(), 1));
   else if (kBankFamily[bank.family].per_member == BANK_MEMBER_SCALARS)
   {
-    NAM_HIP_CHECK(hipMalloc(&g.d_a1, sizeof(A1Plan)));
-    NAM_HIP_CHECK(hipMemcpy(g.d_a1, &p.a1, sizeof(A1Plan), hipMemcpyHostToDevice));
-    NAM_HIP_CHECK(hipMalloc(&g.d_bank_scal, bank.scal.size() * sizeof(float)));
-    NAM_HIP_CHECK(hipMemcpy(g.d_bank_scal, bank.scal.data(), bank.scal.size() * sizeof(float), hipMemcpyHostToDevice));
+    NAM_HIP_CHECK(upload(g.d_a1, &p.a1, 1));
+    NAM_HIP_CHECK(upload(g.d_bank_scal, bank.scal.data(), bank.scal.size()));
   }
-  NAM_HIP_CHECK(hipMalloc(&g.d_bank_member, (size_t)b->n_streams * sizeof(int)));
-  NAM_HIP_CHECK(hipMemcpy(g.d_bank_member, b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(upload(g.d_bank_member, b->stream_member.data(), (size_t)b->n_streams));
   g.bank_stride = bank.blob_stride;
   g.state_stride = p.state_floats;
   return NAM_HIP_OK;
@@ -328,8 +321,8 @@ int upload_bank_group(nam_hip_batch* b, WidthGroup& g)
 // On the batch's stream.
 int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n)
 {
-  NAM_HIP_CHECK(launch_fill_state_bank(g.d_state, g.state_stride, d_map, n, g.d_init, g.d_bank_member, b->bank->n_init,
-                                       g.plan->state_floats, b->stream));
+  NAM_HIP_CHECK(launch_fill_state_bank(g.d_state.get(), g.state_stride, d_map, n, g.d_init.get(), g.d_bank_member.get(), b->bank->n_init,
+                                       g.plan->state_floats, b->stream.get()));
   return NAM_HIP_OK;
 }
 
@@ -362,22 +355,11 @@ int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, in
   WidthGroup& g = b->groups[b->model->full_width];
   for (int s : moved)
     b->stream_member[s] = member;
-  NAM_HIP_CHECK(hipMemcpy(g.d_bank_member, b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
-  // fresh state of the new member for the streams that moved: Reset (+ prewarm), every other stream untouched
-  int* d_moved = nullptr;
-  NAM_HIP_CHECK(hipMalloc(&d_moved, moved.size() * sizeof(int)));
-  NAM_HIP_CHECK(hipMemcpy(d_moved, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(hipMemcpy(g.d_bank_member.get(), b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
+  // fresh state of the new member for the streams that moved: Reset (+ prewarm), every other stream untouched.
   // An LSTM's Reset clears nothing (the reference's has nothing to clear: its state is h / c, born from the weight stream), so the
   // moved streams would keep the OLD member's h / c: they get the new member's h0 / c0 here, as a newly created batch's streams do
-  int rc = kBankFamily[b->bank->family].per_member == BANK_MEMBER_INIT_STATES ? bank_fill_initial_state(b, g, d_moved, (int)moved.size()) : NAM_HIP_OK;
-  if (rc == NAM_HIP_OK)
-    rc = reset_streams(b, g, d_moved, (int)moved.size(), b->was_reset && b->reset_with_prewarm, -1);
-  const hipError_t e = hipStreamSynchronize(b->stream);
-  (void)hipFree(d_moved);
-  if (rc != NAM_HIP_OK)
-    return rc;
-  NAM_HIP_CHECK(e);
-  return NAM_HIP_OK;
+  return reset_moved_streams(b, g, moved, kBankFamily[b->bank->family].per_member == BANK_MEMBER_INIT_STATES);
 }
 
 } // namespace api

@@ -9,13 +9,13 @@ namespace api
 
 // The blocking entry points inside a persistent session: the kernel reads the buffer from and writes it to HOST-MAPPED
 // memory (float32 rows [stream][channel][max_frames]); in_f32 / in_f64 and out_f32 / out_f64: exactly one of each.
-// The host-mapped windows of the session's blocking (`slots` = 1: nam_hip_batch::in_bar, h_out_map) or ticketed
-// (NAM_HIP_PIPE_SLOTS: pipe_in_bar, pipe_h_out_map) entry points. false: no such memory here (the copying path serves the call).
-bool host_windows(nam_hip_batch* b, int slots, float*& in_bar, float*& h_out_map, float*& d_out_map, bool& failed, bool prealloc)
+// The host-mapped windows of the session's blocking (`slots` = 1: nam_hip_batch::win) or ticketed
+// (NAM_HIP_PIPE_SLOTS: pipe_win) entry points. false: no such memory here (the copying path serves the call).
+bool host_windows(nam_hip_batch* b, int slots, HostWindows& w, bool prealloc)
 {
-  if (failed)
+  if (w.failed)
     return false;
-  if (in_bar)
+  if (w.in_bar)
     return true;
   const int ic = b->model->spec->in_channels(), oc = b->model->spec->out_channels();
   const size_t pitch = (size_t)b->n_streams * std::max(ic, oc) * b->max_frames; // (one slot; the same for both windows: a command carries ONE offset)
@@ -29,31 +29,22 @@ bool host_windows(nam_hip_batch* b, int slots, float*& in_bar, float*& h_out_map
     std::fprintf(stderr, "nam_hip: %d streams x %d frames x %d host-buffer slots exceed the 2 GB session window: host buffers of this "
                          "batch go through staging copies instead of the mapped windows (smaller max_frames or fewer streams per batch avoid this)\n",
                  b->n_streams, b->max_frames, slots);
-    failed = true;
+    w.failed = true;
     return false;
   }
-  if (hipExtMallocWithFlags(reinterpret_cast<void**>(&in_bar), pitch * slots * sizeof(float), hipDeviceMallocFinegrained) != hipSuccess)
+  // both or neither, built aside and handed over whole: a later call must not find the input window without the output window
+  // (it would submit commands with a null output base and copy from a null mapping)
+  DeviceBuf<float> in_bar;
+  MappedBuf<float> out_map;
+  if (alloc_fine_grained(in_bar, pitch * slots) != hipSuccess // (no host-writable device memory here)
+      || out_map.alloc(pitch * slots) != hipSuccess)
   {
     (void)hipGetLastError();
-    in_bar = nullptr;
-    failed = true; // no host-writable device memory here
+    w.failed = true; // the copying path takes over
     return false;
   }
-  // all three or none: a later call must not find the input window without the output window (it would submit commands
-  // with a null output base and copy from a null mapping)
-  if (hipHostMalloc(reinterpret_cast<void**>(&h_out_map), pitch * slots * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess
-      || hipHostGetDevicePointer(reinterpret_cast<void**>(&d_out_map), h_out_map, 0) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    if (h_out_map)
-      (void)hipHostFree(h_out_map);
-    (void)hipFree(in_bar);
-    in_bar = nullptr;
-    h_out_map = nullptr;
-    d_out_map = nullptr;
-    failed = true; // the copying path takes over
-    return false;
-  }
+  w.in_bar = std::move(in_bar);
+  w.out_map = std::move(out_map);
   return true;
 }
 
@@ -73,7 +64,7 @@ bool host_mapped_applies(nam_hip_batch* b, int n_frames)
 // n_frames not a multiple of 64), < 0 on failure.
 int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_f64, float* out_f32, double* out_f64, int n_frames)
 {
-  if (!host_mapped_applies(b, n_frames) || !host_windows(b, 1, b->in_bar, b->h_out_map, b->d_out_map, b->map_failed))
+  if (!host_mapped_applies(b, n_frames) || !host_windows(b, 1, b->win))
     return 1;
   const int ic = b->model->spec->in_channels(), oc = b->model->spec->out_channels();
   const long stride = b->max_frames;
@@ -81,7 +72,7 @@ int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_
   const size_t rows_in = (size_t)b->n_streams * ic, rows_out = (size_t)b->n_streams * oc;
   for (size_t r = 0; r < rows_in; r++)
   {
-    float* dst = b->in_bar + r * stride;
+    float* dst = b->win.in_bar.get() + r * stride;
     if (in_f32)
       copy_to_window(dst, in_f32 + r * n_frames, (size_t)n_frames);
     else // double -> float exactly as _set_condition_array does (NAM/wavenet/model.cpp:817)
@@ -99,12 +90,12 @@ int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_
   if (linger_now != b->blocking_linger && b->ps.active && b->ps.outstanding)
   {
     // (the running launch was started under the other rule: let it go first — a whole flush; rare: the pattern changed)
-    const int rf = persist_flush(b, b->stream);
+    const int rf = persist_flush(b, b->stream.get());
     if (rf != NAM_HIP_OK)
       return rf;
   }
   b->blocking_linger = linger_now;
-  const int rc = persist_submit(b, b->in_bar, b->d_out_map, n_frames, stride, b->stream);
+  const int rc = persist_submit(b, b->win.in_bar.get(), b->win.out_map.dev(), n_frames, stride, b->stream.get());
   if (rc != NAM_HIP_OK)
   {
     b->one_buffer_call = b->short_blocking_call = false;
@@ -112,14 +103,14 @@ int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_
   }
   // this call's own commands: the per-command completion word when the launch publishes it (it may linger on), else the
   // whole launch (it leaves when it has drained the ring)
-  const int rw = b->ps.cmd_done_published ? persist_wait(b, b->stream, b->ps.seq, false) : persist_flush(b, b->stream);
+  const int rw = b->ps.cmd_done_published ? persist_wait(b, b->stream.get(), b->ps.seq, false) : persist_flush(b, b->stream.get());
   b->one_buffer_call = b->short_blocking_call = false;
   if (rw != NAM_HIP_OK)
     return rw;
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
   for (size_t r = 0; r < rows_out; r++)
   {
-    const float* src = b->h_out_map + r * stride;
+    const float* src = b->win.out_map.host() + r * stride;
     if (out_f32)
       std::memcpy(out_f32 + r * n_frames, src, (size_t)n_frames * sizeof(float));
     else
@@ -136,18 +127,18 @@ int pipe_submit(nam_hip_batch* b, const float* in, int n_frames, PipeSlot& sl, i
   const int ic = b->model->spec->in_channels(), oc = b->model->spec->out_channels();
   const size_t rows_in = (size_t)b->n_streams * ic, rows_out = (size_t)b->n_streams * oc;
   sl.n_frames = n_frames;
-  if (host_mapped_applies(b, n_frames) && host_windows(b, NAM_HIP_PIPE_SLOTS, b->pipe_in_bar, b->pipe_h_out_map, b->pipe_d_out_map, b->pipe_map_failed))
+  if (host_mapped_applies(b, n_frames) && host_windows(b, NAM_HIP_PIPE_SLOTS, b->pipe_win))
   {
     // the session: the input goes through the PCIe window into the slot's rows, the commands follow it; the resident
     // launch writes the slot's rows of the host-side window
     const long stride = b->max_frames, at = (long)slot * (long)std::max(rows_in, rows_out) * b->max_frames;
     const double t0 = stats_on() ? stat_now_us() : 0.0;
     for (size_t r = 0; r < rows_in; r++)
-      copy_to_window(b->pipe_in_bar + at + r * stride, in + r * n_frames, (size_t)n_frames);
+      copy_to_window(b->pipe_win.in_bar.get() + at + r * stride, in + r * n_frames, (size_t)n_frames);
     push_out_host_stores();
     const double t1 = stats_on() ? stat_now_us() : 0.0;
     b->pipe_session = true;
-    const int rc = persist_submit(b, b->pipe_in_bar + at, b->pipe_d_out_map + at, n_frames, stride, b->stream);
+    const int rc = persist_submit(b, b->pipe_win.in_bar.get() + at, b->pipe_win.out_map.dev() + at, n_frames, stride, b->stream.get());
     if (stats_on())
     {
       const double t2 = stat_now_us();
@@ -167,22 +158,22 @@ int pipe_submit(nam_hip_batch* b, const float* in, int n_frames, PipeSlot& sl, i
     const size_t slot_in = rows_in * b->max_frames, slot_out = rows_out * b->max_frames;
     if (!b->pipe_h_in)
     {
-      NAM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b->pipe_h_in), slot_in * NAM_HIP_PIPE_SLOTS * sizeof(float), hipHostMallocDefault));
-      NAM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b->pipe_h_out), slot_out * NAM_HIP_PIPE_SLOTS * sizeof(float), hipHostMallocDefault));
-      NAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b->pipe_d_in), slot_in * NAM_HIP_PIPE_SLOTS * sizeof(float)));
-      NAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b->pipe_d_out), slot_out * NAM_HIP_PIPE_SLOTS * sizeof(float)));
+      NAM_HIP_CHECK(hipHostMalloc(b->pipe_h_in.out(), slot_in * NAM_HIP_PIPE_SLOTS * sizeof(float), hipHostMallocDefault));
+      NAM_HIP_CHECK(hipHostMalloc(b->pipe_h_out.out(), slot_out * NAM_HIP_PIPE_SLOTS * sizeof(float), hipHostMallocDefault));
+      NAM_HIP_CHECK(hipMalloc(b->pipe_d_in.out(), slot_in * NAM_HIP_PIPE_SLOTS * sizeof(float)));
+      NAM_HIP_CHECK(hipMalloc(b->pipe_d_out.out(), slot_out * NAM_HIP_PIPE_SLOTS * sizeof(float)));
     }
     if (!sl.done)
-      NAM_HIP_CHECK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    float *hi = b->pipe_h_in + slot * slot_in, *ho = b->pipe_h_out + slot * slot_out;
-    float *di = b->pipe_d_in + slot * slot_in, *dn = b->pipe_d_out + slot * slot_out;
+      NAM_HIP_CHECK(hipEventCreateWithFlags(sl.done.out(), hipEventDisableTiming));
+    float *hi = b->pipe_h_in.get() + slot * slot_in, *ho = b->pipe_h_out.get() + slot * slot_out;
+    float *di = b->pipe_d_in.get() + slot * slot_in, *dn = b->pipe_d_out.get() + slot * slot_out;
     std::memcpy(hi, in, rows_in * n_frames * sizeof(float));
-    NAM_HIP_CHECK(hipMemcpyAsync(di, hi, rows_in * n_frames * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    NAM_HIP_CHECK(hipMemcpyAsync(di, hi, rows_in * n_frames * sizeof(float), hipMemcpyHostToDevice, b->stream.get()));
     const int rc = nam_hip_batch_process_device(b, di, dn, n_frames, n_frames, nullptr);
     if (rc != NAM_HIP_OK)
       return rc;
-    NAM_HIP_CHECK(hipMemcpyAsync(ho, dn, rows_out * n_frames * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    NAM_HIP_CHECK(hipEventRecord(sl.done, b->stream));
+    NAM_HIP_CHECK(hipMemcpyAsync(ho, dn, rows_out * n_frames * sizeof(float), hipMemcpyDeviceToHost, b->stream.get()));
+    NAM_HIP_CHECK(hipEventRecord(sl.done.get(), b->stream.get()));
     sl.how = 1;
     return NAM_HIP_OK;
   }
@@ -205,7 +196,7 @@ int pipe_wait(nam_hip_batch* b, PipeSlot& sl, int slot, float* out)
     const double t0 = stats_on() ? stat_now_us() : 0.0;
     if (b->ps.active && sl.epoch == b->ps.epoch) // (a session that has ended ended flushed)
     {
-      const int rc = persist_wait(b, b->stream, sl.seq_end, false);
+      const int rc = persist_wait(b, b->stream.get(), sl.seq_end, false);
       if (rc != NAM_HIP_OK)
         return rc;
     }
@@ -216,7 +207,7 @@ int pipe_wait(nam_hip_batch* b, PipeSlot& sl, int slot, float* out)
       const size_t rows_in = (size_t)b->n_streams * b->model->spec->in_channels();
       const long stride = b->max_frames, at = (long)slot * (long)std::max(rows_in, rows_out) * b->max_frames;
       for (size_t r = 0; r < rows_out; r++)
-        std::memcpy(out + r * n_frames, b->pipe_h_out_map + at + r * stride, (size_t)n_frames * sizeof(float));
+        std::memcpy(out + r * n_frames, b->pipe_win.out_map.host() + at + r * stride, (size_t)n_frames * sizeof(float));
     }
     if (stats_on())
     {
@@ -227,9 +218,9 @@ int pipe_wait(nam_hip_batch* b, PipeSlot& sl, int slot, float* out)
   }
   else if (sl.how == 1)
   {
-    NAM_HIP_CHECK(hipEventSynchronize(sl.done));
+    NAM_HIP_CHECK(hipEventSynchronize(sl.done.get()));
     if (out)
-      std::memcpy(out, b->pipe_h_out + (size_t)slot * rows_out * b->max_frames, rows_out * n_frames * sizeof(float));
+      std::memcpy(out, b->pipe_h_out.get() + (size_t)slot * rows_out * b->max_frames, rows_out * n_frames * sizeof(float));
   }
   else if (out)
     std::memcpy(out, sl.held.data(), rows_out * n_frames * sizeof(float));

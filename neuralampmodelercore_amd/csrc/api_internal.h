@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "device_owner.h"
 #include "kernels.h"
 #include "model_spec.h"
 #include "plan.h"
@@ -130,20 +131,21 @@ namespace namhip
 {
 namespace api
 {
+// (every device allocation is an owner, device_owner.h: `g = WidthGroup()` frees the group's, and so does the batch's end)
 struct WidthGroup
 {
   const Plan* plan = nullptr;
-  float* d_blob = nullptr;
-  NamOp* d_ops = nullptr;
-  A1Plan* d_a1 = nullptr;
-  float* d_wr_blob = nullptr; // nam_wn_reg_kernel's weights, tables and macro-ops (plan.h: WrPlan)
-  float* d_state = nullptr; // [n_streams][state_stride] (allocated when the first stream joins)
-  float* d_init = nullptr; // LSTM initial state
-  float* d_scratch = nullptr; // LSTM cells too large for LDS: nam_lstm_kernel<true>'s h / c / gate columns
+  DeviceBuf<float> d_blob;
+  DeviceBuf<NamOp> d_ops;
+  DeviceBuf<A1Plan> d_a1;
+  DeviceBuf<float> d_wr_blob; // nam_wn_reg_kernel's weights, tables and macro-ops (plan.h: WrPlan)
+  DeviceBuf<float> d_state; // [n_streams][state_stride] (allocated when the first stream joins)
+  DeviceBuf<float> d_init; // LSTM initial state
+  DeviceBuf<float> d_scratch; // LSTM cells too large for LDS: nam_lstm_kernel<true>'s h / c / gate columns
   long scratch_floats = 0;
   long state_stride = 0;
   std::vector<int> streams; // members, ascending
-  int* d_map = nullptr; // device copy of `streams` (nullptr when the group is all streams in order)
+  DeviceBuf<int> d_map; // device copy of `streams` (empty when the group is all streams in order)
   // Which layout the state currently holds: -1 = freshly zeroed (any), 0 = the op program's rings (shared by the A1
   // kernels unless they run on zero-padded channels: plan.h, Plan::a1_padded_layout), 1 = the padded A1 rings,
   // 2 = nam_wn_reg_kernel's 64-frame conv-input histories
@@ -152,15 +154,15 @@ struct WidthGroup
   // later Resets refill from it): one stream's state right after zero + prewarm — every stream's is the same — keyed by
   // the kernel that produced it and the frames it ran. A later Reset / SetSlimmableSize copies it instead of running
   // the silence again.
-  float* d_prewarm = nullptr;
+  DeviceBuf<float> d_prewarm;
   int prewarm_kernel = -1, prewarm_len = 0;
   // a bank batch's one group (api_bank.cpp): d_blob holds [members][bank_stride] floats, and the kernels pick a stream's member
   // through d_bank_member[stream] (indexed by STREAM, not by launch position) and its scalars from d_bank_scal[2 member].
   // No prewarm cache: a member's prewarmed state depends on its weights, so a Reset runs the silence for every stream.
   // BANK_MEMBER_INIT_STATES: no d_a1 and no d_bank_scal; d_init holds [members][n_init] floats, a stream's h0 / c0 its member's row.
   // BANK_BLOB_WR: the members' blobs are in d_wr_blob (where pick_kernel and wr_groups look), d_blob stays empty.
-  int* d_bank_member = nullptr;
-  float* d_bank_scal = nullptr;
+  DeviceBuf<int> d_bank_member;
+  DeviceBuf<float> d_bank_scal;
   long bank_stride = 0;
 };
 
@@ -188,14 +190,13 @@ struct PersistSession
   // it, and host-writable through the PCIe BAR (MI355X exposes all of HBM): the host stores a command itself when the
   // caller's stream is idle (the usual real-time case: nothing to order behind; a posted write, ~0.1 us), else the
   // store is enqueued on that stream (hipStreamWriteValue64: ~4 us of host time and a small kernel on the device)
-  unsigned long long* d_ring = nullptr;
+  DeviceBuf<unsigned long long> d_ring;
   bool host_store_ok = false; // the ring is fine-grained memory (else plain device memory: stream-ordered stores only)
-  unsigned* h_words = nullptr; // host-mapped: [0, n_wg) progress, [n_wg, 2 n_wg) completion (bit 31 = exited)
-  unsigned* d_words = nullptr; // the same words as the device sees them
-  unsigned* d_cons = nullptr; // device memory: commands consumed per workgroup (where its next launch resumes)
-  unsigned* d_cmd_count = nullptr; // device memory [kPRing]: workgroups through command c (A1Args::p_cmd_count), zero between commands
-  unsigned *h_cmd_done = nullptr, *d_cmd_done = nullptr; // host-mapped [kPRing]: c + 1 once every workgroup is through command c
-  hipStream_t last_caller = nullptr; // the stream the last doorbell was rung on
+  MappedBuf<unsigned> words; // host-mapped: [0, n_wg) progress, [n_wg, 2 n_wg) completion (bit 31 = exited); host() / dev(): the same words as either side sees them
+  DeviceBuf<unsigned> d_cons; // device memory: commands consumed per workgroup (where its next launch resumes)
+  DeviceBuf<unsigned> d_cmd_count; // device memory [kPRing]: workgroups through command c (A1Args::p_cmd_count), zero between commands
+  MappedBuf<unsigned> cmd_done; // host-mapped [kPRing]: c + 1 once every workgroup is through command c
+  hipStream_t last_caller = nullptr; // the stream the last doorbell was rung on (the caller's: not owned)
   int grace = 0; // A1Args::p_grace of the next launch
   long long seq0 = -1; // A1Args::p_seq0 / p_cmd0 of the next launch
   unsigned long long cmd0 = 0;
@@ -203,8 +204,8 @@ struct PersistSession
   bool flushed_valid = false;
   bool outstanding = false; // a launch of the session may still be running
   bool need_order = false; // the next launch must wait for the batch's own stream (session start)
-  hipStream_t kstream = nullptr; // the resident launch's own stream (nothing else may be enqueued behind it)
-  hipEvent_t order = nullptr; // makes the launch wait for what the caller had enqueued before the first buffer
+  StreamOwner kstream; // the resident launch's own stream (nothing else may be enqueued behind it)
+  EventOwner order; // makes the launch wait for what the caller had enqueued before the first buffer
   unsigned seq = 0; // commands submitted in this session
   const float* in_base = nullptr;
   float* out_base = nullptr;
@@ -212,7 +213,7 @@ struct PersistSession
   long stride = 0;
   int n_wg = 0; // workgroups of the session's launch
   int kind = -1; // PersistKind
-  int done_off = 0; // h_words: [0, done_off) progress words, [done_off, 2 done_off) completion words
+  int done_off = 0; // words: [0, done_off) progress words, [done_off, 2 done_off) completion words
   // Sequence numbers are 31-bit (bit 31 of a completion word is the "left" flag): a session START — where every
   // workgroup stands at exactly `seq` and nothing is in flight — rebases them to 0 once they pass this mark
   // (NAM_HIP_PERSIST_REBASE_AT overrides it: tests)
@@ -223,7 +224,7 @@ struct PersistSession
   // developer statistics (NAM_HIP_SESSION_STATS=1: printed when the batch is destroyed)
   unsigned long long n_launches = 0, n_host_doorbells = 0, n_stream_doorbells = 0, n_starts = 0, n_flush_relaunches = 0;
   double t_poll = 0, t_out = 0, t_in = 0, t_cmd = 0, t_poll_max = 0, t_out_max = 0, t_in_max = 0, t_cmd_max = 0; // us (NAM_HIP_SESSION_STATS)
-  long long *h_why = nullptr, *d_why = nullptr; // (NAM_HIP_SESSION_STATS) per workgroup: reason << 56 | grace loop << 48 | all-through count << 24 | own count
+  MappedBuf<long long> why; // (NAM_HIP_SESSION_STATS) per workgroup: reason << 56 | grace loop << 48 | all-through count << 24 | own count
   unsigned long long n_waits = 0, n_polls = 0; // ticket waits, looks at the buffer's completion word
   unsigned epoch = 0; // counts session starts (a ticket of an earlier session is complete: sessions end flushed)
   // Burst lengths (commands between two whole flushes) of this session, newest first; ~0u = not seen yet. A host that flushes after
@@ -235,7 +236,7 @@ struct PersistSession
   unsigned burst_start = 0; // `seq` at the last whole flush
   bool short_bursts() const { return bursts[0] <= 4u && bursts[1] <= 4u && bursts[2] <= 4u; }
   bool one_buffer_bursts() const { return bursts[0] == 1u && bursts[1] == 1u && bursts[2] == 1u; } // (nam_wn_reg_kernel: one wave per stream then)
-  hipEvent_t retired = nullptr; // the completion signal of the session's latest launch (kernels.h: nam_launch), recorded by the dispatch itself
+  EventOwner retired; // the completion signal of the session's latest launch (kernels.h: nam_launch), recorded by the dispatch itself
   bool cmd_done_published = false; // the running launch stores p_cmd_done behind every command's results (A1Args::p_out_host == 2); p_prog stays ring bookkeeping every 16 commands
 };
 
@@ -247,8 +248,16 @@ struct PipeSlot
   int n_frames = 0;
   int how = 0; // 0: a command range of the host-mapped session | 1: copies + launch on the batch's stream, `done` behind them | 2: rendered by a blocking call, kept in `held`
   unsigned seq_end = 0, epoch = 0; // how == 0: the session's command count behind this buffer, the session it belongs to
-  hipEvent_t done = nullptr;
+  EventOwner done;
   std::vector<float> held;
+};
+
+// The two windows of host buffers a session reads and writes itself (api_host_io.cpp: host_windows): both or neither
+struct HostWindows
+{
+  DeviceBuf<float> in_bar; // one address for both sides
+  MappedBuf<float> out_map; // host() / dev(): the host's address / the same memory as the device sees it
+  bool failed = false; // the allocation was refused once: the copying path stays
 };
 } // namespace api
 } // namespace namhip
@@ -261,38 +270,38 @@ struct nam_hip_batch
   int device = 0;
   int n_streams = 0;
   int max_frames = 0;
-  hipStream_t stream = nullptr;
-  std::vector<WidthGroup> groups;
-  std::vector<int> stream_width;
-  float* d_in = nullptr; // staging for the host-pointer entry points
-  float* d_out = nullptr;
-  float* h_stage = nullptr; // pinned, used by the f64 path
+  // Release order = the members' declaration order, backwards (nam_hip_batch_destroy only quiesces and deletes): the session (`ps`,
+  // the last owner below) goes first, then the groups, then staging and windows, then the ticket events (`pipe`), and `stream`
+  // last, when nothing that was enqueued on it is left. A new owner goes where its release belongs in that order.
+  StreamOwner stream;
+  PipeSlot pipe[NAM_HIP_PIPE_SLOTS];
+  DeviceBuf<float> d_in; // staging for the host-pointer entry points
+  DeviceBuf<float> d_out;
+  PinnedBuf<float> h_stage; // pinned, used by the f64 path
   // host-mapped staging of the blocking entry points in persistent mode: the session's kernel reads the input from and
   // writes the output to host memory itself (its input loads / output stores are system-scope anyway), so a blocking
   // call is: copy in, store the command(s), watch the completion words, copy out — no launch of a copy, no stream sync
   // input: FINE-GRAINED DEVICE memory the host writes through the PCIe BAR (posted writes; the device then reads local
   // HBM — device reads of host memory serialise at a microsecond or two per wavefront: 1.9 ms per buffer at 256 streams);
   // output: host-mapped memory the device writes (posted writes again), read by the host from its own DRAM
-  float* in_bar = nullptr; // one address for both sides
-  float *h_out_map = nullptr, *d_out_map = nullptr; // host address / the same memory as the device sees it
-  bool map_failed = false; // the allocation was refused once: the copying path stays
+  HostWindows win;
   // the ticketed entry points (nam_hip_batch_submit_f32) have windows of their own, the same two kinds of memory,
   // NAM_HIP_PIPE_SLOTS buffers deep: [slot][row][max_frames], slot = ticket % NAM_HIP_PIPE_SLOTS
-  float* pipe_in_bar = nullptr;
-  float *pipe_h_out_map = nullptr, *pipe_d_out_map = nullptr;
-  bool pipe_map_failed = false;
-  PipeSlot pipe[NAM_HIP_PIPE_SLOTS];
+  HostWindows pipe_win;
   long long pipe_next = 0; // the next ticket
   bool pipe_session = false; // the session serves ticketed buffers: its launches publish every command (PersistSession::cmd_done_published)
-  float *pipe_h_in = nullptr, *pipe_h_out = nullptr, *pipe_d_in = nullptr, *pipe_d_out = nullptr; // staging of the copying form ([slot][row][max_frames])
+  PinnedBuf<float> pipe_h_in, pipe_h_out; // staging of the copying form ([slot][row][max_frames])
+  DeviceBuf<float> pipe_d_in, pipe_d_out;
   std::vector<float> pipe_cvt; // the _f64 forms of submit / wait: one buffer of float32 on the way in / out
   int kernel = NAM_HIP_KERNEL_AUTO;
-  long long* dbg = nullptr; // device buffer of the profiling instantiation (nam_hip_batch_debug_timeline)
+  DeviceBuf<long long> dbg; // device buffer of the profiling instantiation (nam_hip_batch_debug_timeline: empty outside that call)
+  std::vector<WidthGroup> groups;
+  std::vector<int> stream_width;
   bool was_reset = false;
   bool reset_with_prewarm = true; // thread_local gPrewarmOnResetDefault = true (NAM/dsp.cpp:20)
   // the caller-supplied stream of the last nam_hip_batch_process_device: control calls that free or rewrite device
   // memory (Reset, SetSlimmableSize, destroy) wait for it as well as for the batch's own stream
-  hipStream_t last_ext_stream = nullptr;
+  hipStream_t last_ext_stream = nullptr; // (the caller's: not owned)
   bool short_blocking_call = false; // a blocking host call of up to four buffers is being served: the caller waits for it, so the FIRST buffer's
                                     // latency is what counts — nam_a1_p4_kernel (four waves per layer: ~6 us through the model) rather than
                                     // nam_a1_q_kernel (one wave per layer: ~30 us; faster only once buffers overlap)
@@ -417,6 +426,9 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
                  int n_frames, long io_stride, hipStream_t s);
 int prewarm_frames(const nam_hip_batch* b, const Plan& p);
 int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool prewarm, int first_stream);
+// fresh state for the streams `moved` (ascending, not empty) that have just joined `g`: their ids to the device, optionally their
+// members' initial states (an LSTM bank), Reset (+ prewarm as the batch was last reset), and the batch's stream drained
+int reset_moved_streams(nam_hip_batch* b, WidthGroup& g, const std::vector<int>& moved, bool fill_initial_states);
 // api_session.cpp
 int persist_family(const nam_hip_batch* b, const WidthGroup& g);
 int persist_kind(const nam_hip_batch* b);
@@ -429,14 +441,13 @@ int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_fram
 int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, hipStream_t caller);
 void persist_free(nam_hip_batch* b);
 // api_launch.cpp
-void free_group(WidthGroup& g);
 int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out);
 // api_bank.cpp
 int upload_bank_group(nam_hip_batch* b, WidthGroup& g);
 int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n);
 int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, int member);
 // api_host_io.cpp
-bool host_windows(nam_hip_batch* b, int slots, float*& in_bar, float*& h_out_map, float*& d_out_map, bool& failed, bool prealloc = false);
+bool host_windows(nam_hip_batch* b, int slots, HostWindows& w, bool prealloc = false);
 bool host_mapped_applies(nam_hip_batch* b, int n_frames);
 int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_f64, float* out_f32, double* out_f64, int n_frames);
 int pipe_submit(nam_hip_batch* b, const float* in, int n_frames, PipeSlot& sl, int slot);

@@ -10,30 +10,17 @@ namespace api
 int upload_group(nam_hip_batch* b, WidthGroup& g)
 {
   const Plan& p = *g.plan;
-  NAM_HIP_CHECK(hipMalloc(&g.d_blob, std::max<size_t>(p.blob.size(), 1) * sizeof(float)));
-  if (!p.blob.empty())
-    NAM_HIP_CHECK(hipMemcpy(g.d_blob, p.blob.data(), p.blob.size() * sizeof(float), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(upload(g.d_blob, p.blob.data(), p.blob.size(), 1));
   if (p.arch == ARCH_WAVENET)
   {
-    NAM_HIP_CHECK(hipMalloc(&g.d_ops, p.ops.size() * sizeof(NamOp)));
-    NAM_HIP_CHECK(hipMemcpy(g.d_ops, p.ops.data(), p.ops.size() * sizeof(NamOp), hipMemcpyHostToDevice));
+    NAM_HIP_CHECK(upload(g.d_ops, p.ops.data(), p.ops.size()));
     if (p.a1.valid)
-    {
-      NAM_HIP_CHECK(hipMalloc(&g.d_a1, sizeof(A1Plan)));
-      NAM_HIP_CHECK(hipMemcpy(g.d_a1, &p.a1, sizeof(A1Plan), hipMemcpyHostToDevice));
-    }
+      NAM_HIP_CHECK(upload(g.d_a1, &p.a1, 1));
     if (p.wr.ok)
-    {
-      NAM_HIP_CHECK(hipMalloc(&g.d_wr_blob, p.wr.blob.size() * sizeof(float)));
-      NAM_HIP_CHECK(hipMemcpy(g.d_wr_blob, p.wr.blob.data(), p.wr.blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+      NAM_HIP_CHECK(upload(g.d_wr_blob, p.wr.blob.data(), p.wr.blob.size()));
   }
   else if (p.arch == ARCH_LSTM)
-  {
-    const auto& init = p.lstm.init_state;
-    NAM_HIP_CHECK(hipMalloc(&g.d_init, std::max<size_t>(init.size(), 1) * sizeof(float)));
-    NAM_HIP_CHECK(hipMemcpy(g.d_init, init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+    NAM_HIP_CHECK(upload(g.d_init, p.lstm.init_state.data(), p.lstm.init_state.size(), 1));
   g.state_stride = p.state_floats;
   (void)b;
   return NAM_HIP_OK;
@@ -44,13 +31,13 @@ int ensure_state(nam_hip_batch* b, WidthGroup& g)
   if (g.d_state)
     return NAM_HIP_OK;
   const size_t bytes = (size_t)b->n_streams * g.state_stride * sizeof(float);
-  NAM_HIP_CHECK(hipMalloc(&g.d_state, bytes));
-  NAM_HIP_CHECK(hipMemsetAsync(g.d_state, 0, bytes, b->stream));
+  NAM_HIP_CHECK(hipMalloc(g.d_state.out(), bytes));
+  NAM_HIP_CHECK(hipMemsetAsync(g.d_state.get(), 0, bytes, b->stream.get()));
   if (g.plan->arch == ARCH_LSTM && g.d_bank_member) // a bank: every stream its member's h0 / c0
     return bank_fill_initial_state(b, g, nullptr, b->n_streams);
   if (g.plan->arch == ARCH_LSTM) // h0 / c0 from the weight stream, once per (sub)model instance (lstm.cpp:24-28)
-    NAM_HIP_CHECK(launch_fill_state(g.d_state, g.state_stride, nullptr, b->n_streams, g.d_init,
-                                    (int)g.plan->lstm.init_state.size(), g.plan->state_floats, b->stream));
+    NAM_HIP_CHECK(launch_fill_state(g.d_state.get(), g.state_stride, nullptr, b->n_streams, g.d_init.get(),
+                                    (int)g.plan->lstm.init_state.size(), g.plan->state_floats, b->stream.get()));
   return NAM_HIP_OK;
 }
 
@@ -59,8 +46,8 @@ hipError_t quiesce(nam_hip_batch* b)
 {
   if (b->ps.active && persist_stop(b) != NAM_HIP_OK) // a resident launch owns the streams' state until it has left
     return hipErrorUnknown;
-  hipError_t e = b->stream ? hipStreamSynchronize(b->stream) : hipSuccess;
-  if (b->last_ext_stream && b->last_ext_stream != b->stream)
+  hipError_t e = b->stream ? hipStreamSynchronize(b->stream.get()) : hipSuccess;
+  if (b->last_ext_stream && b->last_ext_stream != b->stream.get())
   {
     const hipError_t e2 = hipStreamSynchronize(b->last_ext_stream);
     if (e == hipSuccess)
@@ -81,16 +68,14 @@ int refresh_map(nam_hip_batch* b, WidthGroup& g)
   if (g.d_map)
   {
     NAM_HIP_CHECK(quiesce(b));
-    NAM_HIP_CHECK(hipFree(g.d_map));
-    g.d_map = nullptr;
+    NAM_HIP_CHECK(g.d_map.reset());
   }
   bool identity = (int)g.streams.size() == b->n_streams;
   for (size_t i = 0; identity && i < g.streams.size(); i++)
     identity = g.streams[i] == (int)i;
   if (g.streams.empty() || identity)
     return NAM_HIP_OK;
-  NAM_HIP_CHECK(hipMalloc(&g.d_map, g.streams.size() * sizeof(int)));
-  NAM_HIP_CHECK(hipMemcpy(g.d_map, g.streams.data(), g.streams.size() * sizeof(int), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(upload(g.d_map, g.streams.data(), g.streams.size()));
   return NAM_HIP_OK;
 }
 
@@ -153,11 +138,11 @@ PersistArgs persist_args(const nam_hip_batch* b)
   PersistArgs pa;
   if (!b->ps_launching)
     return pa;
-  pa.ring = b->ps.d_ring;
+  pa.ring = b->ps.d_ring.get();
   pa.ring_mask = (int)kPRing - 1;
-  pa.cons = b->ps.d_cons;
-  pa.prog = b->ps.d_words;
-  pa.done = b->ps.d_words + b->ps.done_off;
+  pa.cons = b->ps.d_cons.get();
+  pa.prog = b->ps.words.dev();
+  pa.done = b->ps.words.dev() + b->ps.done_off;
   pa.seq0 = b->ps.seq0;
   pa.cmd0 = b->ps.cmd0;
   pa.grace = b->ps.grace;
@@ -181,8 +166,8 @@ static void session_args(const nam_hip_batch* b, A1Args& a)
   a.p_grace = pa.grace;
   a.p_out_host = b->ps.out_is_host ? (b->ps.cmd_done_published ? 2 : 1) : 0;
   a.p_linger = (b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus) ? session_linger_ticks(b) : 0; // (more workgroups than CUs take turns: the ones on the chip must leave when the ring is empty)
-  a.p_cmd_count = b->ps.d_cmd_count;
-  a.p_cmd_done = b->ps.d_cmd_done;
+  a.p_cmd_count = b->ps.d_cmd_count.get();
+  a.p_cmd_done = b->ps.cmd_done.dev();
 }
 
 // The function of a per-model code object on the current device (hipModuleLoad is per device: cached per path and
@@ -264,8 +249,8 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
                   "nam_wn_reg_kernel's LDS-image rings differ): call nam_hip_batch_reset before switching");
     g.state_family = 2;
     WrGroup& G = a.g[k];
-    G.blob = g.d_wr_blob;
-    G.state = g.d_state;
+    G.blob = g.d_wr_blob.get();
+    G.state = g.d_state.get();
     G.stream_map = maps[k];
     G.state_stride = g.state_stride;
     G.n_ops = (int)w.ops.size();
@@ -371,7 +356,7 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
   a.in_ch = groups[0]->plan->in_channels;
   a.out_ch = groups[0]->plan->out_channels;
   a.ps = persist_args(b);
-  a.bank_member = groups[0]->d_bank_member; // (a bank batch has one group: groups[0]->d_wr_blob is [members][bank_stride])
+  a.bank_member = groups[0]->d_bank_member.get(); // (a bank batch has one group: groups[0]->d_wr_blob is [members][bank_stride])
   a.bank_stride = groups[0]->bank_stride;
   // every group on the model's own code object (they share one: build_model), or every group on the ahead-of-time kernel
   if (stages == 2) // (the kernels read a two-wave launch's cut from [1]: WrGroup::split_op)
@@ -420,7 +405,7 @@ int launch_wr_all(nam_hip_batch* b, const WrGroupList& gs, const float* d_in, fl
   int counts[kWrMaxGroups];
   for (int k = 0; k < gs.n; k++)
   {
-    maps[k] = gs.g[k]->d_map;
+    maps[k] = gs.g[k]->d_map.get();
     counts[k] = (int)gs.g[k]->streams.size();
   }
   return launch_wr(b, gs.g, maps, counts, gs.n, d_in, d_out, n_frames, io_stride, s);
@@ -524,8 +509,8 @@ const char* group_kernel_name(const nam_hip_batch* b, const WidthGroup& g, int n
 template <typename Args>
 static void common_args(Args& a, const WidthGroup& g, const int* d_map, const float* d_in, float* d_out, int n_frames, long io_stride)
 {
-  a.blob = g.d_blob;
-  a.state = g.d_state;
+  a.blob = g.d_blob.get();
+  a.state = g.d_state.get();
   a.state_stride = g.state_stride;
   a.stream_map = d_map;
   a.in = d_in;
@@ -546,15 +531,15 @@ static int uniform_act(const A1Plan& a1)
 static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args& a, int n, hipStream_t s)
 {
   const Plan& p = *g.plan;
-  a.plan = g.d_a1;
+  a.plan = g.d_a1.get();
   a.act_p0 = p.a1.arr[0].act_p0; // uniform across arrays and layers for the A1 kernels (plan.cpp)
-  a.dbg = b->dbg;
-  if (b->ps_launching && b->ps.h_why)
-    a.dbg = b->ps.d_why; // (NAM_HIP_SESSION_STATS: why a lingering workgroup left — il_common.h: session_wait_command)
+  a.dbg = b->dbg.get();
+  if (b->ps_launching && b->ps.why)
+    a.dbg = b->ps.why.dev(); // (NAM_HIP_SESSION_STATS: why a lingering workgroup left — il_common.h: session_wait_command)
   a.n_rings = p.a1.n_rings;
   a.head_scale = p.blob[(size_t)p.a1.head_scale_off];
-  a.bank_member = g.d_bank_member;
-  a.bank_scal = g.d_bank_scal;
+  a.bank_member = g.d_bank_member.get();
+  a.bank_scal = g.d_bank_scal.get();
   a.bank_stride = g.bank_stride;
   const bool il = fn == FN_A1_P2 || fn == FN_A1_P4 || fn == FN_A1_Q;
   if (g.d_bank_member && !((bank_rules(b).fns >> fn) & 1u))
@@ -618,7 +603,7 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
 static int launch_generic_program(const WidthGroup& g, GenericArgs& a, int n, hipStream_t s)
 {
   const Plan& p = *g.plan;
-  a.ops = g.d_ops;
+  a.ops = g.d_ops.get();
   a.in_ch = p.in_channels;
   a.out_ch = p.out_channels;
   // conv weights from LDS when the model's weights fit next to the activation rows (kernels.h)
@@ -639,7 +624,7 @@ static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTM
   a.n_streams = n;
   if (fn == FN_LSTM_ROW || fn == FN_LSTM_WIDE)
   {
-    a.bank_member = g.d_bank_member; // (a bank: a.blob is [members][bank_stride], whole plan blobs)
+    a.bank_member = g.d_bank_member.get(); // (a bank: a.blob is [members][bank_stride], whole plan blobs)
     a.bank_stride = g.bank_stride;
     a.ps = persist_args(b);
     NAM_HIP_CHECK(fn == FN_LSTM_ROW ? launch_lstm_row(a, s) : launch_lstm_wide(a, s));
@@ -654,14 +639,12 @@ static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTM
     if (need > g.scratch_floats)
     {
       NAM_HIP_CHECK(hipStreamSynchronize(s));
-      if (g.d_scratch)
-        NAM_HIP_CHECK(hipFree(g.d_scratch));
-      g.d_scratch = nullptr;
       g.scratch_floats = 0;
-      NAM_HIP_CHECK(hipMalloc(&g.d_scratch, (size_t)need * sizeof(float)));
+      NAM_HIP_CHECK(g.d_scratch.reset());
+      NAM_HIP_CHECK(hipMalloc(g.d_scratch.out(), (size_t)need * sizeof(float)));
       g.scratch_floats = need;
     }
-    a.scratch = g.d_scratch;
+    a.scratch = g.d_scratch.get();
     NAM_HIP_CHECK(launch_lstm(a, s));
   }
   return NAM_HIP_OK;
@@ -735,26 +718,26 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
       const int fam = state_family_of(p, kernel);
       if (g.prewarm_kernel == kernel && g.prewarm_len == frames && (all || g.state_family < 0 || g.state_family == fam))
       {
-        NAM_HIP_CHECK(launch_fill_state(g.d_state, g.state_stride, d_map, n, g.d_prewarm, p.state_floats, p.state_floats, b->stream));
+        NAM_HIP_CHECK(launch_fill_state(g.d_state.get(), g.state_stride, d_map, n, g.d_prewarm.get(), p.state_floats, p.state_floats, b->stream.get()));
         g.state_family = fam;
         return NAM_HIP_OK;
       }
     }
-    NAM_HIP_CHECK(launch_fill_state(g.d_state, g.state_stride, d_map, n, nullptr, 0, p.state_floats, b->stream));
+    NAM_HIP_CHECK(launch_fill_state(g.d_state.get(), g.state_stride, d_map, n, nullptr, 0, p.state_floats, b->stream.get()));
     if (all)
       g.state_family = -1; // every stream of the group is zeroed: either layout may follow
   }
   if (frames > 0)
   {
-    const int rc = launch_group(b, g, d_map, n, nullptr, nullptr, frames, 0, b->stream);
+    const int rc = launch_group(b, g, d_map, n, nullptr, nullptr, frames, 0, b->stream.get());
     if (rc != NAM_HIP_OK)
       return rc;
     if (p.arch == ARCH_WAVENET && first_stream >= 0 && !g.d_bank_member) // (a bank's prewarmed state depends on the member: no cache)
     {
       if (!g.d_prewarm)
-        NAM_HIP_CHECK(hipMalloc(&g.d_prewarm, (size_t)p.state_floats * sizeof(float)));
-      NAM_HIP_CHECK(hipMemcpyAsync(g.d_prewarm, g.d_state + (size_t)first_stream * g.state_stride,
-                                   (size_t)p.state_floats * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
+        NAM_HIP_CHECK(hipMalloc(g.d_prewarm.out(), (size_t)p.state_floats * sizeof(float)));
+      NAM_HIP_CHECK(hipMemcpyAsync(g.d_prewarm.get(), g.d_state.get() + (size_t)first_stream * g.state_stride,
+                                   (size_t)p.state_floats * sizeof(float), hipMemcpyDeviceToDevice, b->stream.get()));
       g.prewarm_kernel = kernel_for_launch(b, g, frames);
       g.prewarm_len = frames;
     }
@@ -762,32 +745,20 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
   return NAM_HIP_OK;
 }
 
-
-void free_group(WidthGroup& g)
+// The tail of nam_hip_batch_set_slimmable_size and bank_set_stream_model (api_internal.h)
+// (`moved.front()` seeds the prewarm cache; a bank group has none: reset_streams)
+int reset_moved_streams(nam_hip_batch* b, WidthGroup& g, const std::vector<int>& moved, bool fill_initial_states)
 {
-  if (g.d_blob)
-    (void)hipFree(g.d_blob);
-  if (g.d_ops)
-    (void)hipFree(g.d_ops);
-  if (g.d_wr_blob)
-    (void)hipFree(g.d_wr_blob);
-  if (g.d_a1)
-    (void)hipFree(g.d_a1);
-  if (g.d_state)
-    (void)hipFree(g.d_state);
-  if (g.d_init)
-    (void)hipFree(g.d_init);
-  if (g.d_scratch)
-    (void)hipFree(g.d_scratch);
-  if (g.d_map)
-    (void)hipFree(g.d_map);
-  if (g.d_prewarm)
-    (void)hipFree(g.d_prewarm);
-  if (g.d_bank_member)
-    (void)hipFree(g.d_bank_member);
-  if (g.d_bank_scal)
-    (void)hipFree(g.d_bank_scal);
-  g = WidthGroup();
+  DeviceBuf<int> d_moved;
+  NAM_HIP_CHECK(upload(d_moved, moved.data(), moved.size()));
+  int rc = fill_initial_states ? bank_fill_initial_state(b, g, d_moved.get(), (int)moved.size()) : NAM_HIP_OK;
+  if (rc == NAM_HIP_OK)
+    rc = reset_streams(b, g, d_moved.get(), (int)moved.size(), b->was_reset && b->reset_with_prewarm, moved.front());
+  const hipError_t e = hipStreamSynchronize(b->stream.get()); // (before d_moved goes: the launches read it)
+  if (rc != NAM_HIP_OK)
+    return rc;
+  NAM_HIP_CHECK(e);
+  return NAM_HIP_OK;
 }
 
 int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out)

@@ -38,7 +38,7 @@ int persist_kind(const nam_hip_batch* b)
       return b->n_streams <= kPersistTurns * per_cu * cus ? PERSIST_WN_REG : PERSIST_NONE;
     }
   }
-  if ((int)g.streams.size() != b->n_streams || g.d_map != nullptr)
+  if ((int)g.streams.size() != b->n_streams || g.d_map)
     return PERSIST_NONE;
   if (g.plan->arch == ARCH_WAVENET)
   {
@@ -77,8 +77,8 @@ static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, u
   {
     // the first launch of the session starts behind whatever the batch's own stream still has in flight (a reset, a
     // prewarm, an ordinary launch)
-    NAM_HIP_CHECK(hipEventRecord(ps.order, b->stream));
-    NAM_HIP_CHECK(hipStreamWaitEvent(ps.kstream, ps.order, 0));
+    NAM_HIP_CHECK(hipEventRecord(ps.order.get(), b->stream.get()));
+    NAM_HIP_CHECK(hipStreamWaitEvent(ps.kstream.get(), ps.order.get(), 0));
     ps.need_order = false;
   }
   ps.n_launches++;
@@ -88,7 +88,7 @@ static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, u
   // the workgroups set the top bit of their completion word when they leave: cleared here, "all set" = no launch of
   // the session is running any more (cheaper for the host to look at than hipStreamQuery on a busy stream)
   for (int w = 0; w < ps.n_wg; w++)
-    __atomic_and_fetch(&ps.h_words[ps.done_off + w], 0x7fffffffu, __ATOMIC_RELAXED);
+    __atomic_and_fetch(&ps.words.host()[ps.done_off + w], 0x7fffffffu, __ATOMIC_RELAXED);
   ps.outstanding = true;
   // ticketed host buffers: nam_a1_q_kernel / nam_kq_kernel store the per-buffer completion word (p_cmd_done) behind every
   // command's results (their p_prog, like every kernel's, is ring bookkeeping every 16 commands — never a completion signal;
@@ -108,14 +108,14 @@ static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, u
     {
       ps.grace = std::max(ps.grace, session_linger_ticks(b));
       // "a workgroup of this launch has left" (il_common.h: session_leaving; p_cmd_count[mask + 2] = [kPRing + 1]): none yet
-      NAM_HIP_CHECK(hipMemsetAsync(ps.d_cmd_count + kPRing + 1, 0, sizeof(unsigned), ps.kstream));
+      NAM_HIP_CHECK(hipMemsetAsync(ps.d_cmd_count.get() + kPRing + 1, 0, sizeof(unsigned), ps.kstream.get()));
     }
   }
   b->ps_launching = true; // (a session of the interleaved-frame family runs that family: api_launch.cpp, family_for_launch)
-  namhip::tl_session_stop_event = ps.retired; // (the launch's own completion signal: persist_wait waits on it, not on the stream)
+  namhip::tl_session_stop_event = ps.retired.get(); // (the launch's own completion signal: persist_wait waits on it, not on the stream)
   const int rc = ps.kind == PERSIST_WN_REG
-                   ? launch_wr_all(b, wr_groups(b), ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream)
-                   : launch_group(b, g, nullptr, b->n_streams, ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream);
+                   ? launch_wr_all(b, wr_groups(b), ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get())
+                   : launch_group(b, g, nullptr, b->n_streams, ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get());
   namhip::tl_session_stop_event = nullptr;
   b->ps_launching = false;
   return rc;
@@ -141,11 +141,11 @@ struct PersistWatch
     const auto now = std::chrono::steady_clock::now();
     unsigned long long sig = 0;
     for (int w = 0; w < 2 * b->ps.done_off; w++)
-      sig += __atomic_load_n(&b->ps.h_words[w], __ATOMIC_RELAXED);
+      sig += __atomic_load_n(&b->ps.words.host()[w], __ATOMIC_RELAXED);
     if (polls == 4096 || sig != seen)
       t0 = now;
     seen = sig;
-    const hipError_t q = hipStreamQuery(b->ps.kstream);
+    const hipError_t q = hipStreamQuery(b->ps.kstream.get());
     if (q == hipSuccess)
       return 1;
     if (q != hipErrorNotReady)
@@ -175,7 +175,7 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
   if (whole && ps.outstanding && ps.cmd_done_published && ps.host_store_ok && ps.n_wg <= b->n_cus)
   {
     // a lingering launch: tell it that nothing follows command `seq` (kPRingTail)
-    __atomic_store_n(&ps.d_ring[kPRing], (unsigned long long)ps.seq, __ATOMIC_RELEASE);
+    __atomic_store_n(&ps.d_ring.get()[kPRing], (unsigned long long)ps.seq, __ATOMIC_RELEASE);
     push_out_host_stores();
     told_leave = true;
   }
@@ -193,7 +193,7 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
       // ONE word: stored by the last workgroup through the last command of the buffer, behind everybody's results
       // (A1Args::p_cmd_done). A short spin on it between looks at the launch itself (the 2 n_wg words below, which the
       // device writes all the time: a pass over them costs the host microseconds).
-      const unsigned* flag = &ps.h_cmd_done[(target - 1u) & (kPRing - 1u)];
+      const unsigned* flag = &ps.cmd_done.host()[(target - 1u) & (kPRing - 1u)];
       for (int spin = 0; spin < 512; spin++)
       {
         ps.n_polls++;
@@ -210,7 +210,7 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
     unsigned lo = ~0u, all_left = 0x80000000u;
     for (int w = 0; w < ps.n_wg; w++)
     {
-      const unsigned v = __atomic_load_n(&ps.h_words[ps.done_off + w], __ATOMIC_ACQUIRE);
+      const unsigned v = __atomic_load_n(&ps.words.host()[ps.done_off + w], __ATOMIC_ACQUIRE);
       lo = std::min(lo, v & 0x7fffffffu);
       all_left &= v;
     }
@@ -243,13 +243,13 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
       // dispatch's own signal costs ~1.4 us and leaves nothing pending on the session's stream: a device-wide synchronize behind
       // this flush (a host that fences per burst: bench.py's timed regions) finds the queue empty instead of pushing a marker
       // through it (~11 us)
-      if (whole && ps.retired && ps.n_launches > 0)
-        NAM_HIP_CHECK(hipEventSynchronize(ps.retired));
+      if (whole && ps.retired.get() && ps.n_launches > 0)
+        NAM_HIP_CHECK(hipEventSynchronize(ps.retired.get()));
       if (told_leave)
       {
         // the session goes on after a flush: the "leave" word must not stay at this count, or a later launch whose workgroups
         // stand exactly there would leave at once instead of lingering (il_common.h: session_wait_command, `leave == tag - 1`)
-        __atomic_store_n(&ps.d_ring[kPRing], ~0ull, __ATOMIC_RELEASE);
+        __atomic_store_n(&ps.d_ring.get()[kPRing], ~0ull, __ATOMIC_RELEASE);
         push_out_host_stores();
       }
       return NAM_HIP_OK;
@@ -258,7 +258,7 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
     // left just before one landed. Make sure of the former, then run the launch again (it resumes where each stopped).
     if (!delivered)
     {
-      NAM_HIP_CHECK(hipStreamSynchronize(caller ? caller : b->stream));
+      NAM_HIP_CHECK(hipStreamSynchronize(caller ? caller : b->stream.get()));
       if (ps.last_caller && ps.last_caller != caller)
         NAM_HIP_CHECK(hipStreamSynchronize(ps.last_caller));
       delivered = true;
@@ -270,22 +270,22 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
       int behind = 0;
       for (int w = 0; w < ps.n_wg; w++)
       {
-        const unsigned d = ps.h_words[ps.done_off + w] & 0x7fffffffu;
+        const unsigned d = ps.words.host()[ps.done_off + w] & 0x7fffffffu;
         mn = std::min(mn, d), mx = std::max(mx, d);
         behind += (int)(d - target) < 0 ? 1 : 0;
       }
       std::fprintf(stderr, "nam_hip relaunch from a wait: target %u, submitted %u, workgroups' counts %u .. %u, %d behind the target\n", target, ps.seq, mn, mx, behind);
-      if (ps.h_why)
+      if (ps.why)
       {
         int hist[2][5] = {{0}};
         long long ex[2] = {0, 0};
         for (int w = 0; w < ps.n_wg; w++)
         {
-          const long long y = ps.h_why[w];
-          const int grp = (int)((ps.h_words[ps.done_off + w] & 0x7fffffffu) - target) < 0 ? 0 : 1;
+          const long long y = ps.why.host()[w];
+          const int grp = (int)((ps.words.host()[ps.done_off + w] & 0x7fffffffu) - target) < 0 ? 0 : 1;
           hist[grp][std::min<int>((int)(y >> 56) & 7, 4)]++;
           ex[grp] = y;
-          ps.h_why[w] = 0;
+          ps.why.host()[w] = 0;
         }
         for (int g = 0; g < 2; g++)
           std::fprintf(stderr, "   %s the target: left without a reason recorded %d, leave word %d, cap %d, everybody through %d, somebody left %d; e.g. %s loop, all through %lld, own count %lld\n",
@@ -306,11 +306,11 @@ int persist_stop(nam_hip_batch* b)
   PersistSession& ps = b->ps;
   if (!ps.active)
     return NAM_HIP_OK;
-  const int rc = persist_flush(b, ps.last_caller ? ps.last_caller : b->stream);
+  const int rc = persist_flush(b, ps.last_caller ? ps.last_caller : b->stream.get());
   // the state is the caller's again only when the launch has gone: a successful whole flush has waited on the launch's own
   // completion signal (persist_wait; 1.4 us — a stream synchronize pushes a marker through the queue, 11 us: profiles/r05/sync_tail.txt)
-  if (rc != NAM_HIP_OK || !ps.retired)
-    NAM_HIP_CHECK(hipStreamSynchronize(ps.kstream));
+  if (rc != NAM_HIP_OK || !ps.retired.get())
+    NAM_HIP_CHECK(hipStreamSynchronize(ps.kstream.get()));
   ps.active = false;
   return rc;
 }
@@ -340,55 +340,49 @@ int persist_prepare(nam_hip_batch* b)
 static int persist_prepare_alloc(nam_hip_batch* b)
 {
   PersistSession& ps = b->ps;
-    ps.host_store_ok = hipExtMallocWithFlags(reinterpret_cast<void**>(&ps.d_ring), (kPRing + kPRingTail) * sizeof(unsigned long long),
-                                             hipDeviceMallocFinegrained) == hipSuccess;
-    if (!ps.host_store_ok)
-    {
-      (void)hipGetLastError();
-      NAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ps.d_ring), (kPRing + kPRingTail) * sizeof(unsigned long long)));
-    }
-    NAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ps.d_cons), (size_t)b->n_streams * sizeof(unsigned)));
-    NAM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ps.d_cmd_count), (kPRing + kPRingTail) * sizeof(unsigned))); // ([kPRing]: the highest command every workgroup is through)
-    NAM_HIP_CHECK(hipMemset(ps.d_cmd_count, 0, (kPRing + kPRingTail) * sizeof(unsigned)));
-    NAM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ps.h_cmd_done), kPRing * sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
-    NAM_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ps.d_cmd_done), ps.h_cmd_done, 0));
-    std::memset(ps.h_cmd_done, 0, kPRing * sizeof(unsigned));
-    if (stats_on())
-    {
-      NAM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ps.h_why), (size_t)b->n_streams * sizeof(long long), hipHostMallocMapped | hipHostMallocCoherent));
-      NAM_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ps.d_why), ps.h_why, 0));
-      std::memset(ps.h_why, 0, (size_t)b->n_streams * sizeof(long long));
-    }
-    NAM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ps.h_words), 2 * (size_t)b->n_streams * sizeof(unsigned),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-    NAM_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ps.d_words), ps.h_words, 0));
-    // A stream of the highest priority has a hardware queue of its own: HIP multiplexes streams of one priority onto
-    // a few hardware queues, and a doorbell enqueued behind the session's launch on a shared queue would only be
-    // rung after the launch has left.
-    int prio_lo = 0, prio_hi = 0;
-    NAM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    NAM_HIP_CHECK(hipStreamCreateWithPriority(&ps.kstream, hipStreamNonBlocking, prio_hi));
-    NAM_HIP_CHECK(hipEventCreateWithFlags(&ps.order, hipEventDisableTiming));
-    NAM_HIP_CHECK(hipEventCreateWithFlags(&ps.retired, hipEventDisableTiming));
-    NAM_HIP_CHECK(hipMemset(ps.d_ring, 0, kPRing * sizeof(unsigned long long)));
-    NAM_HIP_CHECK(hipMemset(ps.d_ring + kPRing, 0xff, kPRingTail * sizeof(unsigned long long))); // (the "leave" word: no count)
-    NAM_HIP_CHECK(hipDeviceSynchronize());
-    NAM_HIP_CHECK(hipMemset(ps.d_cons, 0, (size_t)b->n_streams * sizeof(unsigned)));
-    std::memset(ps.h_words, 0, 2 * (size_t)b->n_streams * sizeof(unsigned));
-    ps.seq = 0; // (sequence numbers run on across sessions — no ring slot needs clearing — until they are rebased, below)
-    ps.burst_start = 0;
-    if (const char* e = std::getenv("NAM_HIP_PERSIST_REBASE_AT"))
-      ps.rebase_at = (unsigned)std::max(1l, std::atol(e));
-    if (const char* e = std::getenv("NAM_HIP_PERSIST_TIMEOUT_MS"))
-      ps.timeout_ms = std::max(1l, std::atol(e));
+  const size_t n_wg = (size_t)b->n_streams;
+  ps.host_store_ok = alloc_fine_grained(ps.d_ring, kPRing + kPRingTail) == hipSuccess;
+  if (!ps.host_store_ok)
   {
-    // a session of the headline kernel may start its low-latency sibling later (short_bursts): its code object is loaded now,
-    // not at the switch (~1.6 ms on first use) — both output forms, the window is not known yet
-    const WidthGroup& g0 = b->groups[b->model->full_width];
-    if (g0.plan->arch == ARCH_WAVENET && g0.plan->a1.valid && g0.plan->a1.p2_ok && q_runs(b, *g0.plan))
-      for (int oh = 0; oh < 2; oh++)
-        NAM_HIP_CHECK(preload_a1_p4_session(g0.plan->a1.p2_c0, g0.plan->a1.p2_c1, g0.plan->a1.arr[0].act, oh != 0, g0.d_bank_member != nullptr));
+    (void)hipGetLastError();
+    NAM_HIP_CHECK(hipMalloc(ps.d_ring.out(), (kPRing + kPRingTail) * sizeof(unsigned long long)));
   }
+  NAM_HIP_CHECK(hipMalloc(ps.d_cons.out(), n_wg * sizeof(unsigned)));
+  NAM_HIP_CHECK(hipMalloc(ps.d_cmd_count.out(), (kPRing + kPRingTail) * sizeof(unsigned))); // ([kPRing]: the highest command every workgroup is through)
+  NAM_HIP_CHECK(hipMemset(ps.d_cmd_count.get(), 0, (kPRing + kPRingTail) * sizeof(unsigned)));
+  NAM_HIP_CHECK(ps.cmd_done.alloc(kPRing));
+  std::memset(ps.cmd_done.host(), 0, kPRing * sizeof(unsigned));
+  if (stats_on())
+  {
+    NAM_HIP_CHECK(ps.why.alloc(n_wg));
+    std::memset(ps.why.host(), 0, n_wg * sizeof(long long));
+  }
+  NAM_HIP_CHECK(ps.words.alloc(2 * n_wg));
+  // A stream of the highest priority has a hardware queue of its own: HIP multiplexes streams of one priority onto
+  // a few hardware queues, and a doorbell enqueued behind the session's launch on a shared queue would only be
+  // rung after the launch has left.
+  int prio_lo = 0, prio_hi = 0;
+  NAM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+  NAM_HIP_CHECK(hipStreamCreateWithPriority(ps.kstream.out(), hipStreamNonBlocking, prio_hi));
+  NAM_HIP_CHECK(hipEventCreateWithFlags(ps.order.out(), hipEventDisableTiming));
+  NAM_HIP_CHECK(hipEventCreateWithFlags(ps.retired.out(), hipEventDisableTiming));
+  NAM_HIP_CHECK(hipMemset(ps.d_ring.get(), 0, kPRing * sizeof(unsigned long long)));
+  NAM_HIP_CHECK(hipMemset(ps.d_ring.get() + kPRing, 0xff, kPRingTail * sizeof(unsigned long long))); // (the "leave" word: no count)
+  NAM_HIP_CHECK(hipDeviceSynchronize());
+  NAM_HIP_CHECK(hipMemset(ps.d_cons.get(), 0, n_wg * sizeof(unsigned)));
+  std::memset(ps.words.host(), 0, 2 * n_wg * sizeof(unsigned));
+  ps.seq = 0; // (sequence numbers run on across sessions — no ring slot needs clearing — until they are rebased, below)
+  ps.burst_start = 0;
+  if (const char* e = std::getenv("NAM_HIP_PERSIST_REBASE_AT"))
+    ps.rebase_at = (unsigned)std::max(1l, std::atol(e));
+  if (const char* e = std::getenv("NAM_HIP_PERSIST_TIMEOUT_MS"))
+    ps.timeout_ms = std::max(1l, std::atol(e));
+  // a session of the headline kernel may start its low-latency sibling later (short_bursts): its code object is loaded now,
+  // not at the switch (~1.6 ms on first use) — both output forms, the window is not known yet
+  const WidthGroup& g0 = b->groups[b->model->full_width];
+  if (g0.plan->arch == ARCH_WAVENET && g0.plan->a1.valid && g0.plan->a1.p2_ok && q_runs(b, *g0.plan))
+    for (int oh = 0; oh < 2; oh++)
+      NAM_HIP_CHECK(preload_a1_p4_session(g0.plan->a1.p2_c0, g0.plan->a1.p2_c1, g0.plan->a1.arr[0].act, oh != 0, (bool)g0.d_bank_member));
   return NAM_HIP_OK;
 }
 
@@ -406,17 +400,17 @@ int persist_start(nam_hip_batch* b, const float* d_in, float* d_out, long stride
     ps.rebase_pending = false;
     // a session starts flushed (persist_stop: every workgroup at exactly `seq`, the launch gone): renumber from 0. Stale
     // ring slots carry tags near the old count, which a small count never matches; cleared anyway.
-    NAM_HIP_CHECK(hipStreamSynchronize(ps.kstream));
-    NAM_HIP_CHECK(hipMemset(ps.d_ring, 0, kPRing * sizeof(unsigned long long)));
-    NAM_HIP_CHECK(hipMemset(ps.d_ring + kPRing, 0xff, kPRingTail * sizeof(unsigned long long))); // (the "leave" word: no count)
-    NAM_HIP_CHECK(hipMemset(ps.d_cons, 0, (size_t)b->n_streams * sizeof(unsigned)));
-    NAM_HIP_CHECK(hipMemset(ps.d_cmd_count, 0, (kPRing + kPRingTail) * sizeof(unsigned)));
+    NAM_HIP_CHECK(hipStreamSynchronize(ps.kstream.get()));
+    NAM_HIP_CHECK(hipMemset(ps.d_ring.get(), 0, kPRing * sizeof(unsigned long long)));
+    NAM_HIP_CHECK(hipMemset(ps.d_ring.get() + kPRing, 0xff, kPRingTail * sizeof(unsigned long long))); // (the "leave" word: no count)
+    NAM_HIP_CHECK(hipMemset(ps.d_cons.get(), 0, (size_t)b->n_streams * sizeof(unsigned)));
+    NAM_HIP_CHECK(hipMemset(ps.d_cmd_count.get(), 0, (kPRing + kPRingTail) * sizeof(unsigned)));
     NAM_HIP_CHECK(hipDeviceSynchronize());
-    std::memset(ps.h_cmd_done, 0, kPRing * sizeof(unsigned)); // (tags of the old numbering)
+    std::memset(ps.cmd_done.host(), 0, kPRing * sizeof(unsigned)); // (tags of the old numbering)
     for (int w = 0; w < b->n_streams; w++)
     {
-      ps.h_words[w] = 0u;
-      ps.h_words[b->n_streams + w] = 0x80000000u;
+      ps.words.host()[w] = 0u;
+      ps.words.host()[b->n_streams + w] = 0x80000000u;
     }
     ps.seq = 0;
     ps.burst_start = 0;
@@ -430,11 +424,11 @@ int persist_start(nam_hip_batch* b, const float* d_in, float* d_out, long stride
     // another kernel, another workgroup count: every workgroup of the new shape starts behind the commands consumed
     // so far (nothing of the old session is in flight: a session ends with a flush)
     std::vector<unsigned> at((size_t)b->n_streams, ps.seq);
-    NAM_HIP_CHECK(hipMemcpy(ps.d_cons, at.data(), at.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    NAM_HIP_CHECK(hipMemcpy(ps.d_cons.get(), at.data(), at.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     for (int w = 0; w < b->n_streams; w++)
     {
-      ps.h_words[w] = ps.seq;
-      ps.h_words[b->n_streams + w] = ps.seq | 0x80000000u;
+      ps.words.host()[w] = ps.seq;
+      ps.words.host()[b->n_streams + w] = ps.seq | 0x80000000u;
     }
     ps.kind = kind;
     ps.flushed = ps.seq;
@@ -535,8 +529,8 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
       unsigned lo = ~0u, all_left = 0x80000000u;
       for (int w = 0; w < ps.n_wg; w++)
       {
-        const unsigned d = __atomic_load_n(&ps.h_words[ps.done_off + w], __ATOMIC_RELAXED);
-        lo = std::min(lo, std::max(__atomic_load_n(&ps.h_words[w], __ATOMIC_RELAXED), d & 0x7fffffffu));
+        const unsigned d = __atomic_load_n(&ps.words.host()[ps.done_off + w], __ATOMIC_RELAXED);
+        lo = std::min(lo, std::max(__atomic_load_n(&ps.words.host()[w], __ATOMIC_RELAXED), d & 0x7fffffffu));
         all_left &= d;
       }
       if (ps.seq - lo < kPRing - 128)
@@ -566,7 +560,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
     idle = uniform = true;
     for (int w = 0; w < ps.n_wg && idle; w++)
     {
-      const unsigned v = __atomic_load_n(&ps.h_words[ps.done_off + w], __ATOMIC_ACQUIRE);
+      const unsigned v = __atomic_load_n(&ps.words.host()[ps.done_off + w], __ATOMIC_ACQUIRE);
       idle = (v & 0x80000000u) != 0;
       uniform = uniform && v == left;
     }
@@ -581,7 +575,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
   if (ps.host_store_ok && (!ps.last_caller || ps.last_caller == caller) && hipStreamQuery(caller) == hipSuccess)
   {
     ps.n_host_doorbells++;
-    __atomic_store_n(&ps.d_ring[slot], cmd, __ATOMIC_RELEASE);
+    __atomic_store_n(&ps.d_ring.get()[slot], cmd, __ATOMIC_RELEASE);
 #if defined(__x86_64__) || defined(__i386__)
     __builtin_ia32_sfence(); // (the BAR mapping may be write-combining: push the store out now)
 #else
@@ -608,7 +602,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
         return rc;
     }
     ps.n_stream_doorbells++;
-    NAM_HIP_CHECK(hipStreamWriteValue64(caller, ps.d_ring + slot, cmd, 0));
+    NAM_HIP_CHECK(hipStreamWriteValue64(caller, ps.d_ring.get() + slot, cmd, 0));
   }
   ps.seq++;
   ps.flushed_valid = false;
@@ -621,26 +615,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
 
 void persist_free(nam_hip_batch* b)
 {
-  PersistSession& ps = b->ps;
-  if (ps.d_ring)
-    (void)hipFree(ps.d_ring);
-  if (ps.d_cons)
-    (void)hipFree(ps.d_cons);
-  if (ps.d_cmd_count)
-    (void)hipFree(ps.d_cmd_count);
-  if (ps.h_cmd_done)
-    (void)hipHostFree(ps.h_cmd_done);
-  if (ps.h_why)
-    (void)hipHostFree(ps.h_why);
-  if (ps.h_words)
-    (void)hipHostFree(ps.h_words);
-  if (ps.kstream)
-    (void)hipStreamDestroy(ps.kstream);
-  if (ps.order)
-    (void)hipEventDestroy(ps.order);
-  if (ps.retired)
-    (void)hipEventDestroy(ps.retired);
-  ps = PersistSession();
+  b->ps = PersistSession(); // (every owner releases; every field is back at its default, `enabled` included)
 }
 
 } // namespace api

@@ -333,9 +333,9 @@ static int create_batch(const nam_hip_model* model, std::shared_ptr<const nam_hi
   b->n_streams = n_streams;
   b->max_frames = max_frames;
   // everything that can fail runs inside this lambda; on failure the half-built batch goes through
-  // nam_hip_batch_destroy, which frees whatever was already allocated (stream, blobs, state, staging)
+  // nam_hip_batch_destroy: its owners release whatever was already allocated (stream, blobs, state, staging)
   const int rc = [&]() -> int {
-    NAM_HIP_CHECK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    NAM_HIP_CHECK(hipStreamCreateWithFlags(b->stream.out(), hipStreamNonBlocking));
     b->groups.resize(model->plans.size());
     for (size_t i = 0; i < model->plans.size(); i++)
     {
@@ -354,11 +354,10 @@ static int create_batch(const nam_hip_model* model, std::shared_ptr<const nam_hi
       return r;
     const size_t in_floats = (size_t)n_streams * model->spec->in_channels() * max_frames;
     const size_t out_floats = (size_t)n_streams * model->spec->out_channels() * max_frames;
-    NAM_HIP_CHECK(hipMalloc(&b->d_in, in_floats * sizeof(float)));
-    NAM_HIP_CHECK(hipMalloc(&b->d_out, out_floats * sizeof(float)));
-    NAM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b->h_stage), std::max(in_floats, out_floats) * sizeof(float),
-                                hipHostMallocDefault));
-    NAM_HIP_CHECK(hipStreamSynchronize(b->stream));
+    NAM_HIP_CHECK(hipMalloc(b->d_in.out(), in_floats * sizeof(float)));
+    NAM_HIP_CHECK(hipMalloc(b->d_out.out(), out_floats * sizeof(float)));
+    NAM_HIP_CHECK(hipHostMalloc(b->h_stage.out(), std::max(in_floats, out_floats) * sizeof(float), hipHostMallocDefault));
+    NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
     return NAM_HIP_OK;
   }();
   if (rc != NAM_HIP_OK)
@@ -366,6 +365,7 @@ static int create_batch(const nam_hip_model* model, std::shared_ptr<const nam_hi
     const std::string msg = g_last_error; // destroy must not clobber the reason
     nam_hip_batch_destroy(b);
     g_last_error = msg;
+    (void)hipGetLastError(); // (reported through rc: the refused call's code must not answer the next batch's first launch check)
     return rc;
   }
   *out_batch = b;
@@ -422,47 +422,17 @@ void nam_hip_batch_destroy(nam_hip_batch* batch)
     return;
   (void)hipSetDevice(batch->device);
   (void)quiesce(batch);
-  if (const char* e = std::getenv("NAM_HIP_SESSION_STATS"))
-    if (e[0] == '1' && batch->ps.n_starts)
-      std::fprintf(stderr, "nam_hip session: %llu starts, %llu launches (%llu from a wait / flush), %llu commands stored by the host, %llu through the stream\n",
-                   batch->ps.n_starts, batch->ps.n_launches, batch->ps.n_flush_relaunches, batch->ps.n_host_doorbells, batch->ps.n_stream_doorbells);
-  if (const char* e = std::getenv("NAM_HIP_SESSION_STATS"))
-    if (e[0] == '1' && batch->ps.n_waits)
-      std::fprintf(stderr, "nam_hip tickets: %llu waits, %.1f looks at the completion word each\n", batch->ps.n_waits, (double)batch->ps.n_polls / batch->ps.n_waits);
+  if (stats_on() && batch->ps.n_starts)
+    std::fprintf(stderr, "nam_hip session: %llu starts, %llu launches (%llu from a wait / flush), %llu commands stored by the host, %llu through the stream\n",
+                 batch->ps.n_starts, batch->ps.n_launches, batch->ps.n_flush_relaunches, batch->ps.n_host_doorbells, batch->ps.n_stream_doorbells);
   if (stats_on() && batch->ps.n_waits)
+  {
+    std::fprintf(stderr, "nam_hip tickets: %llu waits, %.1f looks at the completion word each\n", batch->ps.n_waits, (double)batch->ps.n_polls / batch->ps.n_waits);
     std::fprintf(stderr, "nam_hip tickets, us per buffer (max): wait for the count %.2f (%.1f), copy out %.2f (%.1f), copy in %.2f (%.1f), commands %.2f (%.1f)\n",
                  batch->ps.t_poll / batch->ps.n_waits, batch->ps.t_poll_max, batch->ps.t_out / batch->ps.n_waits, batch->ps.t_out_max,
                  batch->ps.t_in / batch->ps.n_waits, batch->ps.t_in_max, batch->ps.t_cmd / batch->ps.n_waits, batch->ps.t_cmd_max);
-  persist_free(batch);
-  for (auto& g : batch->groups)
-    free_group(g);
-  if (batch->d_in)
-    (void)hipFree(batch->d_in);
-  if (batch->d_out)
-    (void)hipFree(batch->d_out);
-  if (batch->h_stage)
-    (void)hipHostFree(batch->h_stage);
-  if (batch->in_bar)
-    (void)hipFree(batch->in_bar);
-  if (batch->h_out_map)
-    (void)hipHostFree(batch->h_out_map);
-  if (batch->pipe_in_bar)
-    (void)hipFree(batch->pipe_in_bar);
-  if (batch->pipe_h_out_map)
-    (void)hipHostFree(batch->pipe_h_out_map);
-  if (batch->pipe_h_in)
-    (void)hipHostFree(batch->pipe_h_in);
-  if (batch->pipe_h_out)
-    (void)hipHostFree(batch->pipe_h_out);
-  if (batch->pipe_d_in)
-    (void)hipFree(batch->pipe_d_in);
-  if (batch->pipe_d_out)
-    (void)hipFree(batch->pipe_d_out);
-  for (PipeSlot& sl : batch->pipe)
-    if (sl.done)
-      (void)hipEventDestroy(sl.done);
-  if (batch->stream)
-    (void)hipStreamDestroy(batch->stream);
+  }
+  // the session, the groups, staging and windows, the ticket events, the stream: in the order the struct states (api_internal.h)
   delete batch;
 }
 
@@ -478,11 +448,11 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
   {
     if (g.streams.empty())
       continue;
-    const int rc = reset_streams(batch, g, g.d_map, (int)g.streams.size(), prewarm != 0, g.streams.front());
+    const int rc = reset_streams(batch, g, g.d_map.get(), (int)g.streams.size(), prewarm != 0, g.streams.front());
     if (rc != NAM_HIP_OK)
       return rc;
   }
-  NAM_HIP_CHECK(hipStreamSynchronize(batch->stream));
+  NAM_HIP_CHECK(hipStreamSynchronize(batch->stream.get()));
   if (batch->ps.enabled && persist_eligible(batch)) // (a session's window-independent resources: see nam_hip_batch_set_persistent)
   {
     const int rc = persist_prepare(batch);
@@ -546,16 +516,7 @@ int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids
       return rc;
   }
   // fresh sub-model state for the streams that moved: Reset (+ prewarm) as in slimmable.cpp:433-447
-  int* d_moved = nullptr;
-  NAM_HIP_CHECK(hipMalloc(&d_moved, moved.size() * sizeof(int)));
-  NAM_HIP_CHECK(hipMemcpy(d_moved, moved.data(), moved.size() * sizeof(int), hipMemcpyHostToDevice));
-  rc = reset_streams(batch, batch->groups[w], d_moved, (int)moved.size(), batch->was_reset && batch->reset_with_prewarm, moved.front());
-  hipError_t e = hipStreamSynchronize(batch->stream);
-  (void)hipFree(d_moved);
-  if (rc != NAM_HIP_OK)
-    return rc;
-  NAM_HIP_CHECK(e);
-  return NAM_HIP_OK;
+  return reset_moved_streams(batch, batch->groups[w], moved, false);
 }
 
 int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float* d_out, int n_frames,
@@ -566,7 +527,7 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
   if (frame_stride < n_frames)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_process_device: frame_stride < n_frames");
   NAM_HIP_CHECK(hipSetDevice(batch->device));
-  hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : batch->stream;
+  hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : batch->stream.get();
   if (hip_stream)
     batch->last_ext_stream = s;
   if (batch->ps.enabled && persist_eligible(batch))
@@ -596,7 +557,7 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
   {
     if (g.streams.empty())
       continue;
-    const int rc = launch_group(batch, g, g.d_map, (int)g.streams.size(), d_in, d_out, n_frames, (long)frame_stride, s);
+    const int rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), d_in, d_out, n_frames, (long)frame_stride, s);
     if (rc != NAM_HIP_OK)
       return rc;
   }
@@ -619,18 +580,18 @@ int nam_hip_batch_process_f32(nam_hip_batch* batch, const float* in, float* out,
     if (rc <= 0)
       return rc; // done through the session (0) or failed (< 0); 1 = not applicable: the copying path below
   }
-  NAM_HIP_CHECK(hipMemcpyAsync(batch->d_in, in, in_bytes, hipMemcpyHostToDevice, batch->stream));
-  const int rc = nam_hip_batch_process_device(batch, batch->d_in, batch->d_out, n_frames, n_frames, nullptr);
+  NAM_HIP_CHECK(hipMemcpyAsync(batch->d_in.get(), in, in_bytes, hipMemcpyHostToDevice, batch->stream.get()));
+  const int rc = nam_hip_batch_process_device(batch, batch->d_in.get(), batch->d_out.get(), n_frames, n_frames, nullptr);
   if (rc != NAM_HIP_OK)
     return rc;
   if (batch->ps.active) // persistent mode: the buffer is done when every workgroup has published its count
   {
-    const int rw = persist_flush(batch, batch->stream);
+    const int rw = persist_flush(batch, batch->stream.get());
     if (rw != NAM_HIP_OK)
       return rw;
   }
-  NAM_HIP_CHECK(hipMemcpyAsync(out, batch->d_out, out_bytes, hipMemcpyDeviceToHost, batch->stream));
-  NAM_HIP_CHECK(hipStreamSynchronize(batch->stream));
+  NAM_HIP_CHECK(hipMemcpyAsync(out, batch->d_out.get(), out_bytes, hipMemcpyDeviceToHost, batch->stream.get()));
+  NAM_HIP_CHECK(hipStreamSynchronize(batch->stream.get()));
   return NAM_HIP_OK;
 }
 
@@ -728,17 +689,18 @@ int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* const* in, float
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_render_f32: signal too long for one launch");
   NAM_HIP_CHECK(hipSetDevice(batch->device));
   // device-resident planar audio [stream][channel][T]; rows of shorter signals are zero-padded
-  float *d_in = nullptr, *d_out = nullptr;
+  DeviceBuf<float> in_buf, out_buf; // (freed on every way out, behind the stream's synchronize below)
   const size_t in_bytes = (size_t)N * ic * T * sizeof(float), out_bytes = (size_t)N * oc * T * sizeof(float);
-  NAM_HIP_CHECK(hipMalloc(&d_in, in_bytes));
-  hipError_t e = hipMalloc(&d_out, out_bytes);
+  NAM_HIP_CHECK(hipMalloc(in_buf.out(), in_bytes));
+  hipError_t e = hipMalloc(out_buf.out(), out_bytes);
+  float *const d_in = in_buf.get(), *const d_out = out_buf.get();
   int rc = NAM_HIP_OK;
   if (e == hipSuccess)
-    e = hipMemsetAsync(d_in, 0, in_bytes, batch->stream);
+    e = hipMemsetAsync(d_in, 0, in_bytes, batch->stream.get());
   for (int s = 0; s < N && e == hipSuccess; s++)
     if (n_frames[s] > 0)
       e = hipMemcpy2DAsync(d_in + (size_t)s * ic * T, (size_t)T * sizeof(float), in[s], (size_t)n_frames[s] * sizeof(float),
-                           (size_t)n_frames[s] * sizeof(float), ic, hipMemcpyHostToDevice, batch->stream);
+                           (size_t)n_frames[s] * sizeof(float), ic, hipMemcpyHostToDevice, batch->stream.get());
   if (e == hipSuccess)
     rc = nam_hip_batch_process_device(batch, d_in, d_out, (int)T, T, nullptr);
   if (e == hipSuccess && rc == NAM_HIP_OK && batch->ps.active) // (a short render went through the session: it ends here —
@@ -746,11 +708,8 @@ int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* const* in, float
   for (int s = 0; s < N && e == hipSuccess && rc == NAM_HIP_OK; s++)
     if (n_frames[s] > 0)
       e = hipMemcpy2DAsync(out[s], (size_t)n_frames[s] * sizeof(float), d_out + (size_t)s * oc * T, (size_t)T * sizeof(float),
-                           (size_t)n_frames[s] * sizeof(float), oc, hipMemcpyDeviceToHost, batch->stream);
-  const hipError_t es = hipStreamSynchronize(batch->stream);
-  (void)hipFree(d_in);
-  if (d_out)
-    (void)hipFree(d_out);
+                           (size_t)n_frames[s] * sizeof(float), oc, hipMemcpyDeviceToHost, batch->stream.get());
+  const hipError_t es = hipStreamSynchronize(batch->stream.get());
   if (rc != NAM_HIP_OK)
     return rc;
   NAM_HIP_CHECK(e);
@@ -776,22 +735,22 @@ int nam_hip_batch_process_f64(nam_hip_batch* batch, const double* in, double* ou
   }
   // double -> float exactly as _set_condition_array does (NAM/wavenet/model.cpp:817)
   for (size_t i = 0; i < n_in; i++)
-    batch->h_stage[i] = (float)in[i];
-  NAM_HIP_CHECK(hipMemcpyAsync(batch->d_in, batch->h_stage, n_in * sizeof(float), hipMemcpyHostToDevice, batch->stream));
-  const int rc = nam_hip_batch_process_device(batch, batch->d_in, batch->d_out, n_frames, n_frames, nullptr);
+    batch->h_stage.get()[i] = (float)in[i];
+  NAM_HIP_CHECK(hipMemcpyAsync(batch->d_in.get(), batch->h_stage.get(), n_in * sizeof(float), hipMemcpyHostToDevice, batch->stream.get()));
+  const int rc = nam_hip_batch_process_device(batch, batch->d_in.get(), batch->d_out.get(), n_frames, n_frames, nullptr);
   if (rc != NAM_HIP_OK)
     return rc;
   if (batch->ps.active)
   {
-    const int rw = persist_flush(batch, batch->stream);
+    const int rw = persist_flush(batch, batch->stream.get());
     if (rw != NAM_HIP_OK)
       return rw;
   }
   NAM_HIP_CHECK(
-    hipMemcpyAsync(batch->h_stage, batch->d_out, n_out * sizeof(float), hipMemcpyDeviceToHost, batch->stream));
-  NAM_HIP_CHECK(hipStreamSynchronize(batch->stream));
+    hipMemcpyAsync(batch->h_stage.get(), batch->d_out.get(), n_out * sizeof(float), hipMemcpyDeviceToHost, batch->stream.get()));
+  NAM_HIP_CHECK(hipStreamSynchronize(batch->stream.get()));
   for (size_t i = 0; i < n_out; i++)
-    out[i] = (double)batch->h_stage[i];
+    out[i] = (double)batch->h_stage.get()[i];
   return NAM_HIP_OK;
 }
 
@@ -829,7 +788,7 @@ int nam_hip_batch_set_persistent(nam_hip_batch* batch, int enable)
     // the blocking entry points' host windows too, when they are small (a batch of long buffers that only ever runs
     // device-resident audio must not pin hundreds of MB for calls it never makes: such a batch allocates them at its first
     // host-buffer call, if it makes one)
-    (void)host_windows(batch, 1, batch->in_bar, batch->h_out_map, batch->d_out_map, batch->map_failed, /*prealloc=*/true);
+    (void)host_windows(batch, 1, batch->win, /*prealloc=*/true);
   }
   return eligible ? 1 : 0;
 }
@@ -842,7 +801,7 @@ int nam_hip_batch_flush(nam_hip_batch* batch, void* hip_stream)
   if (!batch->ps.active)
     return NAM_HIP_OK;
   // the doorbells were enqueued on the caller's stream: they are only guaranteed to have been rung once it has drained
-  hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : batch->stream;
+  hipStream_t s = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : batch->stream.get();
   return persist_flush(batch, s);
 }
 
@@ -926,18 +885,23 @@ int nam_hip_batch_debug_timeline(nam_hip_batch* batch, int n_frames, long long* 
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_debug_timeline: bad argument");
   NAM_HIP_CHECK(hipSetDevice(batch->device));
   const size_t bytes = 96 * 8 * sizeof(long long);
-  NAM_HIP_CHECK(hipMalloc(&batch->dbg, bytes));
-  NAM_HIP_CHECK(hipMemset(batch->dbg, 0, bytes));
-  NAM_HIP_CHECK(hipDeviceSynchronize()); // (the fill runs on the null stream, the launch on the batch's non-blocking one)
-  int rc = NAM_HIP_OK;
-  for (auto& g : batch->groups)
-    if (!g.streams.empty() && rc == NAM_HIP_OK)
-      rc = launch_group(batch, g, g.d_map, (int)g.streams.size(), nullptr, nullptr, n_frames, 0, batch->stream);
-  hipError_t e = hipStreamSynchronize(batch->stream);
+  // batch->dbg is what launch_a1_family hands to every launch: set for this call's launches only, empty again on every way out
+  hipError_t e = hipMalloc(batch->dbg.out(), bytes);
   if (e == hipSuccess)
-    e = hipMemcpy(out_stamps, batch->dbg, bytes, hipMemcpyDeviceToHost);
-  (void)hipFree(batch->dbg);
-  batch->dbg = nullptr;
+    e = hipMemset(batch->dbg.get(), 0, bytes);
+  if (e == hipSuccess)
+    e = hipDeviceSynchronize(); // (the fill runs on the null stream, the launch on the batch's non-blocking one)
+  int rc = NAM_HIP_OK;
+  if (e == hipSuccess)
+  {
+    for (auto& g : batch->groups)
+      if (!g.streams.empty() && rc == NAM_HIP_OK)
+        rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), nullptr, nullptr, n_frames, 0, batch->stream.get());
+    e = hipStreamSynchronize(batch->stream.get());
+    if (e == hipSuccess)
+      e = hipMemcpy(out_stamps, batch->dbg.get(), bytes, hipMemcpyDeviceToHost);
+  }
+  (void)batch->dbg.reset();
   if (rc != NAM_HIP_OK)
     return rc;
   NAM_HIP_CHECK(e);
