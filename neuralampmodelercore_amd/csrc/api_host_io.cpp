@@ -80,8 +80,10 @@ int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_
         dst[i] = (float)in_f64[r * n_frames + i];
   }
   push_out_host_stores();
-  b->one_buffer_call = n_frames == kBlock; // (one command, then the caller waits: the stages of a pipeline would only queue up)
-  b->short_blocking_call = n_frames <= 4 * kBlock;
+  CallHints hints; // what this call tells the launches started on its behalf, and no launch after it
+  hints.one_buffer_call = n_frames == kBlock; // (one command, then the caller waits: the stages of a pipeline would only queue up)
+  hints.short_blocking_call = n_frames <= 4 * kBlock;
+  const SessionCaller caller(b->stream.get(), hints);
   // nam::DSP::process back to back (NAM/dsp.h:97; tools/benchmodel.cpp:129-132: a loop of blocking calls): when the previous
   // call returned a moment ago, the launch this call starts — or still finds — publishes every command's completion and
   // lingers for the next one. A caller that comes once per audio period (1.3 ms at 64 frames) never makes a launch linger.
@@ -90,21 +92,17 @@ int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_
   if (linger_now != b->blocking_linger && b->ps.active && b->ps.outstanding)
   {
     // (the running launch was started under the other rule: let it go first — a whole flush; rare: the pattern changed)
-    const int rf = persist_flush(b, b->stream.get());
+    const int rf = persist_flush(b, caller);
     if (rf != NAM_HIP_OK)
       return rf;
   }
   b->blocking_linger = linger_now;
-  const int rc = persist_submit(b, b->win.in_bar.get(), b->win.out_map.dev(), n_frames, stride, b->stream.get());
+  const int rc = persist_submit(b, b->win.in_bar.get(), b->win.out_map.dev(), n_frames, stride, caller);
   if (rc != NAM_HIP_OK)
-  {
-    b->one_buffer_call = b->short_blocking_call = false;
     return rc < 0 ? rc : fail(NAM_HIP_ERR_DEVICE, "persistent session: the host-mapped buffer was refused");
-  }
   // this call's own commands: the per-command completion word when the launch publishes it (it may linger on), else the
   // whole launch (it leaves when it has drained the ring)
-  const int rw = b->ps.cmd_done_published ? persist_wait(b, b->stream.get(), b->ps.seq, false) : persist_flush(b, b->stream.get());
-  b->one_buffer_call = b->short_blocking_call = false;
+  const int rw = b->ps.cmd_done_published ? persist_wait(b, caller, b->ps.seq, false) : persist_flush(b, caller);
   if (rw != NAM_HIP_OK)
     return rw;
   __atomic_thread_fence(__ATOMIC_ACQUIRE);

@@ -231,12 +231,12 @@ struct PersistSession
   // every buffer or two (a device-resident real-time chain: process_device + flush per 64 .. 256 frames) waits for the FIRST buffer of
   // every launch: the official 16 / 8 topology then starts as nam_a1_p4_kernel (four waves per layer: the first buffer is through in
   // ~6 us) instead of nam_a1_q_kernel (one wave per layer: ~27 us, faster only once buffers overlap) — the rule of the blocking host
-  // calls (short_blocking_call), learnt from the caller's own pattern: three bursts in a row of at most four buffers
+  // calls (CallHints::short_blocking_call), learnt from the caller's own pattern: three bursts in a row of at most four buffers
   unsigned bursts[3] = {~0u, ~0u, ~0u};
   unsigned burst_start = 0; // `seq` at the last whole flush
   bool short_bursts() const { return bursts[0] <= 4u && bursts[1] <= 4u && bursts[2] <= 4u; }
   bool one_buffer_bursts() const { return bursts[0] == 1u && bursts[1] == 1u && bursts[2] == 1u; } // (nam_wn_reg_kernel: one wave per stream then)
-  EventOwner retired; // the completion signal of the session's latest launch (kernels.h: nam_launch), recorded by the dispatch itself
+  EventOwner retired; // the completion signal of the session's latest launch (kernels.h: LaunchStream), recorded by the dispatch itself
   bool cmd_done_published = false; // the running launch stores p_cmd_done behind every command's results (A1Args::p_out_host == 2); p_prog stays ring bookkeeping every 16 commands
 };
 
@@ -294,7 +294,6 @@ struct nam_hip_batch
   DeviceBuf<float> pipe_d_in, pipe_d_out;
   std::vector<float> pipe_cvt; // the _f64 forms of submit / wait: one buffer of float32 on the way in / out
   int kernel = NAM_HIP_KERNEL_AUTO;
-  DeviceBuf<long long> dbg; // device buffer of the profiling instantiation (nam_hip_batch_debug_timeline: empty outside that call)
   std::vector<WidthGroup> groups;
   std::vector<int> stream_width;
   bool was_reset = false;
@@ -302,15 +301,11 @@ struct nam_hip_batch
   // the caller-supplied stream of the last nam_hip_batch_process_device: control calls that free or rewrite device
   // memory (Reset, SetSlimmableSize, destroy) wait for it as well as for the batch's own stream
   hipStream_t last_ext_stream = nullptr; // (the caller's: not owned)
-  bool short_blocking_call = false; // a blocking host call of up to four buffers is being served: the caller waits for it, so the FIRST buffer's
-                                    // latency is what counts — nam_a1_p4_kernel (four waves per layer: ~6 us through the model) rather than
-                                    // nam_a1_q_kernel (one wave per layer: ~30 us; faster only once buffers overlap)
   int wr_last_stages = 0; // (NAM_HIP_SESSION_STATS: what nam_wn_reg_kernel's last multi-buffer launch ran as)
   bool wr_last_dense = false;
   bool blocking_linger = false; // blocking host calls are coming back to back (the previous one returned < kBlockingLingerGapUs ago): the session's
                                 // launch publishes every command and lingers for the next call, like a ticket session's
   double t_blocking_return = -1e18; // host clock (us) when the last blocking host call of the session path returned
-  bool one_buffer_call = false; // a blocking host call of ONE 64-frame buffer is being served: nothing to overlap, a launch started now runs nam_wn_reg_kernel as one wave per stream
   int blocking_linger_us = 200; // 0 = blocking host calls never make a launch linger (NAM_HIP_BLOCKING_LINGER_US)
   int blocking_linger_gap_us = 50; // "back to back": the previous blocking call returned less than this ago
   int ticket_linger = kTicketLingerDefault; // ticks of the 100 MHz clock a ticket session's launch looks for the next buffer (NAM_HIP_TICKET_LINGER_US)
@@ -321,7 +316,6 @@ struct nam_hip_batch
   int wr_max_stages = 4;
   bool no_pipe = false;
   PersistSession ps;
-  bool ps_launching = false; // launch_group is starting the session's resident launch
   int n_cus = 0; // compute units of the device
 };
 
@@ -399,12 +393,26 @@ int bank_blob_base(const Plan& p, int family);
 // the blob of a member's plan the family's kernels read (BankFamilyRules::blob_source)
 const std::vector<float>& bank_blob(const Plan& p, int family);
 
-// What select_kernel needs to know about a launch besides the batch and the group
-struct LaunchQuestion
+// What a blocking host call knows about itself (process_host_mapped); every other API call has none
+struct CallHints
 {
-  int n_frames; // the launch length
-  int session_kind; // PersistKind of the session whose resident launch this is; PERSIST_NONE: an ordinary launch
-  bool short_blocking_call; // a blocking host call of up to four buffers is being served (nam_hip_batch::short_blocking_call)
+  bool short_blocking_call = false; // up to four buffers and the caller waits: the FIRST buffer's latency counts — nam_a1_p4_kernel (~6 us through the model), not nam_a1_q_kernel (~30 us; faster once buffers overlap)
+  bool one_buffer_call = false; // ONE 64-frame buffer: nothing to overlap, a launch started now runs nam_wn_reg_kernel as one wave per stream
+};
+// What a launch is for: built where the API call knows the facts, handed down by const&, stored nowhere. Default: an ordinary launch.
+struct LaunchContext
+{
+  int session_kind = PERSIST_NONE; // PersistKind of the session whose resident launch this is (persist_launch)
+  CallHints hints; // of the API call the launch is started for
+  hipEvent_t retired = nullptr; // a resident launch: the session's completion event (PersistSession::retired; kernels.h: LaunchStream)
+  long long* dbg = nullptr; // nam_hip_batch_debug_timeline: the profiling instantiation's device buffer
+};
+// The API call a session function works for: the stream its doorbells are rung on (not owned), and its hints for a launch the function starts
+struct SessionCaller // (a bare stream: a caller without hints)
+{
+  hipStream_t stream;
+  CallHints hints;
+  SessionCaller(hipStream_t s, CallHints h = CallHints()) : stream(s), hints(h) {}
 };
 
 // api_launch.cpp
@@ -415,15 +423,15 @@ int state_family_of(const Plan& p, int kernel);
 int refresh_map(nam_hip_batch* b, WidthGroup& g);
 int pick_kernel(const nam_hip_batch* b, const WidthGroup& g);
 const char* group_kernel_name(const nam_hip_batch* b, const WidthGroup& g, int n_frames);
-PersistArgs persist_args(const nam_hip_batch* b);
+PersistArgs persist_args(const nam_hip_batch* b, const LaunchContext& ctx);
 int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* maps, const int* counts, int n_groups,
-              const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s);
+              const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx);
 WrGroupList wr_groups(nam_hip_batch* b);
 int launch_wr_all(nam_hip_batch* b, const WrGroupList& gs, const float* d_in, float* d_out, int n_frames, long io_stride,
-                  hipStream_t s);
+                  hipStream_t s, const LaunchContext& ctx);
 int kernel_for_launch(const nam_hip_batch* b, const WidthGroup& g, int n_frames);
 int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out,
-                 int n_frames, long io_stride, hipStream_t s);
+                 int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx);
 int prewarm_frames(const nam_hip_batch* b, const Plan& p);
 int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool prewarm, int first_stream);
 // fresh state for the streams `moved` (ascending, not empty) that have just joined `g`: their ids to the device, optionally their
@@ -432,13 +440,13 @@ int reset_moved_streams(nam_hip_batch* b, WidthGroup& g, const std::vector<int>&
 // api_session.cpp
 int persist_family(const nam_hip_batch* b, const WidthGroup& g);
 int persist_kind(const nam_hip_batch* b);
-int persist_flush(nam_hip_batch* b, hipStream_t caller);
-int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool whole);
-int persist_stop(nam_hip_batch* b);
+int persist_flush(nam_hip_batch* b, const SessionCaller& caller);
+int persist_wait(nam_hip_batch* b, const SessionCaller& caller, unsigned target, bool whole);
+int persist_stop(nam_hip_batch* b, CallHints hints);
 int persist_prepare(nam_hip_batch* b);
 int persist_start(nam_hip_batch* b, const float* d_in, float* d_out, long stride);
-int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long stride, hipStream_t caller);
-int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, hipStream_t caller);
+int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long stride, const SessionCaller& caller);
+int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, const SessionCaller& caller);
 void persist_free(nam_hip_batch* b);
 // api_launch.cpp
 int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out);

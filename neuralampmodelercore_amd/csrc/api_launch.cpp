@@ -44,7 +44,7 @@ int ensure_state(nam_hip_batch* b, WidthGroup& g)
 // Wait for everything the batch may still have in flight: its own stream and the last caller-supplied one.
 hipError_t quiesce(nam_hip_batch* b)
 {
-  if (b->ps.active && persist_stop(b) != NAM_HIP_OK) // a resident launch owns the streams' state until it has left
+  if (b->ps.active && persist_stop(b, CallHints()) != NAM_HIP_OK) // a resident launch owns the streams' state until it has left
     return hipErrorUnknown;
   hipError_t e = b->stream ? hipStreamSynchronize(b->stream.get()) : hipSuccess;
   if (b->last_ext_stream && b->last_ext_stream != b->stream.get())
@@ -133,10 +133,10 @@ int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
 }
 
 // the session's side of a persistent launch of a one-wavefront-per-workgroup kernel (kernels.h: PersistArgs)
-PersistArgs persist_args(const nam_hip_batch* b)
+PersistArgs persist_args(const nam_hip_batch* b, const LaunchContext& ctx)
 {
   PersistArgs pa;
-  if (!b->ps_launching)
+  if (ctx.session_kind == PERSIST_NONE)
     return pa;
   pa.ring = b->ps.d_ring.get();
   pa.ring_mask = (int)kPRing - 1;
@@ -151,11 +151,11 @@ PersistArgs persist_args(const nam_hip_batch* b)
 
 // ... and of the workgroup-per-stream kernels (nam_a1_q_kernel, nam_a1_p4_kernel, nam_a1_p2_kernel, nam_kq_kernel), which carry the
 // same words as A1Args::p_* plus where the results go and how long the launch lingers
-static void session_args(const nam_hip_batch* b, A1Args& a)
+static void session_args(const nam_hip_batch* b, const LaunchContext& ctx, A1Args& a)
 {
-  if (!b->ps_launching)
+  if (ctx.session_kind == PERSIST_NONE)
     return;
-  const PersistArgs pa = persist_args(b);
+  const PersistArgs pa = persist_args(b, ctx);
   a.p_ring = pa.ring;
   a.p_ring_mask = pa.ring_mask;
   a.p_cons = pa.cons;
@@ -230,7 +230,7 @@ static int wr_jit_function(const std::string& path, int device, int stages, void
 // nam_wn_reg_kernel over up to kWrMaxGroups width groups in ONE launch (kernels.h: WrArgs): group k's `counts[k]` streams
 // (`maps[k]`: position -> stream index, nullptr = identity) become consecutive workgroups.
 int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* maps, const int* counts, int n_groups,
-              const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s)
+              const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx)
 {
   WrArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -279,8 +279,9 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
   int stages = 1;
   bool dense = false; // the two-wavefronts-per-SIMD build of the per-model code object
   // (a session whose caller flushes after EVERY buffer is a series of one-buffer calls: nothing for a pipeline to overlap)
-  const bool one_buffer_bursts = b->ps_launching && !b->pipe_session && b->ps.one_buffer_bursts();
-  if (!b->no_pipe && !b->one_buffer_call && !one_buffer_bursts && (b->ps_launching || n_frames > kBlock))
+  const bool session = ctx.session_kind != PERSIST_NONE;
+  const bool one_buffer_bursts = session && !b->pipe_session && b->ps.one_buffer_bursts();
+  if (!b->no_pipe && !ctx.hints.one_buffer_call && !one_buffer_bursts && (session || n_frames > kBlock))
   {
     // the launch's relative duration with nst waves per stream: a workgroup is nst waves at one wave per SIMD plus its LDS
     // image (and the queues), the workgroups beyond what the chip holds run in later turns (persist_kind), and a stream's
@@ -355,7 +356,7 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
   a.n_frames = n_frames;
   a.in_ch = groups[0]->plan->in_channels;
   a.out_ch = groups[0]->plan->out_channels;
-  a.ps = persist_args(b);
+  a.ps = persist_args(b, ctx);
   a.bank_member = groups[0]->d_bank_member.get(); // (a bank batch has one group: groups[0]->d_wr_blob is [members][bank_stride])
   a.bank_stride = groups[0]->bank_stride;
   // every group on the model's own code object (they share one: build_model), or every group on the ahead-of-time kernel
@@ -372,10 +373,10 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
     const int rc = wr_jit_function(module, b->device, stages, &fn, dense);
     if (rc != NAM_HIP_OK)
       return rc;
-    NAM_HIP_CHECK(launch_wn_reg_jit(fn, a, total, lds_bytes, stages, s));
+    NAM_HIP_CHECK(launch_wn_reg_jit(fn, a, total, lds_bytes, stages, LaunchStream(s, ctx.retired)));
     return NAM_HIP_OK;
   }
-  NAM_HIP_CHECK(launch_wn_reg(a, total, lds_bytes, layers, runs, rt_layers, stages, s));
+  NAM_HIP_CHECK(launch_wn_reg(a, total, lds_bytes, layers, runs, rt_layers, stages, LaunchStream(s, ctx.retired)));
   return NAM_HIP_OK;
 }
 
@@ -399,7 +400,7 @@ WrGroupList wr_groups(nam_hip_batch* b)
   return out;
 }
 int launch_wr_all(nam_hip_batch* b, const WrGroupList& gs, const float* d_in, float* d_out, int n_frames, long io_stride,
-                  hipStream_t s)
+                  hipStream_t s, const LaunchContext& ctx)
 {
   const int* maps[kWrMaxGroups];
   int counts[kWrMaxGroups];
@@ -408,7 +409,7 @@ int launch_wr_all(nam_hip_batch* b, const WrGroupList& gs, const float* d_in, fl
     maps[k] = gs.g[k]->d_map.get();
     counts[k] = (int)gs.g[k]->streams.size();
   }
-  return launch_wr(b, gs.g, maps, counts, gs.n, d_in, d_out, n_frames, io_stride, s);
+  return launch_wr(b, gs.g, maps, counts, gs.n, d_in, d_out, n_frames, io_stride, s, ctx);
 }
 
 // The WaveNet kernel a launch of n_frames runs: pick_kernel, except that under AUTO a launch that walks several blocks
@@ -426,9 +427,9 @@ int kernel_for_launch(const nam_hip_batch* b, const WidthGroup& g, int n_frames)
 
 // ... and of a launch in general: the resident launch of a session of the interleaved-frame family runs that family whatever a
 // one-buffer launch of the batch would (persist_kind: PERSIST_A1_P2 needs no more than AUTO and a model the family takes)
-static int family_for_launch(const nam_hip_batch* b, const WidthGroup& g, const LaunchQuestion& q)
+static int family_for_launch(const nam_hip_batch* b, const WidthGroup& g, int n_frames, const LaunchContext& ctx)
 {
-  return q.session_kind == PERSIST_A1_P2 ? NAM_HIP_KERNEL_A1_IL : kernel_for_launch(b, g, q.n_frames);
+  return ctx.session_kind == PERSIST_A1_P2 ? NAM_HIP_KERNEL_A1_IL : kernel_for_launch(b, g, n_frames);
 }
 
 // the functions as rocprofv3 --kernel-trace shows them, without template arguments (in KernelFn's order)
@@ -437,12 +438,12 @@ static const char* const kKernelFnName[KERNEL_FN_COUNT] = {
   "nam_a1_p2_kernel", "nam_a1_p4_kernel", "nam_a1_q_kernel", // WaveNets
   "nam_lstm_kernel", "nam_lstm_mfma_kernel", "nam_lstm_mfma_reg_kernel", "nam_lstm_row_kernel", "nam_lstm_wide_kernel"};
 
-// Which __global__ function the group runs for the launch `q` describes: what launch_group launches and what
+// Which __global__ function the group runs for a launch of `n_frames` in the context `ctx`: what launch_group launches and what
 // nam_hip_batch_kernel_name reports.
-static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const LaunchQuestion& q)
+static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, int n_frames, const LaunchContext& ctx)
 {
   const Plan& p = *g.plan;
-  const bool session = q.session_kind != PERSIST_NONE;
+  const bool session = ctx.session_kind != PERSIST_NONE;
   if (p.arch != ARCH_WAVENET)
   {
     // AUTO: small cells (hidden <= 4) one gate row per lane and four streams per wavefront, cells of 5 .. 32 units two
@@ -459,13 +460,13 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const
       return lstm_mfma_in_registers(p.lstm) ? FN_LSTM_MFMA_REG : FN_LSTM_MFMA;
     return FN_LSTM;
   }
-  if (q.session_kind == PERSIST_WN_REG) // (one launch for every width group: launch_wr_all)
+  if (ctx.session_kind == PERSIST_WN_REG) // (one launch for every width group: launch_wr_all)
     return FN_WN_REG;
   // nam_a1_p4_kernel / nam_a1_q_kernel / nam_kq_kernel (pipelines, consecutive buffers in flight at once) instead of the
   // one-buffer kernels: whenever a launch holds more than one buffer — a persistent session, an offline render, a prewarm. A
   // launch of one block has nothing to overlap (every stage waits for the one before).
-  const bool pipeline = !b->no_pipe && (session || q.n_frames > kBlock);
-  switch (family_for_launch(b, g, q))
+  const bool pipeline = !b->no_pipe && (session || n_frames > kBlock);
+  switch (family_for_launch(b, g, n_frames, ctx))
   {
     case NAM_HIP_KERNEL_GENERIC: return FN_GENERIC;
     case NAM_HIP_KERNEL_WN_REG: return FN_WN_REG;
@@ -474,9 +475,9 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const
       if (!pipeline) // one buffer: the four-wave kernel, job table compiled in
         return FN_A1_P2;
       // the 16 / 8 topology as twelve one-wave stages, most rings resident in LDS (kernel_a1_q.hip) — unless the caller waits for
-      // the FIRST buffer (nam_hip_batch::short_blocking_call; PersistSession::short_bursts, which ticket sessions never follow) —
+      // the FIRST buffer (CallHints::short_blocking_call; PersistSession::short_bursts, which ticket sessions never follow) —
       // else as a pipeline of wave sets (three wavefronts per SIMD) across consecutive buffers
-      if (q_runs(b, p) && !q.short_blocking_call && !(session && !b->pipe_session && b->ps.short_bursts()))
+      if (q_runs(b, p) && !ctx.hints.short_blocking_call && !(session && !b->pipe_session && b->ps.short_bursts()))
         return FN_A1_Q;
       return FN_A1_P4;
     default: // NAM_HIP_KERNEL_A1_MFMA
@@ -484,7 +485,7 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const
         return FN_A1_MFMA;
       // the K-tap kernel addresses the launch's input through a 32-bit buffer descriptor (1 GiB of float32 audio per
       // stream and launch): longer launches take the VALU kernel, same state layout
-      if (q.n_frames > (1 << 28))
+      if (n_frames > (1 << 28))
         return FN_A1;
       // the A2 topology with more than one buffer in the launch (a session, a render, a prewarm): the pipeline of one-wave
       // stages compiled for it (kernel_kq.hip); same state as the K-tap kernel
@@ -502,7 +503,7 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, const
 const char* group_kernel_name(const nam_hip_batch* b, const WidthGroup& g, int n_frames)
 {
   const bool session_command = b->ps.enabled && n_frames == kBlock;
-  return kKernelFnName[select_kernel(b, g, LaunchQuestion{n_frames, session_command ? persist_kind(b) : (int)PERSIST_NONE, false})];
+  return kKernelFnName[select_kernel(b, g, n_frames, LaunchContext{session_command ? persist_kind(b) : (int)PERSIST_NONE})]; // (no hints)
 }
 
 // what every kernel's argument block starts with (kernels.h): the group's weights and state, the launch's streams and audio
@@ -528,13 +529,14 @@ static int uniform_act(const A1Plan& a1)
   return a1.arr[0].act;
 }
 
-static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args& a, int n, hipStream_t s)
+static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args& a, int n, hipStream_t stream, const LaunchContext& ctx)
 {
+  const LaunchStream s(stream, ctx.retired); // (for the session-capable kernels; the others take the bare stream)
   const Plan& p = *g.plan;
   a.plan = g.d_a1.get();
   a.act_p0 = p.a1.arr[0].act_p0; // uniform across arrays and layers for the A1 kernels (plan.cpp)
-  a.dbg = b->dbg.get();
-  if (b->ps_launching && b->ps.why)
+  a.dbg = ctx.dbg;
+  if (ctx.session_kind != PERSIST_NONE && b->ps.why)
     a.dbg = b->ps.why.dev(); // (NAM_HIP_SESSION_STATS: why a lingering workgroup left — il_common.h: session_wait_command)
   a.n_rings = p.a1.n_rings;
   a.head_scale = p.blob[(size_t)p.a1.head_scale_off];
@@ -554,7 +556,7 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
     a.xt_off = p.a1.ws_xt_off - base;
     a.n_xt = p.a1.ws_n_xt;
     a.act = act;
-    session_args(b, a);
+    session_args(b, ctx, a);
     if (!p.a1.p2_ok) // (pick_kernel: the interleaved-frame kernels exist for the official topologies' compile-time tables only)
       return fail(NAM_HIP_ERR_UNSUPPORTED, "NAM_HIP_KERNEL_A1_IL: not one of the official topologies");
     if (fn == FN_A1_Q)
@@ -575,11 +577,11 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
     a.consts_off = p.a1.kt_lds_src_off;
     a.r1_off = p.a1.kt_rech_off;
     a.act = p.a1.arr[0].act;
-    session_args(b, a);
+    session_args(b, ctx, a);
     NAM_HIP_CHECK(launch_kq(a, n, p.a1.arr[0].act, s));
   }
   else if (fn == FN_KT_MFMA)
-    NAM_HIP_CHECK(launch_kt_mfma(a, n, p.a1.kt_nk, p.a1.arr[0].channels, p.a1.kt_lds_floats, p.a1.arr[0].act, s));
+    NAM_HIP_CHECK(launch_kt_mfma(a, n, p.a1.kt_nk, p.a1.arr[0].channels, p.a1.kt_lds_floats, p.a1.arr[0].act, stream));
   else if (fn == FN_A1_MFMA)
   {
     a.n_mjobs = p.a1.ws_jobs;
@@ -593,10 +595,10 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
     a.lds_cond_b = p.a1.ws_lds_cond_b;
     a.lds_bytes = p.a1.ws_lds_bytes;
     a.prefetch = p.a1.ws_prefetch;
-    NAM_HIP_CHECK(launch_a1_mfma(a, n, uniform_act(p.a1), s));
+    NAM_HIP_CHECK(launch_a1_mfma(a, n, uniform_act(p.a1), stream));
   }
   else
-    NAM_HIP_CHECK(launch_a1(a, n, s));
+    NAM_HIP_CHECK(launch_a1(a, n, stream));
   return NAM_HIP_OK;
 }
 
@@ -619,15 +621,15 @@ static int launch_generic_program(const WidthGroup& g, GenericArgs& a, int n, hi
   return NAM_HIP_OK;
 }
 
-static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTMArgs& a, int n, hipStream_t s)
+static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTMArgs& a, int n, hipStream_t s, const LaunchContext& ctx)
 {
   a.n_streams = n;
   if (fn == FN_LSTM_ROW || fn == FN_LSTM_WIDE)
   {
     a.bank_member = g.d_bank_member.get(); // (a bank: a.blob is [members][bank_stride], whole plan blobs)
     a.bank_stride = g.bank_stride;
-    a.ps = persist_args(b);
-    NAM_HIP_CHECK(fn == FN_LSTM_ROW ? launch_lstm_row(a, s) : launch_lstm_wide(a, s));
+    a.ps = persist_args(b, ctx);
+    NAM_HIP_CHECK(fn == FN_LSTM_ROW ? launch_lstm_row(a, {s, ctx.retired}) : launch_lstm_wide(a, {s, ctx.retired}));
   }
   else if (fn == FN_LSTM_MFMA || fn == FN_LSTM_MFMA_REG) // (launch_lstm_mfma tells the two apart: lstm_mfma_in_registers)
     NAM_HIP_CHECK(launch_lstm_mfma(a, s));
@@ -652,22 +654,21 @@ static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTM
 
 // Launch one group's kernel over `n` streams given by `d_map` (nullptr = streams 0..n-1).
 int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out,
-                 int n_frames, long io_stride, hipStream_t s)
+                 int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx)
 {
   if (n <= 0 || n_frames <= 0)
     return NAM_HIP_OK;
   const Plan& p = *g.plan;
-  const LaunchQuestion q{n_frames, b->ps_launching ? b->ps.kind : (int)PERSIST_NONE, b->short_blocking_call};
-  const KernelFn fn = select_kernel(b, g, q);
+  const KernelFn fn = select_kernel(b, g, n_frames, ctx);
   if (p.arch != ARCH_WAVENET)
   {
     LSTMArgs a = lstm_args(p.lstm);
     common_args(a, g, d_map, d_in, d_out, n_frames, io_stride);
-    return launch_lstm_family(b, g, fn, a, n, s);
+    return launch_lstm_family(b, g, fn, a, n, s, ctx);
   }
   // the op program and the A1 kernels of a channel-padded model keep different ring layouts: a change of kernel
   // family is only legal on freshly reset state
-  const int fam = state_family_of(p, family_for_launch(b, g, q));
+  const int fam = state_family_of(p, family_for_launch(b, g, n_frames, ctx));
   if (g.state_family >= 0 && g.state_family != fam)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT,
                 "kernel change crosses state layouts (the op program's rings, the A1 kernels' zero-padded rings and "
@@ -678,7 +679,7 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
     WidthGroup* one[1] = {&g};
     const int* maps[1] = {d_map};
     const int counts[1] = {n};
-    return launch_wr(b, one, maps, counts, 1, d_in, d_out, n_frames, io_stride, s);
+    return launch_wr(b, one, maps, counts, 1, d_in, d_out, n_frames, io_stride, s, ctx);
   }
   if (fn == FN_GENERIC)
   {
@@ -688,7 +689,7 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
   }
   A1Args a;
   common_args(a, g, d_map, d_in, d_out, n_frames, io_stride);
-  return launch_a1_family(b, g, fn, a, n, s);
+  return launch_a1_family(b, g, fn, a, n, s, ctx);
 }
 
 // DSP::prewarm (NAM/dsp.cpp:67-101): process whole max_frames-sized buffers of silence until at
@@ -729,7 +730,7 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
   }
   if (frames > 0)
   {
-    const int rc = launch_group(b, g, d_map, n, nullptr, nullptr, frames, 0, b->stream.get());
+    const int rc = launch_group(b, g, d_map, n, nullptr, nullptr, frames, 0, b->stream.get(), LaunchContext());
     if (rc != NAM_HIP_OK)
       return rc;
     if (p.arch == ARCH_WAVENET && first_stream >= 0 && !g.d_bank_member) // (a bank's prewarmed state depends on the member: no cache)

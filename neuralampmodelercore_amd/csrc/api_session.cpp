@@ -68,8 +68,8 @@ int persist_kind(const nam_hip_batch* b)
 
 // (Re)starts the session's launch: every workgroup resumes behind the commands it has consumed so far and runs until
 // it finds the ring empty. `grace_us`: how long the launch looks for its first doorbell (rung just before, on the
-// caller's hardware queue, so it may land after the launch has started).
-static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, unsigned long long cmd0 = 0)
+// caller's hardware queue, so it may land after the launch has started). `hints`: of the API call the launch is started for.
+static int persist_launch(nam_hip_batch* b, CallHints hints, int grace_us, long long seq0 = -1, unsigned long long cmd0 = 0)
 {
   PersistSession& ps = b->ps;
   WidthGroup& g = b->groups[b->model->full_width];
@@ -94,11 +94,9 @@ static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, u
   // command's results (their p_prog, like every kernel's, is ring bookkeeping every 16 commands — never a completion signal;
   // the other kernels' tickets complete when the launch has left)
   {
-    const Plan& p = *g.plan;
     // ... and, round 6, a BLOCKING host caller that hands one buffer in after the other (nam_hip_batch::blocking_linger):
     // nam_a1_p4_kernel — what the official topology's short blocking calls run — publishes the word too, so the call waits
     // for its own command and the next call finds the launch still there (no launch, no prologue, no retirement per call)
-    (void)p;
     ps.cmd_done_published = (b->pipe_session || b->blocking_linger) && ps.out_is_host && !b->no_pipe
                         && (ps.kind == PERSIST_A1_P2 || ps.kind == PERSIST_KQ); // (pipe_session: never the short-burst rule)
     // ... and linger: a workgroup that finds itself up to date when a launch starts (another one's backlog was the reason for
@@ -111,14 +109,11 @@ static int persist_launch(nam_hip_batch* b, int grace_us, long long seq0 = -1, u
       NAM_HIP_CHECK(hipMemsetAsync(ps.d_cmd_count.get() + kPRing + 1, 0, sizeof(unsigned), ps.kstream.get()));
     }
   }
-  b->ps_launching = true; // (a session of the interleaved-frame family runs that family: api_launch.cpp, family_for_launch)
-  namhip::tl_session_stop_event = ps.retired.get(); // (the launch's own completion signal: persist_wait waits on it, not on the stream)
-  const int rc = ps.kind == PERSIST_WN_REG
-                   ? launch_wr_all(b, wr_groups(b), ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get())
-                   : launch_group(b, g, nullptr, b->n_streams, ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get());
-  namhip::tl_session_stop_event = nullptr;
-  b->ps_launching = false;
-  return rc;
+  // (a session of the interleaved-frame family runs that family: family_for_launch; `retired`: the launch's own completion signal, what persist_wait waits on)
+  const LaunchContext ctx{ps.kind, hints, ps.retired.get()};
+  return ps.kind == PERSIST_WN_REG
+           ? launch_wr_all(b, wr_groups(b), ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get(), ctx)
+           : launch_group(b, g, nullptr, b->n_streams, ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get(), ctx);
 }
 
 // Watchdog of the host's spins on the session's completion words: the resident launch normally answers within
@@ -158,15 +153,15 @@ struct PersistWatch
 };
 
 // Blocks until every submitted command has been consumed by every workgroup and its results are visible.
-// `caller`: the stream the doorbells were rung on.
-int persist_flush(nam_hip_batch* b, hipStream_t caller)
+// `caller`: the stream the doorbells were rung on, and the hints of the API call that waits (SessionCaller).
+int persist_flush(nam_hip_batch* b, const SessionCaller& caller)
 {
   return b->ps.active ? persist_wait(b, caller, b->ps.seq, true) : NAM_HIP_OK;
 }
 
 // `whole`: every submitted command (target == seq) and the launch gone. Otherwise: the first `target` commands of the
 // session rendered and visible — the launch may run on (the per-buffer completion word p_cmd_done counts then, if the launch publishes it).
-int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool whole)
+int persist_wait(nam_hip_batch* b, const SessionCaller& caller, unsigned target, bool whole)
 {
   PersistSession& ps = b->ps;
   if (!ps.active)
@@ -258,8 +253,8 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
     // left just before one landed. Make sure of the former, then run the launch again (it resumes where each stopped).
     if (!delivered)
     {
-      NAM_HIP_CHECK(hipStreamSynchronize(caller ? caller : b->stream.get()));
-      if (ps.last_caller && ps.last_caller != caller)
+      NAM_HIP_CHECK(hipStreamSynchronize(caller.stream ? caller.stream : b->stream.get()));
+      if (ps.last_caller && ps.last_caller != caller.stream)
         NAM_HIP_CHECK(hipStreamSynchronize(ps.last_caller));
       delivered = true;
     }
@@ -295,18 +290,18 @@ int persist_wait(nam_hip_batch* b, hipStream_t caller, unsigned target, bool who
     }
     if (++relaunches > 64)
       return fail(NAM_HIP_ERR_DEVICE, "persistent session: submitted buffers were not consumed");
-    const int rc = persist_launch(b, 0);
+    const int rc = persist_launch(b, caller.hints, 0);
     if (rc != NAM_HIP_OK)
       return rc;
   }
 }
 
-int persist_stop(nam_hip_batch* b)
+int persist_stop(nam_hip_batch* b, CallHints hints) // (of the API call that ends the session: its flush may have to start the launch once more)
 {
   PersistSession& ps = b->ps;
   if (!ps.active)
     return NAM_HIP_OK;
-  const int rc = persist_flush(b, ps.last_caller ? ps.last_caller : b->stream.get());
+  const int rc = persist_flush(b, SessionCaller(ps.last_caller ? ps.last_caller : b->stream.get(), hints));
   // the state is the caller's again only when the launch has gone: a successful whole flush has waited on the launch's own
   // completion signal (persist_wait; 1.4 us — a stream synchronize pushes a marker through the queue, 11 us: profiles/r05/sync_tail.txt)
   if (rc != NAM_HIP_OK || !ps.retired.get())
@@ -462,7 +457,7 @@ int persist_start(nam_hip_batch* b, const float* d_in, float* d_out, long stride
 // as a command of a session (the caller then launches as usual).
 // A buffer of any multiple of 64 frames (what hosts send: NAM/dsp.h:97 takes any num_frames <= maxBufferSize; plugins run
 // 64 ... 1,024) is that many commands, submitted back to back: the session renders them without a kernel boundary in between.
-int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long stride, hipStream_t caller)
+int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long stride, const SessionCaller& caller)
 {
   // (longer calls — an offline render of a whole file — are one resident launch of their own: same kernel, no commands)
   if (n_frames <= 0 || n_frames % kBlock != 0 || n_frames > kPersistMaxFrames)
@@ -482,7 +477,7 @@ int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_fram
         // (the session that starts with this buffer renumbers from 0 even if the count itself has not reached the mark yet:
         // otherwise a buffer of several commands would reach it in mid-buffer and be split after all)
         ps.rebase_pending = ps.rebase_pending || past_mark;
-        const int rc = persist_stop(b);
+        const int rc = persist_stop(b, caller.hints);
         if (rc != NAM_HIP_OK)
           return rc;
       }
@@ -497,7 +492,7 @@ int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_fram
   return NAM_HIP_OK;
 }
 
-int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, hipStream_t caller)
+int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, const SessionCaller& caller)
 {
   PersistSession& ps = b->ps;
   if (ps.active)
@@ -508,7 +503,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
     // otherwise run its count into bit 31, the "left" flag of the completion words; persist_start renumbers from 0.
     if (stride != ps.stride || off_in != off_out || off_in < 0 || off_in > 0x1fff0000l /* (the kernels address a window through a 2 GB buffer descriptor) */ || ps.seq >= ps.rebase_at)
     {
-      const int rc = persist_stop(b);
+      const int rc = persist_stop(b, caller.hints);
       if (rc != NAM_HIP_OK)
         return rc;
     }
@@ -572,7 +567,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
   const unsigned slot = ps.seq & (kPRing - 1);
   // Nothing in flight on the caller's stream: nothing to order the command behind, the host stores it itself (no
   // device-side write operation, which costs the host ~4 us and the device a small kernel per buffer).
-  if (ps.host_store_ok && (!ps.last_caller || ps.last_caller == caller) && hipStreamQuery(caller) == hipSuccess)
+  if (ps.host_store_ok && (!ps.last_caller || ps.last_caller == caller.stream) && hipStreamQuery(caller.stream) == hipSuccess)
   {
     ps.n_host_doorbells++;
     __atomic_store_n(&ps.d_ring.get()[slot], cmd, __ATOMIC_RELEASE);
@@ -584,29 +579,29 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
     if (idle)
     {
       // (when every workgroup stands at the same count, that count and this command travel with the launch itself)
-      const int rc = uniform ? persist_launch(b, 0, (long long)ps.seq, cmd) : persist_launch(b, 0);
+      const int rc = uniform ? persist_launch(b, caller.hints, 0, (long long)ps.seq, cmd) : persist_launch(b, caller.hints, 0);
       if (rc != NAM_HIP_OK)
         return rc;
     }
   }
   else
   {
-    if (ps.last_caller && ps.last_caller != caller)
+    if (ps.last_caller && ps.last_caller != caller.stream)
       NAM_HIP_CHECK(hipStreamSynchronize(ps.last_caller)); // commands of two streams: keep them in order
     // the launch first, the stream-ordered store behind it: the two travel on different hardware queues, and the
     // launch looks for its first command for kGraceUs
     if (idle)
     {
-      const int rc = persist_launch(b, kGraceUs);
+      const int rc = persist_launch(b, caller.hints, kGraceUs);
       if (rc != NAM_HIP_OK)
         return rc;
     }
     ps.n_stream_doorbells++;
-    NAM_HIP_CHECK(hipStreamWriteValue64(caller, ps.d_ring.get() + slot, cmd, 0));
+    NAM_HIP_CHECK(hipStreamWriteValue64(caller.stream, ps.d_ring.get() + slot, cmd, 0));
   }
   ps.seq++;
   ps.flushed_valid = false;
-  ps.last_caller = caller;
+  ps.last_caller = caller.stream;
   for (auto& g : b->groups)
     if (!g.streams.empty() && g.plan->arch == ARCH_WAVENET)
       g.state_family = persist_family(b, g);

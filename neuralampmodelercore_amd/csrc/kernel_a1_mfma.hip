@@ -430,7 +430,7 @@ template <int ACT_T, bool WT, bool PROF, int D>
 hipError_t launch_mfma_inst(const A1Args& a, int n_blocks, hipStream_t stream)
 {
   // (the LDS layout is sized per model: plan.h, ws_lds_*)
-  return launch_instance<&nam_a1_mfma_kernel<ACT_T, WT, PROF, D>, true, kLdsCu>(
+  return launch_instance<&nam_a1_mfma_kernel<ACT_T, WT, PROF, D>, kLdsCu>(
       dim3(n_blocks), dim3(512), a.lds_bytes, stream, a.plan, a.blob, a);
 }
 template <int ACT_T, bool WT, bool PROF>

@@ -482,14 +482,14 @@ __global__ __launch_bounds__(256) void nam_a1_p2_kernel(const float* __restrict_
 namespace
 {
 template <int C0, int C1, int ACT_T, bool WT, bool PERSIST, bool BANK>
-hipError_t launch_p2_inst(const A1Args& a, int n_blocks, hipStream_t stream)
+hipError_t launch_p2_inst(const A1Args& a, int n_blocks, LaunchStream stream)
 {
   return launch_instance<&nam_a1_p2_kernel<C0, C1, ACT_T, WT, PERSIST, BANK>>(dim3(n_blocks), dim3(256), p2::kLdsBytes, stream, a.blob, a);
 }
 // This kernel's own rule (not kernels.h: with_session_form): its session instantiations never write through.
 // BANK, a model bank (A1Args::bank_member): the 16 / 8 topology with the activations nam_a1_q_kernel takes — what a bank holds (api_bank.cpp)
 template <int C0, int C1, int ACT_T, bool BANK = false>
-hipError_t launch_p2_act(const A1Args& a, int n_blocks, hipStream_t stream)
+hipError_t launch_p2_act(const A1Args& a, int n_blocks, LaunchStream stream)
 {
   // persistent session: plain write-back ring appends (written through, the rows a block appends would be read back
   // from memory instead of the L2 one block later: 27 us per block instead of 10.5, measured)
@@ -499,7 +499,7 @@ hipError_t launch_p2_act(const A1Args& a, int n_blocks, hipStream_t stream)
   return wt ? launch_p2_inst<C0, C1, ACT_T, true, false, BANK>(a, n_blocks, stream) : launch_p2_inst<C0, C1, ACT_T, false, false, BANK>(a, n_blocks, stream);
 }
 template <int C0, int C1>
-hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, hipStream_t stream)
+hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, LaunchStream stream)
 {
   if (act == ACT_FASTTANH)
     return launch_p2_act<C0, C1, ACT_FASTTANH>(a, n_blocks, stream);
@@ -509,7 +509,7 @@ hipError_t launch_p2_shape(const A1Args& a, int n_blocks, int act, hipStream_t s
 }
 } // namespace
 
-hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream)
+hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, LaunchStream stream)
 {
   if (a.bank_member)
   {

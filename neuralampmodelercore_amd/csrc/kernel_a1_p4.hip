@@ -727,7 +727,7 @@ struct P4Pick
   bool bank, session, out_host;
   const A1Args* a;
   int n_blocks;
-  hipStream_t stream;
+  LaunchStream stream;
 };
 template <int C0, int C1, int ACT_T, bool BANK = false>
 hipError_t p4_act(const P4Pick& k)
@@ -777,7 +777,7 @@ hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host, bool ba
   return p4_walk(P4Pick{c0, c1, act, bank, true, out_host, nullptr, 0, nullptr});
 }
 
-hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream)
+hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, LaunchStream stream)
 {
   return p4_walk(P4Pick{c0, c1, act, a.bank_member != nullptr, a.p_ring != nullptr, a.p_out_host != 0, &a, n_blocks, stream});
 }

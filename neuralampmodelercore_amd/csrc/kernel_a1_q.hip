@@ -1182,7 +1182,7 @@ template __global__ void nam_a1_q_kernel<ACT_FASTTANH, false, true>(const float*
 namespace
 {
 template <int ACT_T, bool BANK>
-hipError_t launch_q_bank(const A1Args& a, int n_blocks, hipStream_t stream)
+hipError_t launch_q_bank(const A1Args& a, int n_blocks, LaunchStream stream)
 {
   return with_session_form(a.p_ring != nullptr, a.p_out_host != 0, a.n_frames, [&](auto wt, auto persist) {
     return launch_instance<&nam_a1_q_kernel<ACT_T, decltype(wt)::value, decltype(persist)::value, false, BANK>>(
@@ -1197,10 +1197,10 @@ bool a1_q_takes(int act)
 {
   return act == ACT_FASTTANH || act == ACT_TANH;
 }
-hipError_t launch_a1_q(const A1Args& a, int n_blocks, int act, hipStream_t stream)
+hipError_t launch_a1_q(const A1Args& a, int n_blocks, int act, LaunchStream stream)
 {
   if (a.dbg && !a.p_ring && !a.bank_member) // developer tool (nam_hip_batch_debug_timeline): the stamped instantiation
-    return launch_instance<&nam_a1_q_kernel<ACT_FASTTANH, false, false, true>, true>(dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream, a.blob, a);
+    return launch_instance<&nam_a1_q_kernel<ACT_FASTTANH, false, false, true>>(dim3(n_blocks), dim3(aq::kNst * 64), aq::kLdsBytes, stream.stream, a.blob, a);
   const bool bank = a.bank_member != nullptr; // a model bank runs the BANK instantiations; one model keeps its own
   if (act == ACT_FASTTANH)
     return bank ? launch_q_bank<ACT_FASTTANH, true>(a, n_blocks, stream) : launch_q_bank<ACT_FASTTANH, false>(a, n_blocks, stream);

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(64) void nam_a1_kernel(const A1Plan* __restrict__ P
 
 hipError_t launch_a1(const A1Args& a, int n_blocks, hipStream_t stream)
 {
-  return launch_instance<&nam_a1_kernel, true>(dim3(n_blocks), dim3(64), 0, stream, a.plan, a.blob, a);
+  return launch_instance<&nam_a1_kernel>(dim3(n_blocks), dim3(64), 0, stream, a.plan, a.blob, a);
 }
 
 } // namespace namhip

@@ -464,8 +464,8 @@ hipError_t launch_generic(const GenericArgs& a, int n_blocks, int lds_bytes, hip
 {
   // (rows, and the weights behind them, sized per program: plan_ops.cpp)
   if (a.blob_floats > 0)
-    return launch_instance<&nam_generic_kernel<true>, true, kLdsCu>(dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
-  return launch_instance<&nam_generic_kernel<false>, true, kLdsCu>(dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
+    return launch_instance<&nam_generic_kernel<true>, kLdsCu>(dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
+  return launch_instance<&nam_generic_kernel<false>, kLdsCu>(dim3(n_blocks), dim3(64), lds_bytes, stream, a.ops, a.blob, a);
 }
 
 } // namespace namhip

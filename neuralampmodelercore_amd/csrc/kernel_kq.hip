@@ -777,7 +777,7 @@ __global__ __launch_bounds__(kq::kNst * 64) void nam_kq_kernel(const float* __re
 namespace
 {
 template <int ACT_T, bool BANK>
-hipError_t launch_kq_bank(const A1Args& a, int n_blocks, hipStream_t stream)
+hipError_t launch_kq_bank(const A1Args& a, int n_blocks, LaunchStream stream)
 {
   return with_session_form(a.p_ring != nullptr, a.p_out_host != 0, a.n_frames, [&](auto wt, auto persist) {
     return launch_instance<&nam_kq_kernel<ACT_T, decltype(wt)::value, decltype(persist)::value, BANK>>(dim3(n_blocks), dim3(kq::kNst * 64),
@@ -785,7 +785,7 @@ hipError_t launch_kq_bank(const A1Args& a, int n_blocks, hipStream_t stream)
   });
 }
 template <int ACT_T>
-hipError_t launch_kq_act(const A1Args& a, int n_blocks, hipStream_t stream)
+hipError_t launch_kq_act(const A1Args& a, int n_blocks, LaunchStream stream)
 {
   // a model bank (A1Args::bank_member) runs the BANK instantiations; one model keeps its own
   return a.bank_member ? launch_kq_bank<ACT_T, true>(a, n_blocks, stream) : launch_kq_bank<ACT_T, false>(a, n_blocks, stream);
@@ -800,7 +800,7 @@ bool kq_takes(int act, float act_p0)
 {
   return (act == ACT_LEAKYRELU && act_p0 <= 1.0f) || act == ACT_RELU || act == ACT_TANH || act == ACT_FASTTANH;
 }
-hipError_t launch_kq(const A1Args& a, int n_blocks, int act, hipStream_t stream)
+hipError_t launch_kq(const A1Args& a, int n_blocks, int act, LaunchStream stream)
 {
   if (!kq_takes(act, a.act_p0))
     return hipErrorInvalidValue;

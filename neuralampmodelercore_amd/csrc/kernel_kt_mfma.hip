@@ -278,9 +278,9 @@ hipError_t launch_kt_mfma(const A1Args& a, int n_blocks, int nk, int channels, i
     return hipErrorInvalidValue;
 #define NAM_KT(NK, WT, ACT) \
   (NK == 2 && bank) \
-    ? launch_instance<&nam_kt_mfma_kernel<2, WT, ACT, true>, true, kLdsDefault>( \
+    ? launch_instance<&nam_kt_mfma_kernel<2, WT, ACT, true>, kLdsDefault>( \
         dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a) \
-    : launch_instance<&nam_kt_mfma_kernel<NK, WT, ACT>, true, kLdsDefault>( \
+    : launch_instance<&nam_kt_mfma_kernel<NK, WT, ACT>, kLdsDefault>( \
         dim3(n_blocks), dim3(256), lds_bytes, stream, a.plan, a.blob, a)
 #define NAM_KT_ACT(NK, WT) \
   switch (act) \

@@ -1059,9 +1059,9 @@ hipError_t launch_lstm(const LSTMArgs& a, hipStream_t stream)
     if (!a.scratch)
       return hipErrorInvalidValue;
     const int io_bytes = (a.in_ch + a.out_ch) * kBlock * 65 * (int)sizeof(float);
-    return launch_instance<&nam_lstm_kernel<true>, true, kLdsCu>(dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a);
+    return launch_instance<&nam_lstm_kernel<true>, kLdsCu>(dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a);
   }
-  return launch_instance<&nam_lstm_kernel<false>, true, kLdsCu>(dim3(n_blocks), dim3(64), lstm_lds_bytes(a), stream, a.blob, a);
+  return launch_instance<&nam_lstm_kernel<false>, kLdsCu>(dim3(n_blocks), dim3(64), lstm_lds_bytes(a), stream, a.blob, a);
 }
 
 hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
@@ -1073,9 +1073,9 @@ hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
     // I/O tiles + a pad row that lanes without an output row store to (64 lanes + 64 steps)
     const int io_bytes = ((a.in_ch + a.out_ch) * 16 * 65 + 128) * (int)sizeof(float);
 #define NAM_LSTM_REG(NL, NT) \
-  return a.fast ? launch_instance<&nam_lstm_mfma_reg_kernel<NL, NT, true>, true, kLdsDefault>( \
+  return a.fast ? launch_instance<&nam_lstm_mfma_reg_kernel<NL, NT, true>, kLdsDefault>( \
                     dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a) \
-                : launch_instance<&nam_lstm_mfma_reg_kernel<NL, NT, false>, true, kLdsDefault>( \
+                : launch_instance<&nam_lstm_mfma_reg_kernel<NL, NT, false>, kLdsDefault>( \
                     dim3(n_blocks), dim3(64), io_bytes, stream, a.blob, a)
     const int key = a.n_layers * 10 + a.mf_nt;
     switch (key)
@@ -1095,19 +1095,19 @@ hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream)
     }
 #undef NAM_LSTM_REG
   }
-  return launch_instance<&nam_lstm_mfma_kernel, true, kLdsCu>(dim3(n_blocks), dim3(64), a.mf_lds_bytes, stream, a.blob, a);
+  return launch_instance<&nam_lstm_mfma_kernel, kLdsCu>(dim3(n_blocks), dim3(64), a.mf_lds_bytes, stream, a.blob, a);
 }
 
-hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
+hipError_t launch_lstm_row(const LSTMArgs& a, LaunchStream stream)
 {
   if (!lstm_row_eligible(a))
     return hipErrorInvalidValue;
   const int n_blocks = (a.n_streams + 3) / 4;
   const int lds_bytes = (4 * a.hidden * 65 + 128) * (int)sizeof(float); // h history of the block + the dump slots
 #define NAM_LSTM_ROW_B(NL, NI, NH, BANK) \
-  return a.fast ? launch_instance<&nam_lstm_row_kernel<NL, NI, NH, true, BANK>, false, kLdsDefault>( \
+  return a.fast ? launch_instance<&nam_lstm_row_kernel<NL, NI, NH, true, BANK>, kLdsDefault>( \
                     dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a) \
-                : launch_instance<&nam_lstm_row_kernel<NL, NI, NH, false, BANK>, false, kLdsDefault>( \
+                : launch_instance<&nam_lstm_row_kernel<NL, NI, NH, false, BANK>, kLdsDefault>( \
                     dim3(n_blocks), dim3(64), lds_bytes, stream, a.blob, a)
 #define NAM_LSTM_ROW_H(NL, NI, NH) \
   if (a.bank_member) \
@@ -1133,16 +1133,16 @@ hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream)
 #undef NAM_LSTM_ROW_B
 }
 
-hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream)
+hipError_t launch_lstm_wide(const LSTMArgs& a, LaunchStream stream)
 {
   if (!lstm_wide_eligible(a))
     return hipErrorInvalidValue;
   const int nh = (a.hidden + 3) & ~3;
   const int lds_bytes = (kBlock * (nh + 4) + a.out_ch * nh + a.out_ch) * (int)sizeof(float);
 #define NAM_LSTM_WIDE_B(NL, NI, NH, BANK) \
-  return a.fast ? launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, true, BANK>, false, kLdsDefault>( \
+  return a.fast ? launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, true, BANK>, kLdsDefault>( \
                     dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a) \
-                : launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, false, BANK>, false, kLdsDefault>( \
+                : launch_instance<&nam_lstm_wide_kernel<NL, NI, NH, false, BANK>, kLdsDefault>( \
                     dim3(a.n_streams), dim3(64), lds_bytes, stream, a.blob, a)
 #define NAM_LSTM_WIDE_H(NL, NI, NH) \
   if (a.bank_member) \

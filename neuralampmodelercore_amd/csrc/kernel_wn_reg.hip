@@ -1757,22 +1757,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // a kernel compiled for one model's shapes (`fn`: hipFunction_t of nam_wn_reg_jit / nam_wn_reg_jit2 in that model's code object)
-hipError_t launch_wn_reg_jit(void* fn, const WrArgs& a, int n_workgroups, int lds_bytes, int stages, hipStream_t stream)
+hipError_t launch_wn_reg_jit(void* fn, const WrArgs& a, int n_workgroups, int lds_bytes, int stages, LaunchStream stream)
 {
   if (n_workgroups <= 0 || a.n_frames <= 0)
     return hipSuccess;
   WrArgs args = a;
   size_t size = sizeof(args);
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  if (tl_session_stop_event) // (kernels.h: nam_launch; the Ext form takes the grid in work-items)
+  if (stream.retired) // (kernels.h: LaunchStream; the Ext form takes the grid in work-items)
     return hipExtModuleLaunchKernel(reinterpret_cast<hipFunction_t>(fn), (unsigned)n_workgroups * 64u * (unsigned)stages, 1, 1, 64u * (unsigned)stages, 1, 1,
-                                    (size_t)lds_bytes, stream, nullptr, config, nullptr, tl_session_stop_event, 0);
+                                    (size_t)lds_bytes, stream.stream, nullptr, config, nullptr, stream.retired, 0);
   return hipModuleLaunchKernel(reinterpret_cast<hipFunction_t>(fn), (unsigned)n_workgroups, 1, 1, 64u * (unsigned)stages, 1, 1,
-                               (unsigned)lds_bytes, stream, nullptr, config);
+                               (unsigned)lds_bytes, stream.stream, nullptr, config);
 }
 
 hipError_t launch_wn_reg(const WrArgs& a, int n_workgroups, int lds_bytes, bool layers, bool runs, bool rt_layers, int stages,
-                         hipStream_t stream)
+                         LaunchStream stream)
 {
   if (n_workgroups <= 0 || a.n_frames <= 0)
     return hipSuccess;
@@ -1780,9 +1780,9 @@ hipError_t launch_wn_reg(const WrArgs& a, int n_workgroups, int lds_bytes, bool 
   // keeps 68 KB of rings): up to kWrMaxLdsBytes
   const int set = ((layers && runs) || rt_layers) ? 2 : runs ? 1 : 0;
 #define NAM_WR_LAUNCH(KERNEL) \
-  return set == 2 ? launch_instance<&KERNEL<2>, false, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a) \
-       : set == 1 ? launch_instance<&KERNEL<1>, false, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a) \
-                  : launch_instance<&KERNEL<0>, false, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a)
+  return set == 2 ? launch_instance<&KERNEL<2>, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a) \
+       : set == 1 ? launch_instance<&KERNEL<1>, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a) \
+                  : launch_instance<&KERNEL<0>, kWrMaxLdsBytes>(dim3(n_workgroups), dim3(64 * stages), lds_bytes, stream, a)
   if (stages == 4)
     NAM_WR_LAUNCH(nam_wn_reg4_kernel);
   if (stages > 1)

@@ -33,21 +33,18 @@ struct DynamicLdsLimit
   }
 };
 
-// A session's resident launch carries its own completion signal: persist_launch (api_session.cpp) sets this thread's stop event
-// around the launch call, and the launch sites of the session-capable kernels go through nam_launch — hipExtLaunchKernelGGL puts
-// the event's signal on the dispatch packet itself, so the host's wait for "the launch has retired" (nam_hip_batch_flush,
-// synchronize, the end of a session) is a wait on that signal: ~1.4 us behind the last workgroup instead of the ~11 us a
-// stream / device synchronize takes to push a marker packet through the queue behind a plain launch
-// (tools/src/sync_tail.hip, profiles/r05/sync_tail.txt). nullptr (every other launch): a plain launch.
-extern thread_local hipEvent_t tl_session_stop_event;
-template <typename F, typename... Args>
-inline void nam_launch(F kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, Args... args)
+// Where a session-capable kernel is launched. A session's resident launch carries its own completion signal: persist_launch
+// (api_session.cpp) hands the session's event down as `retired`, and hipExtLaunchKernelGGL puts the event's signal on the
+// dispatch packet itself, so the host's wait for "the launch has retired" (nam_hip_batch_flush, synchronize, the end of a
+// session) is a wait on that signal: ~1.4 us behind the last workgroup instead of the ~11 us a stream / device synchronize
+// takes to push a marker packet through the queue behind a plain launch (tools/src/sync_tail.hip, profiles/r05/sync_tail.txt).
+// nullptr: a plain launch. The other kernels' wrappers take a hipStream_t (it converts WITHOUT an event): nobody can hand them one.
+struct LaunchStream
 {
-  if (tl_session_stop_event)
-    hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, nullptr, tl_session_stop_event, 0, args...);
-  else
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
-}
+  hipStream_t stream;
+  hipEvent_t retired;
+  LaunchStream(hipStream_t s, hipEvent_t r = nullptr) : stream(s), retired(r) {}
+};
 
 // One kernel instantiation on the current device, its dynamic-LDS limit raised to `lds_ceiling`: the limit object lives here, one
 // per `Kernel` (= per instantiation, as DynamicLdsLimit asks). Also what a first launch would otherwise pay for (~1.6 ms: the
@@ -60,22 +57,23 @@ inline hipError_t instance_ready(int lds_ceiling)
   static DynamicLdsLimit lds_limit;
   return lds_limit.ensure(reinterpret_cast<const void*>(Kernel), lds_ceiling);
 }
-// ... and launched: through nam_launch (every session-capable kernel), or kPlain = a plain launch. DynamicLdsLimit records
-// "raised", not a size: a kernel whose LDS request differs from launch to launch names the most it may ask for as kLdsCeiling
+// ... and launched: with the session's completion event on the dispatch when `s` carries one, else plainly — as every launch
+// on a bare hipStream_t is (LaunchStream). DynamicLdsLimit records "raised", not a size: a kernel whose LDS request differs
+// from launch to launch names the most it may ask for as kLdsCeiling
 // (0: every launch of the instantiation asks for the same lds_bytes). kLdsDefault as the ceiling is a refusal bound only: those
 // kernels never need the attribute raised, and one call per device that sets what is the default anyway costs nothing.
-template <auto Kernel, bool kPlain = false, int kLdsCeiling = 0, typename... Args>
-inline hipError_t launch_instance(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, Args... args)
+template <auto Kernel, int kLdsCeiling = 0, typename... Args>
+inline hipError_t launch_instance(dim3 grid, dim3 block, int lds_bytes, LaunchStream s, Args... args)
 {
   if (kLdsCeiling && lds_bytes > kLdsCeiling)
     return hipErrorInvalidValue;
   const hipError_t e = instance_ready<Kernel>(kLdsCeiling ? kLdsCeiling : lds_bytes);
   if (e != hipSuccess)
     return e;
-  if constexpr (kPlain)
-    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+  if (s.retired)
+    hipExtLaunchKernelGGL(Kernel, grid, block, lds_bytes, s.stream, nullptr, s.retired, 0, args...);
   else
-    nam_launch(Kernel, grid, block, lds_bytes, stream, args...);
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, s.stream, args...);
   return hipGetLastError();
 }
 
@@ -303,31 +301,31 @@ struct WrArgs
 // stages = 2 / 4: that many wavefronts per stream (the op program cut at WrGroup::split_op), lds_bytes including the
 // (stages - 1) queues of kWrQueueBytes
 hipError_t launch_wn_reg(const WrArgs& a, int n_workgroups, int lds_bytes, bool layers, bool runs, bool rt_layers, int stages,
-                         hipStream_t stream);
+                         LaunchStream stream);
 // the same kernel compiled for one model's own layer shapes (wr_jit.cpp); fn = hipFunction_t of the model's code object
-hipError_t launch_wn_reg_jit(void* fn, const WrArgs& a, int n_workgroups, int lds_bytes, int stages, hipStream_t stream);
+hipError_t launch_wn_reg_jit(void* fn, const WrArgs& a, int n_workgroups, int lds_bytes, int stages, LaunchStream stream);
 hipError_t launch_generic(const GenericArgs& a, int n_blocks, int lds_bytes, hipStream_t stream);
 hipError_t launch_a1(const A1Args& a, int n_blocks, hipStream_t stream);
 hipError_t launch_a1_mfma(const A1Args& a, int n_blocks, int act, hipStream_t stream);
-hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream);
+hipError_t launch_a1_p2(const A1Args& a, int n_blocks, int c0, int c1, int act, LaunchStream stream);
 // nam_a1_p4_kernel: the same models as a pipeline of wave sets decoupled through LDS (kernel_a1_p4.hip)
-hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, hipStream_t stream);
+hipError_t launch_a1_p4(const A1Args& a, int n_blocks, int c0, int c1, int act, LaunchStream stream);
 hipError_t preload_a1_p4_session(int c0, int c1, int act, bool out_host, bool bank = false); // (kernel_a1_p4.hip)
 // nam_a1_q_kernel (kernel_a1_q.hip): the 16 / 8 official topology (aq_table.h) as twelve one-wave stages with LDS-resident
 // rings; a.tiles_off = the plan's q weight block (A1Plan::q_w_off), a.consts_off = the FULL-layout tile area (ws_tiles_off)
 bool a1_q_takes(int act); // the activations it is compiled for (Fasttanh, Tanh)
-hipError_t launch_a1_q(const A1Args& a, int n_blocks, int act, hipStream_t stream);
+hipError_t launch_a1_q(const A1Args& a, int n_blocks, int act, LaunchStream stream);
 // nam_kq_kernel (kernel_kq.hip): the A2 topology (kp_table.h) as a pipeline of twelve one-wave stages, one lane per frame, on
 // nam_kt_mfma_kernel's stream state; a.tiles_off = the plan's kq weight block (A1Plan::kq_w_off); kq_takes: the activations it
 // is compiled for (LeakyReLU with a slope <= 1, ReLU, Tanh, Fasttanh)
 bool kq_takes(int act, float act_p0);
-hipError_t launch_kq(const A1Args& a, int n_blocks, int act, hipStream_t stream);
+hipError_t launch_kq(const A1Args& a, int n_blocks, int act, LaunchStream stream);
 hipError_t launch_kt_mfma(const A1Args& a, int n_blocks, int nk, int channels, int lds_aux_floats, int act,
                           hipStream_t stream);
 hipError_t launch_lstm(const LSTMArgs& a, hipStream_t stream);
 hipError_t launch_lstm_mfma(const LSTMArgs& a, hipStream_t stream);
-hipError_t launch_lstm_row(const LSTMArgs& a, hipStream_t stream); // hidden <= 4: one gate row per lane
-hipError_t launch_lstm_wide(const LSTMArgs& a, hipStream_t stream); // 5 .. 32 hidden units: two gate rows per lane
+hipError_t launch_lstm_row(const LSTMArgs& a, LaunchStream stream); // hidden <= 4: one gate row per lane
+hipError_t launch_lstm_wide(const LSTMArgs& a, LaunchStream stream); // 5 .. 32 hidden units: two gate rows per lane
 int lstm_lds_bytes(const LSTMArgs& a);
 long lstm_scratch_floats(const LSTMArgs& a); // > 0: the lanes = streams kernel keeps its columns in global scratch
 hipError_t launch_fill_state(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,

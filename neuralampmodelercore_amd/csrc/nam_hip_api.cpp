@@ -5,7 +5,6 @@
 
 namespace namhip
 {
-thread_local hipEvent_t tl_session_stop_event = nullptr; // (kernels.h: nam_launch)
 namespace api
 {
 namespace
@@ -543,7 +542,7 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
   }
   if (batch->ps.active) // this call is not a 64-frame buffer of the session: the resident launch hands the state back first
   {
-    const int rc = persist_stop(batch);
+    const int rc = persist_stop(batch, CallHints());
     if (rc != NAM_HIP_OK)
       return rc;
   }
@@ -551,13 +550,13 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
     // every group on nam_wn_reg_kernel: one launch for the whole (mixed-width) batch
     const WrGroupList gs = wr_groups(batch);
     if (gs.n > 1)
-      return n_frames > 0 ? launch_wr_all(batch, gs, d_in, d_out, n_frames, (long)frame_stride, s) : NAM_HIP_OK;
+      return n_frames > 0 ? launch_wr_all(batch, gs, d_in, d_out, n_frames, (long)frame_stride, s, LaunchContext()) : NAM_HIP_OK;
   }
   for (auto& g : batch->groups)
   {
     if (g.streams.empty())
       continue;
-    const int rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), d_in, d_out, n_frames, (long)frame_stride, s);
+    const int rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), d_in, d_out, n_frames, (long)frame_stride, s, LaunchContext());
     if (rc != NAM_HIP_OK)
       return rc;
   }
@@ -704,7 +703,7 @@ int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* const* in, float
   if (e == hipSuccess)
     rc = nam_hip_batch_process_device(batch, d_in, d_out, (int)T, T, nullptr);
   if (e == hipSuccess && rc == NAM_HIP_OK && batch->ps.active) // (a short render went through the session: it ends here —
-    rc = persist_stop(batch);                                   // the window is about to be freed)
+    rc = persist_stop(batch, CallHints());                      // the window is about to be freed)
   for (int s = 0; s < N && e == hipSuccess && rc == NAM_HIP_OK; s++)
     if (n_frames[s] > 0)
       e = hipMemcpy2DAsync(out[s], (size_t)n_frames[s] * sizeof(float), d_out + (size_t)s * oc * T, (size_t)T * sizeof(float),
@@ -772,7 +771,7 @@ int nam_hip_batch_set_persistent(nam_hip_batch* batch, int enable)
   NAM_HIP_CHECK(hipSetDevice(batch->device));
   if (!enable && batch->ps.active)
   {
-    const int rc = persist_stop(batch);
+    const int rc = persist_stop(batch, CallHints());
     if (rc != NAM_HIP_OK)
       return rc;
   }
@@ -815,7 +814,7 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
   NAM_HIP_CHECK(hipSetDevice(batch->device)); // (ending a session may relaunch: the launchers configure the current device)
   if (batch->ps.active)
   {
-    const int rc = persist_stop(batch);
+    const int rc = persist_stop(batch, CallHints());
     if (rc != NAM_HIP_OK)
       return rc;
   }
@@ -885,23 +884,24 @@ int nam_hip_batch_debug_timeline(nam_hip_batch* batch, int n_frames, long long* 
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_debug_timeline: bad argument");
   NAM_HIP_CHECK(hipSetDevice(batch->device));
   const size_t bytes = 96 * 8 * sizeof(long long);
-  // batch->dbg is what launch_a1_family hands to every launch: set for this call's launches only, empty again on every way out
-  hipError_t e = hipMalloc(batch->dbg.out(), bytes);
+  DeviceBuf<long long> dbg; // handed to this call's launches through their context (launch_a1_family), and to no other
+  hipError_t e = hipMalloc(dbg.out(), bytes);
   if (e == hipSuccess)
-    e = hipMemset(batch->dbg.get(), 0, bytes);
+    e = hipMemset(dbg.get(), 0, bytes);
   if (e == hipSuccess)
     e = hipDeviceSynchronize(); // (the fill runs on the null stream, the launch on the batch's non-blocking one)
   int rc = NAM_HIP_OK;
   if (e == hipSuccess)
   {
+    LaunchContext ctx;
+    ctx.dbg = dbg.get();
     for (auto& g : batch->groups)
       if (!g.streams.empty() && rc == NAM_HIP_OK)
-        rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), nullptr, nullptr, n_frames, 0, batch->stream.get());
-    e = hipStreamSynchronize(batch->stream.get());
+        rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), nullptr, nullptr, n_frames, 0, batch->stream.get(), ctx);
+    e = hipStreamSynchronize(batch->stream.get()); // (before `dbg` goes: the launches write it)
     if (e == hipSuccess)
-      e = hipMemcpy(out_stamps, batch->dbg.get(), bytes, hipMemcpyDeviceToHost);
+      e = hipMemcpy(out_stamps, dbg.get(), bytes, hipMemcpyDeviceToHost);
   }
-  (void)batch->dbg.reset();
   if (rc != NAM_HIP_OK)
     return rc;
   NAM_HIP_CHECK(e);

@@ -139,6 +139,38 @@ def test_create_use_destroy_create_again(nam_lib, oracle, case):
         assert np.array_equal(first, _plain(nam_lib, x))
 
 
+@pytest.mark.parametrize("name,kernel", [("wavenet_a1_standard", "nam_a1_q_kernel"), ("wavenet_a2_max", "nam_wn_reg_kernel")])
+def test_call_forms_interleaved_on_one_batch(nam_lib, oracle, name, kernel):
+    """What a launch runs depends on the call it serves (a blocking host call of up to four buffers starts nam_a1_p4_kernel where
+    nam_a1_q_kernel would run; one of a single buffer runs nam_wn_reg_kernel as one wavefront per stream) and on nothing an earlier
+    call left behind: blocking calls of every class, tickets, a blocking call again and a call outside persistent mode on ONE
+    batch, each followed by a call of another class. The calls run different kernels of one family, so the concatenated output
+    is held against the oracle, every stream, not against another call form."""
+    max_frames = 8 * BLOCK
+    lengths = [BLOCK, 8 * BLOCK, 4 * BLOCK, BLOCK, 2 * BLOCK, BLOCK, BLOCK, 8 * BLOCK]
+    at = np.concatenate([[0], np.cumsum(lengths)])
+    x = stream_bank(N, int(at[-1]), seed=977)
+    part = lambda k: x[:, at[k]:at[k + 1]]
+    b = nam_lib.get_dsp(model_path(name), fast_tanh=True).batch(N, max_frames)
+    assert b.set_persistent(True)
+    assert b.kernel_name(BLOCK) == kernel
+    b.Reset(prewarm=True)
+    ys = [b.process(part(k)) for k in range(4)]
+    tickets = [b.submit(part(4)), b.submit(part(5))]
+    ys += [b.wait(t) for t in tickets]
+    ys.append(b.process(part(6)))
+    assert not b.set_persistent(False)
+    ys.append(b.process(part(7)))
+    b.close()
+    y = np.concatenate(ys, axis=2)
+    assert y.shape == (N, 1, at[-1]) and np.isfinite(y).all()
+    for s in range(N):
+        r = _oracle_run(oracle, name, x[s], max_frames, True)
+        err, scale = float(np.max(np.abs(r - y[s]))), max(1.0, float(np.max(np.abs(r))))
+        print(f"{name}, stream {s}: against the oracle {err:.3e} (|y|max {scale:.3f})")
+        assert err <= _tol(True) * scale, (name, s, err, scale)
+
+
 def test_refused_allocation_leaves_nothing_behind(nam_lib, oracle):
     """nam_hip_batch_create with so many streams that the STATE buffer alone ([n_streams][state bytes per stream]: the oversized
     request, ensure_state's hipMalloc) exceeds the device's total memory: the runtime refuses that one request at once — nothing of

@@ -1,7 +1,7 @@
 // Developer probe (round 6): host clock from the launch call to (a) the call's return, (b) the first wave of the grid writing a
 // flag the host sees (host-mapped memory, system-scope store), (c) the last workgroup's flag — for the session launch's own shape
 // (256 workgroups x 1,024 threads, 144 KB of LDS) and smaller ones, through hipLaunchKernelGGL, hipExtLaunchKernelGGL with a stop
-// event (what the sessions use: kernels.h nam_launch) and with a big by-value argument like A1Args. The queue is idle at every
+// event (what the sessions use: kernels.h launch_instance) and with a big by-value argument like A1Args. The queue is idle at every
 // launch (the sessions' case: a launch per burst).
 //   hipcc --offload-arch=gfx950 -O2 -o /tmp/launch_latency tools/src/launch_latency.hip && /tmp/launch_latency
 #include <hip/hip_runtime.h>
