@@ -42,13 +42,44 @@ extern "C" {
 #define NAM_HIP_ERR_INVALID_ARGUMENT (-1)
 #define NAM_HIP_ERR_FILE (-2) /* nam::NamFileValidationError — NAM/nam_file.cpp:9-40 */
 #define NAM_HIP_ERR_MODEL (-3) /* std::runtime_error at load: bad version / config / weight count */
-#define NAM_HIP_ERR_UNSUPPORTED (-4) /* valid .nam the device path cannot run (e.g. ConvNet / Linear) */
+#define NAM_HIP_ERR_UNSUPPORTED (-4) /* valid .nam the device path cannot run (e.g. ConvNet; a Linear model beyond the device limits below) */
 #define NAM_HIP_ERR_DEVICE (-5) /* HIP runtime error */
 #define NAM_HIP_ERR_TOO_MANY_FRAMES (-6) /* num_frames > max_frames (assert in NAM/wavenet/model.cpp:824) */
 
 #define NAM_HIP_ARCH_WAVENET 1
 #define NAM_HIP_ARCH_LSTM 2
 #define NAM_HIP_ARCH_CONTAINER 3 /* SlimmableContainer: submodels selected by nam_hip_batch_set_slimmable_size */
+#define NAM_HIP_ARCH_LINEAR 4 /* an impulse response (NAM/linear.cpp): see "Linear models" below */
+
+/* ---- Linear models (nam::Linear, NAM/linear.cpp, NAM/linear.h; history: nam::Buffer, NAM/dsp.cpp:203-305) ----
+ * Function: for channels ch < min(in_channels, out_channels): y[ch][n] = bias + sum_{k < receptive_field} weights[k] * x[ch][n - k],
+ *   history zero at the start; one impulse response for every channel, no mixing (linear.cpp:177-189); output channels
+ *   >= min(in, out) are 0, not the bias (linear.cpp:191-195). Exactly receptive_field (+ 1 with "bias": the last one) weights,
+ *   else "Params vector does not match expected size based on architecture parameters" (linear.cpp:68-72).
+ *   GetPrewarmSamples() is 0 (the DSP base, dsp.h:153): Reset with prewarm processes nothing.
+ * "implementation" ("auto" | "direct" / "legacy" / "old" | "fft" / "partitioned_fft" / "partitioned-fft", any letter case;
+ *   anything else fails with "Unsupported Linear implementation: <as given>", linear.cpp:280-293) selects between the reference's
+ *   two CPU engines, which compute the same function with different roundings. It selects NOTHING on the device: it is validated,
+ *   kept in NAM_HIP_FIELD_CONFIG_JSON, and otherwise ignored — one device engine computes every Linear model.
+ * Device limits: receptive_field <= 65,536 (1.4 s at 48 kHz), in_channels and out_channels <= 16; beyond either the load fails
+ *   with NAM_HIP_ERR_UNSUPPORTED and a message naming the limit. receptive_field < 1 or a channel count < 1: NAM_HIP_ERR_MODEL.
+ * Reset: nam_hip_batch_reset ZEROES a Linear batch's input history — the state of a freshly constructed reference model. A
+ *   deliberate choice, because the reference has no single behaviour to mirror: its direct engine keeps the input history across
+ *   Reset (Buffer::Reset / _set_receptive_field are not called from Linear::Reset, linear.cpp:83-97), its FFT engine rebuilds the
+ *   partition state but keeps the direct-tap buffer (linear.cpp:109-165). (Compare the LSTM note at nam_hip_batch_reset.)
+ * Kernels: nam_linear_kernel (what nam_hip_batch_kernel_name* report, for every launch length) between an append and a reduce
+ *   kernel per launch piece: 64 frames x 32 columns of output are one fp32 matrix product of the impulse response's Toeplitz matrix
+ *   with the input history, on v_mfma_f32_32x32x2_f32 — exact float32, fused multiply-adds; the taps are cut into K-splits whose
+ *   partial sums are added in a fixed order: the same call sequence gives the same bits, run to run and at any stream count.
+ *   How a stream is cut into calls changes results only through the order of summation (as under NAM_HIP_KERNEL_AUTO elsewhere).
+ *   nam_hip_model_info::state_bytes_per_stream is the history a batch with max_frames <= 512 keeps per stream (a longer max_frames,
+ *   up to 4,096, adds the difference): (taps rounded up to whole K-splits + one launch piece) frames x min(in, out) channels.
+ * A Linear batch supports create / destroy / reset, process_f32 / _f64 / _device (any length, frame_stride), render_f32,
+ *   submit / wait, synchronize, n_streams, kernel_name*. nam_hip_batch_set_persistent returns 0 (a model without recurrence has
+ *   nothing to keep resident; calls launch as usual); nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO, anything else is
+ *   NAM_HIP_ERR_UNSUPPORTED; set_slimmable_size returns what it returns for any non-slimmable model.
+ *   NAM_HIP_ERR_UNSUPPORTED too: a Linear model as a member of a bank (nam_hip_bank_create), as a submodel of a SlimmableContainer,
+ *   or as a WaveNet's condition_dsp. */
 
 /* kernel selection for nam_hip_batch_set_kernel */
 #define NAM_HIP_KERNEL_AUTO 0

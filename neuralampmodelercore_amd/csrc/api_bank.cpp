@@ -58,6 +58,9 @@ std::string member_refusal(const nam_hip_model& m, int* family)
 {
   const ModelSpec& s = *m.spec;
   *family = BANK_A1_IL;
+  if (s.arch == ARCH_LINEAR)
+    return "a Linear model (nam_linear_kernel multiplies ONE shared impulse response with every stream's history; per-stream "
+           "impulse responses are another kernel: no bank family takes it)";
   if (s.arch == ARCH_LSTM)
   {
     const LSTMPlan& L = member_plan(m).lstm;

@@ -58,6 +58,10 @@ int guarded(F&& f)
   {
     return fail(NAM_HIP_ERR_FILE, e.what());
   }
+  catch (const UnsupportedError& e)
+  {
+    return fail(NAM_HIP_ERR_UNSUPPORTED, e.what());
+  }
   catch (const std::exception& e)
   {
     return fail(NAM_HIP_ERR_MODEL, e.what());
@@ -164,6 +168,12 @@ struct WidthGroup
   DeviceBuf<int> d_bank_member;
   DeviceBuf<float> d_bank_scal;
   long bank_stride = 0;
+  // a Linear batch's one group (plan.h: LinearPlan): no per-stream state — d_state stays empty, state_stride 0 —; the batch's input
+  // history as ONE ring [lin_hist_frames][lin_cols_pad], stream-minor, and the K-splits' partial sums of one launch piece
+  // [n_splits][lin_part_frames][lin_cols_pad]. d_blob holds the padded taps. `lin_pos`: the ring row the next frame goes to — host
+  // state: the launches of a batch are enqueued in call order, each with its position as an argument.
+  DeviceBuf<float> d_lin_hist, d_lin_part;
+  int lin_hist_frames = 0, lin_cols_pad = 0, lin_part_frames = 0, lin_piece = 0, lin_pos = 0;
 };
 
 // Persistent block mode (nam_hip_batch_set_persistent): one resident launch of nam_a1_p2_kernel per session, fed one
@@ -354,6 +364,7 @@ enum KernelFn : int
 {
   FN_GENERIC, FN_WN_REG, FN_A1, FN_A1_MFMA, FN_KT_MFMA, FN_KQ, FN_A1_P2, FN_A1_P4, FN_A1_Q, // WaveNets
   FN_LSTM, FN_LSTM_MFMA, FN_LSTM_MFMA_REG, FN_LSTM_ROW, FN_LSTM_WIDE,
+  FN_LINEAR, // (the compute kernel of a Linear launch piece; its append and reduce kernels ride along: kernel_linear.hip)
   KERNEL_FN_COUNT
 };
 // A bank family's rules: kBankFamily[BankFamily] (api_bank.cpp), asked by pick_kernel, launch_a1_family and

@@ -21,6 +21,21 @@ int upload_group(nam_hip_batch* b, WidthGroup& g)
   }
   else if (p.arch == ARCH_LSTM)
     NAM_HIP_CHECK(upload(g.d_init, p.lstm.init_state.data(), p.lstm.init_state.size(), 1));
+  else if (p.arch == ARCH_LINEAR)
+  {
+    // no per-stream state: the geometry of the batch's history ring and partial sums (ensure_state allocates them)
+    const LinearPlan& L = p.linear;
+    const long cols = (long)b->n_streams * L.cols_per_stream;
+    if (cols > (1l << 24))
+      return fail(NAM_HIP_ERR_UNSUPPORTED, "Linear: more than 16,777,216 columns (streams x channels) in one batch");
+    g.lin_cols_pad = (int)((cols + kLinearColTile - 1) / kLinearColTile * kLinearColTile);
+    g.lin_piece = L.piece_frames(b->max_frames);
+    g.lin_part_frames = (g.lin_piece + kBlock - 1) / kBlock * kBlock;
+    g.lin_hist_frames = L.hist_frames(b->max_frames);
+    g.lin_pos = 0;
+    g.state_stride = 0;
+    return NAM_HIP_OK;
+  }
   g.state_stride = p.state_floats;
   (void)b;
   return NAM_HIP_OK;
@@ -28,6 +43,17 @@ int upload_group(nam_hip_batch* b, WidthGroup& g)
 
 int ensure_state(nam_hip_batch* b, WidthGroup& g)
 {
+  if (g.plan->arch == ARCH_LINEAR)
+  {
+    if (g.d_lin_hist)
+      return NAM_HIP_OK;
+    const size_t hist_bytes = (size_t)g.lin_hist_frames * g.lin_cols_pad * sizeof(float);
+    NAM_HIP_CHECK(hipMalloc(g.d_lin_hist.out(), hist_bytes));
+    NAM_HIP_CHECK(hipMalloc(g.d_lin_part.out(), (size_t)g.plan->linear.n_splits * g.lin_part_frames * g.lin_cols_pad * sizeof(float)));
+    NAM_HIP_CHECK(hipMemsetAsync(g.d_lin_hist.get(), 0, hist_bytes, b->stream.get())); // history starts at zero (Buffer, dsp.cpp:203-230)
+    g.lin_pos = 0;
+    return NAM_HIP_OK;
+  }
   if (g.d_state)
     return NAM_HIP_OK;
   const size_t bytes = (size_t)b->n_streams * g.state_stride * sizeof(float);
@@ -436,7 +462,8 @@ static int family_for_launch(const nam_hip_batch* b, const WidthGroup& g, int n_
 static const char* const kKernelFnName[KERNEL_FN_COUNT] = {
   "nam_generic_kernel", "nam_wn_reg_kernel", "nam_a1_kernel", "nam_a1_mfma_kernel", "nam_kt_mfma_kernel", "nam_kq_kernel",
   "nam_a1_p2_kernel", "nam_a1_p4_kernel", "nam_a1_q_kernel", // WaveNets
-  "nam_lstm_kernel", "nam_lstm_mfma_kernel", "nam_lstm_mfma_reg_kernel", "nam_lstm_row_kernel", "nam_lstm_wide_kernel"};
+  "nam_lstm_kernel", "nam_lstm_mfma_kernel", "nam_lstm_mfma_reg_kernel", "nam_lstm_row_kernel", "nam_lstm_wide_kernel",
+  "nam_linear_kernel"};
 
 // Which __global__ function the group runs for a launch of `n_frames` in the context `ctx`: what launch_group launches and what
 // nam_hip_batch_kernel_name reports.
@@ -444,7 +471,9 @@ static KernelFn select_kernel(const nam_hip_batch* b, const WidthGroup& g, int n
 {
   const Plan& p = *g.plan;
   const bool session = ctx.session_kind != PERSIST_NONE;
-  if (p.arch != ARCH_WAVENET)
+  if (p.arch == ARCH_LINEAR) // one device engine for every Linear model, launch length and stream count
+    return FN_LINEAR;
+  if (p.arch != ARCH_WAVENET) // (ARCH_LSTM: a container's groups carry their submodels' plans)
   {
     // AUTO: small cells (hidden <= 4) one gate row per lane and four streams per wavefront, cells of 5 .. 32 units two
     // gate rows per lane and one stream per wavefront, else the matrix-core kernel (16 streams per wavefront);
@@ -652,6 +681,43 @@ static int launch_lstm_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, LSTM
   return NAM_HIP_OK;
 }
 
+// A Linear batch's launch: cut into pieces of at most the batch's piece length (plan.h: LinearPlan::piece_frames), each piece
+// append + compute + reduce behind one another on `s` (kernel_linear.hip). The ring position is host state, advanced per piece.
+static int launch_linear_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out, int n_frames,
+                               long io_stride, hipStream_t s)
+{
+  const LinearPlan& L = g.plan->linear;
+  if (d_map || n != b->n_streams || !g.d_lin_hist)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "Linear: a launch covers every stream of the batch (one shared history ring)");
+  LinearArgs a;
+  a.blob = g.d_blob.get();
+  a.hist = g.d_lin_hist.get();
+  a.part = g.d_lin_part.get();
+  a.io_stride = io_stride;
+  a.n_streams = n;
+  a.in_ch = L.in_ch;
+  a.out_ch = L.out_ch;
+  a.cols_per_stream = L.cols_per_stream;
+  a.n_cols = n * L.cols_per_stream;
+  a.cols_pad = g.lin_cols_pad;
+  a.hist_frames = g.lin_hist_frames;
+  a.part_frames = g.lin_part_frames;
+  a.n_splits = L.n_splits;
+  a.split_taps = L.split_taps;
+  a.taps_off = L.taps_off;
+  a.bias = L.bias;
+  for (int at = 0; at < n_frames; at += g.lin_piece)
+  {
+    a.n_frames = std::min(g.lin_piece, n_frames - at);
+    a.in = d_in ? d_in + at : nullptr;
+    a.out = d_out ? d_out + at : nullptr;
+    a.pos = g.lin_pos;
+    NAM_HIP_CHECK(launch_linear(a, s));
+    g.lin_pos = (g.lin_pos + a.n_frames) % g.lin_hist_frames;
+  }
+  return NAM_HIP_OK;
+}
+
 // Launch one group's kernel over `n` streams given by `d_map` (nullptr = streams 0..n-1).
 int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out,
                  int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx)
@@ -660,6 +726,8 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
     return NAM_HIP_OK;
   const Plan& p = *g.plan;
   const KernelFn fn = select_kernel(b, g, n_frames, ctx);
+  if (fn == FN_LINEAR)
+    return launch_linear_group(b, g, d_map, n, d_in, d_out, n_frames, io_stride, s);
   if (p.arch != ARCH_WAVENET)
   {
     LSTMArgs a = lstm_args(p.lstm);
@@ -708,6 +776,14 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
   if (n <= 0)
     return NAM_HIP_OK;
   const Plan& p = *g.plan;
+  if (p.arch == ARCH_LINEAR)
+  {
+    // the history of a freshly constructed reference model: zeros (include/nam_hip.h: the reference's two engines keep different
+    // things across Reset). No prewarm: GetPrewarmSamples() is 0 (dsp.h:153)
+    NAM_HIP_CHECK(hipMemsetAsync(g.d_lin_hist.get(), 0, (size_t)g.lin_hist_frames * g.lin_cols_pad * sizeof(float), b->stream.get()));
+    g.lin_pos = 0;
+    return NAM_HIP_OK;
+  }
   const int frames = prewarm ? prewarm_frames(b, p) : 0;
   const bool all = n == (int)g.streams.size();
   if (p.arch == ARCH_WAVENET)

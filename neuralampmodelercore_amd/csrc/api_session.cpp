@@ -22,6 +22,8 @@ int persist_kind(const nam_hip_batch* b)
   const WidthGroup& g = b->groups[b->model->full_width];
   if (!b->ps.enabled)
     return PERSIST_NONE;
+  if (g.plan->arch == ARCH_LINEAR) // no recurrence, nothing to keep resident: a Linear batch launches per call (Linear, follow-up)
+    return PERSIST_NONE;
   const int cus = std::max(b->n_cus, 1);
   {
     // nam_wn_reg_kernel serves every width group with one launch: a mixed-width batch is one session. Its workgroups

@@ -262,6 +262,26 @@ inline bool lstm_mfma_in_registers(const L& l) // nam_lstm_mfma_reg_kernel: ever
   return l.input_size <= 4 && l.n_layers <= 2 && l.mf_nt <= 6;
 }
 
+// Linear (plan.h: LinearPlan; kernel_linear.hip). One PIECE of a launch: n_frames <= the batch's piece length.
+struct LinearArgs
+{
+  const float* blob; // the padded taps (LinearPlan)
+  float* hist; // [hist_frames][cols_pad]: the batch's input history, a ring; row `pos` receives frame 0 of this piece
+  float* part; // [n_splits][part_frames][cols_pad]: the splits' partial sums of this piece
+  const float* in; // planar [stream][in_ch][io_stride], nullptr = silence
+  float* out; // planar [stream][out_ch][io_stride], nullptr = append only
+  long io_stride;
+  int n_frames;
+  int n_streams, in_ch, out_ch, cols_per_stream;
+  int n_cols, cols_pad; // n_streams * cols_per_stream, rounded up to a multiple of kLinearColTile (padded columns stay zero)
+  int hist_frames, pos;
+  int part_frames; // a multiple of 64, >= n_frames
+  int n_splits, split_taps, taps_off;
+  float bias;
+};
+// append + nam_linear_kernel + nam_linear_reduce_kernel (+ zeros for output channels >= cols_per_stream), enqueued on `stream`
+hipError_t launch_linear(const LinearArgs& a, hipStream_t stream);
+
 // nam_wn_reg_kernel (plan.h: WrPlan). One launch serves up to kWrMaxGroups WIDTH GROUPS — streams of a slimmable model
 // (or container) that currently run different sub-models: workgroups [first, next group's first) belong to group g, each
 // with its own op list, weights, LDS layout and state ("LDS repacking" per width); the audio windows are shared.

@@ -23,6 +23,16 @@ struct FileValidationError : std::runtime_error
   }
 };
 
+// A valid .nam document the device path does not run (a Linear model beyond the device limits, inside a container ...):
+// NAM_HIP_ERR_UNSUPPORTED at the C boundary, where every other std::runtime_error is NAM_HIP_ERR_MODEL.
+struct UnsupportedError : std::runtime_error
+{
+  explicit UnsupportedError(const std::string& m)
+  : std::runtime_error(m)
+  {
+  }
+};
+
 enum ActType : int
 {
   ACT_IDENTITY = 0,
@@ -162,11 +172,27 @@ struct LSTMSpec
   long expected_weight_count() const;
 };
 
+// nam::Linear (NAM/linear.cpp:61-80,168-196,306-323): an impulse response. y[ch][n] = bias + sum_{k < R} weights[k] x[ch][n - k] for
+// ch < min(in, out) — one IR for every channel, no mixing —, output channels beyond that are 0 (linear.cpp:191-195).
+constexpr int kLinearMaxReceptiveField = 65536; // device limit: 1.4 s at 48 kHz (every block-size tier of the reference's FFT engine)
+constexpr int kLinearMaxChannels = 16; // device limit, as the LSTM kernels' output channels
+struct LinearSpec
+{
+  int receptive_field = 0;
+  bool bias = false;
+  int in_channels = 1;
+  int out_channels = 1;
+  std::string implementation = "auto"; // as given; validated (linear.cpp:280-293) and otherwise ignored: one device engine
+  std::vector<float> weights; // [receptive_field] taps, lag 0 first, then the bias when `bias`
+  long expected_weight_count() const { return (long)receptive_field + (bias ? 1 : 0); }
+};
+
 enum Arch : int
 {
   ARCH_WAVENET = 1,
   ARCH_LSTM = 2,
-  ARCH_CONTAINER = 3 // SlimmableContainer (NAM/container.cpp): submodels of different sizes, one active at a time
+  ARCH_CONTAINER = 3, // SlimmableContainer (NAM/container.cpp): submodels of different sizes, one active at a time
+  ARCH_LINEAR = 4
 };
 
 struct ModelSpec
@@ -182,14 +208,26 @@ struct ModelSpec
   std::string architecture_name, config_text, metadata_text = "null";
   WaveNetSpec wavenet;
   LSTMSpec lstm;
+  LinearSpec linear;
   // ARCH_CONTAINER: submodels sorted by ascending max_value; SetSlimmableSize(v) activates the first one with
   // v < max_value, else the last (container.cpp:103-115). The container itself is always 1-in / 1-out
   // (container.cpp:19) and has no weights of its own.
   std::vector<double> sub_max_value;
   std::vector<std::shared_ptr<ModelSpec>> submodels;
 
-  int in_channels() const { return arch == ARCH_WAVENET ? wavenet.in_channels : arch == ARCH_LSTM ? lstm.in_channels : 1; }
-  int out_channels() const { return arch == ARCH_WAVENET ? wavenet.out_channels() : arch == ARCH_LSTM ? lstm.out_channels : 1; }
+  int in_channels() const
+  {
+    return arch == ARCH_WAVENET ? wavenet.in_channels : arch == ARCH_LSTM ? lstm.in_channels : arch == ARCH_LINEAR ? linear.in_channels : 1;
+  }
+  int out_channels() const
+  {
+    return arch == ARCH_WAVENET ? wavenet.out_channels() : arch == ARCH_LSTM ? lstm.out_channels : arch == ARCH_LINEAR ? linear.out_channels : 1;
+  }
+  // the model's own flat weight stream (a container has none)
+  const std::vector<float>* weights() const
+  {
+    return arch == ARCH_WAVENET ? &wavenet.weights : arch == ARCH_LSTM ? &lstm.weights : arch == ARCH_LINEAR ? &linear.weights : nullptr;
+  }
   int prewarm_samples() const;
   int container_index(double val) const; // container.cpp:103-115
 };

@@ -48,7 +48,7 @@ int nam_hip_version_support(const char* nam_file_version)
 
 const char* nam_hip_version(void)
 {
-  return "nam_hip 0.2.5 gfx950"; // 0.2.5: nam_hip_bank_create accepts the nam_wn_reg_kernel family (the official nano size, FiLM / gated / nested condition_dsp / post-stack head models, narrow plain stacks: members of one program); 0.2.4: nam_hip_bank_create accepts the LSTM family (cells nam_lstm_row_kernel / nam_lstm_wide_kernel take); 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
+  return "nam_hip 0.2.6 gfx950"; // 0.2.6: Linear models load and run (NAM_HIP_ARCH_LINEAR, nam_linear_kernel); NAM_HIP_ERR_UNSUPPORTED for a Linear model beyond the device limits; 0.2.5: nam_hip_bank_create accepts the nam_wn_reg_kernel family (the official nano size, FiLM / gated / nested condition_dsp / post-stack head models, narrow plain stacks: members of one program); 0.2.4: nam_hip_bank_create accepts the LSTM family (cells nam_lstm_row_kernel / nam_lstm_wide_kernel take); 0.2.3: nam_hip_bank_create accepts the A2 family (A2-topology WaveNets, containers standing for their largest submodel); 0.2.2: model banks (nam_hip_bank_*, nam_hip_batch_create_bank, nam_hip_batch_set / get_stream_model); 0.2.1: nam_hip_model_info has_a1_kernel bits 2 and 3 always equal (include/nam_hip.h); 0.2: nam_hip_load_options::struct_size (0.1 callers: the first 16 bytes are read)
 }
 
 int nam_hip_model_load(const char* nam_path, int fast_tanh, nam_hip_model** out_model)
@@ -207,7 +207,7 @@ int64_t nam_hip_model_get_weights(const nam_hip_model* model, float* out, int64_
   if (!model || capacity < 0)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_model_get_weights: bad argument");
   const ModelSpec& s = *model->spec;
-  const std::vector<float>* w = s.arch == ARCH_WAVENET ? &s.wavenet.weights : s.arch == ARCH_LSTM ? &s.lstm.weights : nullptr;
+  const std::vector<float>* w = s.weights(); // (WaveNet, LSTM, Linear: the file's stream; a container has none of its own)
   const int64_t n = w ? (int64_t)w->size() : 0;
   if (out && w)
     std::memcpy(out, w->data(), (size_t)std::min(n, capacity) * sizeof(float));
@@ -250,7 +250,10 @@ int nam_hip_model_get_info(const nam_hip_model* model, nam_hip_model_info* info)
   std::memset(info, 0, sizeof(*info));
   const ModelSpec& s = *model->spec;
   const Plan& p = model->plans[model->full_width];
-  info->architecture = s.arch == ARCH_WAVENET ? NAM_HIP_ARCH_WAVENET : s.arch == ARCH_LSTM ? NAM_HIP_ARCH_LSTM : NAM_HIP_ARCH_CONTAINER;
+  info->architecture = s.arch == ARCH_WAVENET ? NAM_HIP_ARCH_WAVENET
+                       : s.arch == ARCH_LSTM  ? NAM_HIP_ARCH_LSTM
+                       : s.arch == ARCH_LINEAR ? NAM_HIP_ARCH_LINEAR
+                                               : NAM_HIP_ARCH_CONTAINER;
   info->in_channels = s.in_channels();
   info->out_channels = s.out_channels();
   // what GetPrewarmSamples() of the reference object returns: a SlimmableWavenet answers 0 (slimmable.h:66 — its
@@ -264,9 +267,7 @@ int nam_hip_model_get_info(const nam_hip_model* model, nam_hip_model_info* info)
   info->loudness = s.loudness;
   info->input_level = s.input_level;
   info->output_level = s.output_level;
-  info->num_weights = s.arch == ARCH_WAVENET ? (int64_t)s.wavenet.weights.size()
-                      : s.arch == ARCH_LSTM  ? (int64_t)s.lstm.weights.size()
-                                             : 0; // a container has no weights of its own
+  info->num_weights = s.weights() ? (int64_t)s.weights()->size() : 0; // a container has no weights of its own
   info->fast_tanh = s.fast_tanh ? 1 : 0;
   info->has_a1_kernel = (p.a1.valid ? 1 : 0) | ((p.a1.valid && (p.a1.ws_ok || p.a1.kt_ok)) ? 2 : 0)
                         | ((p.a1.valid && p.a1.il_ok && p.a1.p2_ok) ? 4 | 8 : 0)
@@ -818,6 +819,13 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
     if (rc != NAM_HIP_OK)
       return rc;
   }
+  if (batch->model->spec->arch == ARCH_LINEAR) // one device engine (include/nam_hip.h): nothing to choose
+  {
+    if (kernel != NAM_HIP_KERNEL_AUTO)
+      return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_batch_set_kernel: a Linear batch runs nam_linear_kernel only (NAM_HIP_KERNEL_AUTO)");
+    batch->kernel = kernel;
+    return NAM_HIP_OK;
+  }
   bool all_lstm = true;
   for (const auto& g : batch->groups)
     all_lstm = all_lstm && g.plan->arch == ARCH_LSTM;
@@ -871,6 +879,8 @@ int nam_hip_batch_get_kernel(const nam_hip_batch* batch)
   if (!batch)
     return NAM_HIP_ERR_INVALID_ARGUMENT;
   const WidthGroup& g = batch->groups[batch->model->full_width];
+  if (g.plan->arch == ARCH_LINEAR)
+    return NAM_HIP_KERNEL_AUTO; // (the only choice nam_hip_batch_set_kernel admits)
   if (g.plan->arch != ARCH_WAVENET)
     return NAM_HIP_KERNEL_GENERIC;
   return pick_kernel(batch, g);

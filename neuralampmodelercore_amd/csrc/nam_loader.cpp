@@ -13,6 +13,7 @@
 #include "model_spec.h"
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -493,6 +494,8 @@ int ModelSpec::prewarm_samples() const
     return wavenet.prewarm_samples();
   if (arch == ARCH_CONTAINER) // of the active submodel; a fresh container has the last one active (container.cpp:49,139-144)
     return submodels.back()->prewarm_samples();
+  if (arch == ARCH_LINEAR) // the DSP base's GetPrewarmSamples (dsp.h:153): Linear does not override it
+    return 0;
   // LSTM::GetPrewarmSamples lstm.cpp:127-134
   const int r = (int)(0.5 * sample_rate);
   return r <= 0 ? 1 : r;
@@ -771,6 +774,43 @@ static std::shared_ptr<ModelSpec> build_model(const Value& root, const LoadOptio
       throw std::runtime_error("LSTM weight mismatch: model expects " + std::to_string(c.expected_weight_count())
                                + " weights, but " + std::to_string(c.weights.size()) + " were provided.");
   }
+  else if (arch == "Linear")
+  {
+    // linear::parse_config_json + the Linear ctor (NAM/linear.cpp:306-323, 61-80)
+    m->arch = ARCH_LINEAR;
+    LinearSpec& c = m->linear;
+    c.receptive_field = config.at("receptive_field").as_int();
+    c.bias = config.at("bias").as_bool();
+    c.in_channels = config.value_int("in_channels", 1);
+    c.out_channels = config.value_int("out_channels", 1);
+    if (const Value* impl = config.find("implementation"))
+      c.implementation = impl->as_string();
+    {
+      // parse_implementation (linear.cpp:280-293): case-insensitive; the device runs one engine whatever it says
+      std::string normalized = c.implementation;
+      for (char& ch : normalized)
+        ch = (char)std::tolower((unsigned char)ch);
+      static const char* const known[] = {"auto", "direct", "legacy", "old", "fft", "partitioned_fft", "partitioned-fft"};
+      bool ok = false;
+      for (const char* k : known)
+        ok = ok || normalized == k;
+      if (!ok)
+        throw std::runtime_error("Unsupported Linear implementation: " + c.implementation);
+    }
+    if (c.in_channels <= 0 || c.out_channels <= 0)
+      throw std::runtime_error("Channel counts must be positive");
+    if (c.receptive_field < 1)
+      throw std::runtime_error("Linear: receptive_field must be >= 1");
+    c.weights = std::move(weights);
+    if (c.expected_weight_count() != (long)c.weights.size())
+      throw std::runtime_error("Params vector does not match expected size based on architecture parameters");
+    if (c.receptive_field > kLinearMaxReceptiveField)
+      throw UnsupportedError("Linear: receptive_field " + std::to_string(c.receptive_field) + " exceeds the device limit of "
+                             + std::to_string(kLinearMaxReceptiveField) + " taps");
+    if (c.in_channels > kLinearMaxChannels || c.out_channels > kLinearMaxChannels)
+      throw UnsupportedError("Linear: " + std::to_string(std::max(c.in_channels, c.out_channels))
+                             + " channels exceed the device limit of " + std::to_string(kLinearMaxChannels) + " channels");
+  }
   else if (arch == "SlimmableContainer")
   {
     // ContainerConfig::create + ContainerModel ctor (container.cpp:17-50,150-171)
@@ -788,6 +828,10 @@ static std::shared_ptr<ModelSpec> build_model(const Value& root, const LoadOptio
         throw std::runtime_error("ContainerModel: submodels must be sorted by ascending max_value");
     if (m->sub_max_value.back() < 1.0)
       throw std::runtime_error("ContainerModel: last submodel max_value must be >= 1.0");
+    for (size_t i = 0; i < m->submodels.size(); i++)
+      if (m->submodels[i]->arch == ARCH_LINEAR) // (one shared impulse response per batch: nam_linear_kernel knows no width groups)
+        throw UnsupportedError("SlimmableContainer: submodel " + std::to_string(i)
+                               + " is a Linear model, which the device path runs only as a batch's one model");
     for (const auto& sm : m->submodels)
     {
       if (sm->sample_rate != m->sample_rate && sm->sample_rate != -1.0 && m->sample_rate != -1.0)

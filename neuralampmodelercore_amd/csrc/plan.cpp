@@ -180,8 +180,42 @@ static Plan build_lstm_plan(const ModelSpec& model)
   return plan;
 }
 
+// plan.h: LinearPlan. The splits are a function of R alone (determinism across stream counts); at 256 streams (8 column
+// tiles) and one 64-frame tile, R = 8,192 makes 8 x 64 = 512 one-wave workgroups: two per CU, every CU busy.
+static Plan build_linear_plan(const ModelSpec& model)
+{
+  const LinearSpec& c = model.linear;
+  if (c.receptive_field < 1 || c.receptive_field > kLinearMaxReceptiveField || c.in_channels < 1 || c.out_channels < 1
+      || c.in_channels > kLinearMaxChannels || c.out_channels > kLinearMaxChannels
+      || (long)c.weights.size() != c.expected_weight_count())
+    throw std::runtime_error("plan: Linear model outside the device limits");
+  Plan plan;
+  plan.arch = ARCH_LINEAR;
+  plan.in_channels = c.in_channels;
+  plan.out_channels = c.out_channels;
+  plan.prewarm_samples = 0;
+  LinearPlan& L = plan.linear;
+  const int R = c.receptive_field;
+  L.receptive_field = R;
+  L.in_ch = c.in_channels;
+  L.out_ch = c.out_channels;
+  L.cols_per_stream = std::min(c.in_channels, c.out_channels);
+  const int want = std::min(kLinearMaxSplits, (R + kLinearSplitTapsMin - 1) / kLinearSplitTapsMin);
+  L.split_taps = ((R + want - 1) / want + kBlock - 1) / kBlock * kBlock;
+  L.n_splits = (R + L.split_taps - 1) / L.split_taps;
+  L.bias = c.bias ? c.weights[(size_t)R] : 0.0f;
+  L.taps_off = kLinearPad;
+  plan.blob.assign((size_t)kLinearPad + (size_t)L.n_splits * L.split_taps + kLinearPad, 0.0f);
+  std::copy(c.weights.begin(), c.weights.begin() + R, plan.blob.begin() + L.taps_off);
+  plan.state_floats = L.hist_frames(0) * L.cols_per_stream;
+  L.valid = 1;
+  return plan;
+}
+
 Plan build_plan(const ModelSpec& model, WrShapeSet* jit_shapes)
 {
+  if (model.arch == ARCH_LINEAR)
+    return build_linear_plan(model);
   if (model.arch == ARCH_WAVENET)
   {
     if (model.wavenet.slimmable)
@@ -200,6 +234,9 @@ std::string Plan::describe() const
      << " blob=" << blob.size() << " lds_rows=" << lds_rows << " rings=" << n_rings
      << " state_floats=" << state_floats << " a1=" << a1.valid << " lstm=" << lstm.valid
      << " prewarm=" << prewarm_samples;
+  if (arch == ARCH_LINEAR) // (hist_frames: of a batch whose max_frames is at most piece_cap; a longer max_frames adds the difference)
+    ss << " kernel=nam_linear_kernel receptive_field=" << linear.receptive_field << " hist_frames=" << linear.hist_frames(0)
+       << " splits=" << linear.n_splits << " split_taps=" << linear.split_taps << " piece_cap=" << kLinearPieceCap;
   return ss.str();
 }
 

@@ -14,6 +14,7 @@
 //   * `a1`      (optional) description for the specialised register-resident kernel used for the
 //               plain "A1" WaveNet family (ungated, no FiLM, groups=1): wavenet_a1_standard.nam.
 //   * `lstm`    (optional) description for the LSTM kernel (NAM/lstm.cpp:31-168).
+//   * `linear`  (optional) description for the Linear kernels (NAM/linear.cpp:168-196): the impulse response's K-splits.
 #pragma once
 
 #include <cstdint>
@@ -660,6 +661,42 @@ struct LSTMPlan
   int32_t mf_lds_bytes = 0; // region + h (double buffered) + c + I/O tiles
 };
 
+// ---- Linear (nam_linear_kernel; kernel_linear.hip) -----------------------------------------------------------------
+// One impulse response shared by every column (column = stream x channels-per-stream + channel): a block of 64 output
+// frames of 32 columns is a real GEMM, (64 x K Toeplitz matrix of the IR) . (K x 32 rows of input history), on
+// v_mfma_f32_32x32x2_f32. The IR's R taps are cut into `n_splits` runs of `split_taps` taps (K-splits: one wavefront each,
+// partial sums to a scratch buffer, summed in split order by nam_linear_reduce_kernel). Both counts depend on R ALONE:
+// the order of summation, and with it every output bit, is the same at any stream count and launch length.
+// blob:    [kLinearPad zeros | the R taps, lag 0 first | zeros up to n_splits * split_taps | kLinearPad zeros]: a wavefront
+//          copies its split's taps from there without a bounds check (the kernel masks them to its split in LDS).
+// history: NOT the per-stream [stream][state] layout of the other architectures: one ring [hist_frames][padded columns] of the
+//          batch's input, stream-minor — a row is one coalesced read, an append one coalesced write (api_internal.h:
+//          WidthGroup::d_lin_hist). hist_frames = n_splits * split_taps + one launch piece, the piece being
+//          max(max_frames, kLinearPieceCap) frames: longer launches (a render, process_device of any length) are cut into
+//          pieces by the host (api_launch.cpp: launch_linear).
+constexpr int kLinearPad = 64; // zeros on both sides of the taps: one frame tile
+constexpr int kLinearColTile = 32; // columns per wavefront (the N of the matrix instruction)
+constexpr int kLinearSplitTapsMin = 128, kLinearMaxSplits = 64;
+constexpr int kLinearPieceCap = 512; // frames per launch piece when max_frames is smaller (profiles/linear/README.md)
+constexpr int kLinearPieceMax = 4096; // ... and at most, however long max_frames is (the partial sums are n_splits x piece x columns floats)
+struct LinearPlan
+{
+  int32_t valid = 0;
+  int32_t receptive_field = 0;
+  int32_t in_ch = 1, out_ch = 1;
+  int32_t cols_per_stream = 1; // min(in, out): the channels that carry signal (linear.cpp:177)
+  int32_t n_splits = 1, split_taps = kBlock; // K-splits and taps per split (a multiple of 64)
+  int32_t taps_off = 0; // blob float offset of lag 0 (= kLinearPad)
+  float bias = 0.0f;
+  int piece_frames(int max_frames) const
+  {
+    return max_frames > kLinearPieceMax ? kLinearPieceMax : max_frames > kLinearPieceCap ? max_frames : kLinearPieceCap;
+  }
+  // frames of input history a batch keeps: every split's taps (zero-padded ones included, so that a padded tap reads real,
+  // older input and never a frame of the piece being written) + one piece
+  int hist_frames(int max_frames) const { return n_splits * split_taps + piece_frames(max_frames); }
+};
+
 struct Plan
 {
   int arch = 0;
@@ -678,6 +715,7 @@ struct Plan
   A1Plan a1;
   LSTMPlan lstm;
   WrPlan wr;
+  LinearPlan linear; // (state_floats: the history per stream of a batch with max_frames <= kLinearPieceCap)
   std::string describe() const;
 };
 

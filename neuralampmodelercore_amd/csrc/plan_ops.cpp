@@ -244,7 +244,8 @@ struct Builder
     if (wn.condition_dsp)
     {
       if (wn.condition_dsp->arch != ARCH_WAVENET)
-        throw std::runtime_error("plan: condition_dsp must be a WaveNet for the device path");
+        throw UnsupportedError("plan: a condition_dsp that is not a WaveNet (" + wn.condition_dsp->architecture_name
+                               + "): the device path nests WaveNets only");
       cond = wavenet(wn.condition_dsp->wavenet, in_rows);
       cond_dim = wn.condition_dsp->wavenet.out_channels();
     }
