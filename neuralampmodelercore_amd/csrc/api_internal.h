@@ -6,6 +6,7 @@
 //   api_host_io.cpp   host buffers: the windows both sides can reach, blocking calls through a session, tickets
 //   api_bank.cpp      model banks: the families' rules (kBankFamily), which models may share a batch, the bank's device image,
 //                     per-stream member binding
+//   launch_policy.h   nam_wn_reg_kernel's launch shape, workgroups per CU and stream bound: integers in, integers out (no HIP)
 // No exception leaves these files (guarded); errors are codes + nam_hip_last_error.
 #pragma once
 #include "../../include/nam_hip.h"
@@ -26,6 +27,7 @@
 
 #include "device_owner.h"
 #include "kernels.h"
+#include "launch_policy.h"
 #include "model_spec.h"
 #include "plan.h"
 #include "wr_jit.h"
@@ -135,6 +137,17 @@ namespace namhip
 {
 namespace api
 {
+static_assert(kCuLdsBytes == kLdsCu, "launch_policy.h counts workgroups per CU with the kernels' LDS size");
+
+// Which layout a WaveNet group's state holds (WidthGroup::state_family; state_family_of, persist_family)
+enum StateFamily : int
+{
+  STATE_FRESH = -1, // freshly zeroed: any layout may follow
+  STATE_OPS = 0, // the op program's rings (shared by the A1 kernels unless they run on zero-padded channels: plan.h, Plan::a1_padded_layout)
+  STATE_A1_PADDED = 1, // the padded A1 rings
+  STATE_WN_REG = 2 // nam_wn_reg_kernel's 64-frame conv-input histories
+};
+
 // (every device allocation is an owner, device_owner.h: `g = WidthGroup()` frees the group's, and so does the batch's end)
 struct WidthGroup
 {
@@ -150,10 +163,7 @@ struct WidthGroup
   long state_stride = 0;
   std::vector<int> streams; // members, ascending
   DeviceBuf<int> d_map; // device copy of `streams` (empty when the group is all streams in order)
-  // Which layout the state currently holds: -1 = freshly zeroed (any), 0 = the op program's rings (shared by the A1
-  // kernels unless they run on zero-padded channels: plan.h, Plan::a1_padded_layout), 1 = the padded A1 rings,
-  // 2 = nam_wn_reg_kernel's 64-frame conv-input histories
-  int state_family = -1;
+  StateFamily state_family = STATE_FRESH; // which layout the state currently holds
   // Prewarm cache (the reference caches what prewarm leaves in every conv, conv1d.cpp:151-161 / model.cpp:737-775, and
   // later Resets refill from it): one stream's state right after zero + prewarm — every stream's is the same — keyed by
   // the kernel that produced it and the frames it ran. A later Reset / SetSlimmableSize copies it instead of running
@@ -345,7 +355,7 @@ enum PersistKind : int
   PERSIST_KQ = 4 // nam_kq_kernel (the A2 topology): one workgroup (most of a CU's LDS) per stream, as PERSIST_A1_P2
 };
 
-constexpr int kPersistTurns = 8; // sessions whose workgroups cannot all be on the chip at once: up to this many turns (they consume the same commands one after the other)
+// (kPersistTurns, how many turns a session's workgroups may take on the chip: launch_policy.h)
 constexpr int kGraceUs = 40; // how long a fresh launch looks for the doorbell it was started for
 constexpr int kPersistMaxFrames = 2048; // buffers up to this long go through the session as n_frames / 64 commands
 
@@ -430,7 +440,7 @@ struct SessionCaller // (a bare stream: a caller without hints)
 int upload_group(nam_hip_batch* b, WidthGroup& g);
 int ensure_state(nam_hip_batch* b, WidthGroup& g);
 hipError_t quiesce(nam_hip_batch* b);
-int state_family_of(const Plan& p, int kernel);
+StateFamily state_family_of(const Plan& p, int kernel);
 int refresh_map(nam_hip_batch* b, WidthGroup& g);
 int pick_kernel(const nam_hip_batch* b, const WidthGroup& g);
 const char* group_kernel_name(const nam_hip_batch* b, const WidthGroup& g, int n_frames);
@@ -449,7 +459,7 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
 // members' initial states (an LSTM bank), Reset (+ prewarm as the batch was last reset), and the batch's stream drained
 int reset_moved_streams(nam_hip_batch* b, WidthGroup& g, const std::vector<int>& moved, bool fill_initial_states);
 // api_session.cpp
-int persist_family(const nam_hip_batch* b, const WidthGroup& g);
+StateFamily persist_family(const nam_hip_batch* b, const WidthGroup& g);
 int persist_kind(const nam_hip_batch* b);
 int persist_flush(nam_hip_batch* b, const SessionCaller& caller);
 int persist_wait(nam_hip_batch* b, const SessionCaller& caller, unsigned target, bool whole);
@@ -495,6 +505,14 @@ inline bool kq_runs(const nam_hip_batch*, const Plan& p)
 inline int session_linger_ticks(const nam_hip_batch* b)
 {
   return (b->blocking_linger && !b->pipe_session) ? b->blocking_linger_us * 100 : b->ticket_linger;
+}
+
+// Whether the session's running launch lingers for the next command instead of leaving when the ring is empty (A1Args::p_linger):
+// it publishes every command, the host can store its "leave" word itself, and every workgroup is on the chip at once (more
+// workgroups than CUs take turns: the ones on the chip must leave when the ring is empty). The host and the resident kernel must agree.
+inline bool session_lingers(const nam_hip_batch* b)
+{
+  return b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus;
 }
 
 inline double stat_now_us()

@@ -37,7 +37,6 @@ int upload_group(nam_hip_batch* b, WidthGroup& g)
     return NAM_HIP_OK;
   }
   g.state_stride = p.state_floats;
-  (void)b;
   return NAM_HIP_OK;
 }
 
@@ -82,11 +81,23 @@ hipError_t quiesce(nam_hip_batch* b)
   return e;
 }
 
-int state_family_of(const Plan& p, int kernel)
+StateFamily state_family_of(const Plan& p, int kernel)
 {
   if (kernel == NAM_HIP_KERNEL_WN_REG)
-    return 2;
-  return (p.a1_padded_layout && kernel != NAM_HIP_KERNEL_GENERIC) ? 1 : 0;
+    return STATE_WN_REG;
+  return (p.a1_padded_layout && kernel != NAM_HIP_KERNEL_GENERIC) ? STATE_A1_PADDED : STATE_OPS;
+}
+
+// The op program, the A1 kernels of a channel-padded model and nam_wn_reg_kernel keep different ring layouts: a launch that would
+// run `fam` on state of another one is refused — a change of kernel family is only legal on freshly reset state — else the state is `fam`'s
+static int claim_state_family(WidthGroup& g, StateFamily fam)
+{
+  if (g.state_family != STATE_FRESH && g.state_family != fam)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT,
+                "kernel change crosses state layouts (the op program's rings, the A1 kernels' zero-padded rings and "
+                "nam_wn_reg_kernel's conv-input histories differ): call nam_hip_batch_reset before switching");
+  g.state_family = fam;
+  return NAM_HIP_OK;
 }
 
 int refresh_map(nam_hip_batch* b, WidthGroup& g)
@@ -142,12 +153,8 @@ int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
         // per stream: 8.1 k xRT at any stream count with a launch per buffer, 13.2 k / 21.7 k / 40.5 k at 512 / 1,024 / 2,048
         // streams on the VALU kernel; 48.6 k in a session at 256).
         // Decided on the batch's stream count, which never changes: the two kernels keep different state layouts.
-        if (wr && a1)
-        {
-          const int per_cu = std::min(4, (160 * 1024) / (g.plan->wr.lds_bytes + 512));
-          if (b->n_streams > kPersistTurns * std::max(per_cu, 1) * std::max(b->n_cus, 1)) // (a session's workgroups may take turns)
-            return NAM_HIP_KERNEL_A1;
-        }
+        if (wr && a1 && b->n_streams > wr_stream_bound(g.plan->wr.lds_bytes, b->n_cus)) // (a session's workgroups may take turns)
+          return NAM_HIP_KERNEL_A1;
         return wr ? NAM_HIP_KERNEL_WN_REG : fallback;
       }
       // The K-tap kernel (A2 shapes) spreads a stream over four wavefronts: 2.3x the VALU kernel while the chip has
@@ -191,66 +198,9 @@ static void session_args(const nam_hip_batch* b, const LaunchContext& ctx, A1Arg
   a.p_cmd0 = pa.cmd0;
   a.p_grace = pa.grace;
   a.p_out_host = b->ps.out_is_host ? (b->ps.cmd_done_published ? 2 : 1) : 0;
-  a.p_linger = (b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus) ? session_linger_ticks(b) : 0; // (more workgroups than CUs take turns: the ones on the chip must leave when the ring is empty)
+  a.p_linger = session_lingers(b) ? session_linger_ticks(b) : 0;
   a.p_cmd_count = b->ps.d_cmd_count.get();
   a.p_cmd_done = b->ps.cmd_done.dev();
-}
-
-// The function of a per-model code object on the current device (hipModuleLoad is per device: cached per path and
-// device for the life of the process; a handful of entries).
-// `dense`: the form built for two wavefronts per SIMD (kernel_wn_reg.hip: nam_wn_reg_jit2d / 4d); *dense_ok (optional) reports
-// which stage counts have one the compiler fitted into 256 registers WITHOUT scratch (bit 1: two stages, bit 2: four).
-static int wr_jit_function(const std::string& path, int device, int stages, void** fn, bool dense = false, int* dense_ok = nullptr)
-{
-  struct Entry
-  {
-    std::string path;
-    int device;
-    hipModule_t module;
-    hipFunction_t fn, fn2, fn4; // nam_wn_reg_jit, nam_wn_reg_jit2 (two stages), nam_wn_reg_jit4
-    hipFunction_t fn2d, fn4d; // the dense forms (nullptr: not usable)
-  };
-  static std::vector<Entry> cache;
-  static std::mutex mu;
-  std::lock_guard<std::mutex> lock(mu);
-  auto pick = [&](const Entry& e) {
-    if (dense_ok)
-      *dense_ok = (e.fn2d ? 2 : 0) | (e.fn4d ? 4 : 0);
-    if (fn)
-      *fn = reinterpret_cast<void*>(stages == 4 ? (dense && e.fn4d ? e.fn4d : e.fn4) : stages == 2 ? (dense && e.fn2d ? e.fn2d : e.fn2) : e.fn);
-  };
-  for (const Entry& e : cache)
-    if (e.device == device && e.path == path)
-    {
-      pick(e);
-      return NAM_HIP_OK;
-    }
-  Entry e{path, device, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  NAM_HIP_CHECK(hipModuleLoad(&e.module, path.c_str()));
-  NAM_HIP_CHECK(hipModuleGetFunction(&e.fn, e.module, "nam_wn_reg_jit"));
-  NAM_HIP_CHECK(hipModuleGetFunction(&e.fn2, e.module, "nam_wn_reg_jit2"));
-  NAM_HIP_CHECK(hipModuleGetFunction(&e.fn4, e.module, "nam_wn_reg_jit4"));
-  // more than the default 64 KB of dynamic LDS per workgroup (long dilations: up to 156 KB of rings)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn2), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn4), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
-  static const bool dense_on = [] { const char* v = std::getenv("NAM_HIP_WR_DENSE"); return !(v && v[0] == '0'); }();
-  for (int q = 0; q < 2 && dense_on; q++)
-  {
-    hipFunction_t f = nullptr;
-    if (hipModuleGetFunction(&f, e.module, q == 0 ? "nam_wn_reg_jit2d" : "nam_wn_reg_jit4d") != hipSuccess || !f)
-      continue;
-    int scratch = 1, regs = 1 << 20;
-    if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) != hipSuccess
-        || hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, f) != hipSuccess || scratch > 32 || regs > 256)
-      continue; // (spilled more than a handful of registers, or not a two-per-SIMD build after all: the one-wave-per-SIMD form serves)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
-    (q == 0 ? e.fn2d : e.fn4d) = f;
-  }
-  (void)hipGetLastError();
-  cache.push_back(e);
-  pick(e);
-  return NAM_HIP_OK;
 }
 
 // nam_wn_reg_kernel over up to kWrMaxGroups width groups in ONE launch (kernels.h: WrArgs): group k's `counts[k]` streams
@@ -258,6 +208,7 @@ static int wr_jit_function(const std::string& path, int device, int stages, void
 int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* maps, const int* counts, int n_groups,
               const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx)
 {
+  // 1. the arguments, from the groups
   WrArgs a;
   std::memset(&a, 0, sizeof(a));
   int total = 0, lds_bytes = 0;
@@ -269,11 +220,8 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
     layers = layers || w.has_layers;
     runs = runs || w.has_runs;
     rt_layers = rt_layers || w.has_rt_layers;
-    if (g.state_family >= 0 && g.state_family != 2)
-      return fail(NAM_HIP_ERR_INVALID_ARGUMENT,
-                  "kernel change crosses state layouts (the op program's rings, the A1 kernels' zero-padded rings and "
-                  "nam_wn_reg_kernel's LDS-image rings differ): call nam_hip_batch_reset before switching");
-    g.state_family = 2;
+    if (const int rc = claim_state_family(g, STATE_WN_REG))
+      return rc;
     WrGroup& G = a.g[k];
     G.blob = g.d_wr_blob.get();
     G.state = g.d_state.get();
@@ -299,82 +247,6 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
     total += counts[k];
     lds_bytes = std::max(lds_bytes, w.lds_bytes);
   }
-  // Two or four wavefronts per stream (the program cut up, consecutive buffers in flight: kernel_wn_reg.hip, NST) when the
-  // launch holds more than one buffer and the chip has the SIMDs for it — config 4's 512 streams become 1,024
-  // wavefronts, 256 streams too
-  int stages = 1;
-  bool dense = false; // the two-wavefronts-per-SIMD build of the per-model code object
-  // (a session whose caller flushes after EVERY buffer is a series of one-buffer calls: nothing for a pipeline to overlap)
-  const bool session = ctx.session_kind != PERSIST_NONE;
-  const bool one_buffer_bursts = session && !b->pipe_session && b->ps.one_buffer_bursts();
-  if (!b->no_pipe && !ctx.hints.one_buffer_call && !one_buffer_bursts && (session || n_frames > kBlock))
-  {
-    // the launch's relative duration with nst waves per stream: a workgroup is nst waves at one wave per SIMD plus its LDS
-    // image (and the queues), the workgroups beyond what the chip holds run in later turns (persist_kind), and a stream's
-    // buffer takes 1, 1/1.75, 1/3.1 of the one-wave time (measured: DESIGN 4.5)
-    const int cus = std::max(b->n_cus, 1);
-    auto duration = [&](int nst) {
-      const int lds = lds_bytes + (nst - 1) * kWrQueueBytes;
-      if (lds > kWrMaxLdsBytes)
-        return 1e9;
-      const int on_chip = cus * std::min(4 / nst, (160 * 1024) / (lds + 512));
-      const double speed = nst == 4 ? 3.1 : nst == 2 ? 1.75 : 1.0;
-      const int turns = (total + on_chip - 1) / on_chip;
-      return turns * (1.0 + 0.15 * (turns - 1)) / speed; // a turn's last workgroups leave SIMDs idle; images move in and out
-    };
-    double best = duration(1);
-    if (can_split && b->wr_max_stages >= 2 && duration(2) < 0.9 * best)
-    {
-      stages = 2;
-      best = duration(2);
-    }
-    if (can_split && can_split4 && b->wr_max_stages >= 4 && duration(4) < 0.9 * best)
-    {
-      stages = 4;
-      best = duration(4);
-    }
-    // ... or the DENSE forms of a per-model code object (two wavefronts per SIMD: twice the workgroups per CU; two waves that
-    // share a SIMD each issue nearly as fast as a lone one — profiles/r05/valu_rate_microbench.txt: 8.6 cycles per instruction of
-    // a wave at one AND at two per SIMD — minus what they lose to each other's LDS traffic: 0.9)
-    // ONLY when the best one-per-SIMD form leaves SIMDs without a wavefront (config 5: 768 streams on 1,024 SIMDs): where it
-    // fills the chip exactly (config 4: 512 streams x 2, 1,024 x 1, 256 x 4) a second wavefront per SIMD only adds hand-overs —
-    // measured 3.95 vs 3.87 us (512 streams, four waves per stream dense vs two plain) and 7.59 vs 6.94 (1,024 streams)
-    const bool plain_fills = ((long)total * stages) % (4l * cus) == 0;
-    const std::string& module0 = groups[0]->plan->wr.jit_module;
-    if (!module0.empty() && can_split && b->wr_max_stages >= 2 && !plain_fills)
-    {
-      int ok = 0;
-      if (wr_jit_function(module0, b->device, 1, nullptr, false, &ok) == NAM_HIP_OK && ok != 0)
-      {
-        auto duration_dense = [&](int nst) {
-          const int lds = lds_bytes + (nst - 1) * kWrQueueBytes;
-          if (lds > kWrMaxLdsBytes)
-            return 1e9;
-          const int on_chip = cus * std::min(8 / nst, (160 * 1024) / (lds + 512));
-          const double speed = 0.9 * (nst == 4 ? 3.1 : 1.75);
-          const int turns = (total + on_chip - 1) / on_chip;
-          return turns * (1.0 + 0.15 * (turns - 1)) / speed;
-        };
-        if ((ok & 2) && duration_dense(2) < 0.9 * best)
-        {
-          stages = 2;
-          dense = true;
-          best = duration_dense(2);
-        }
-        if ((ok & 4) && can_split4 && b->wr_max_stages >= 4 && duration_dense(4) < 0.9 * best)
-        {
-          stages = 4;
-          dense = true;
-        }
-      }
-    }
-    lds_bytes += (stages - 1) * kWrQueueBytes;
-    if (stats_on() && (stages != b->wr_last_stages || dense != b->wr_last_dense))
-      std::fprintf(stderr, "nam_hip nam_wn_reg_kernel: %d workgroups as %d wavefront(s) per stream%s, %d bytes of LDS each\n", total, stages,
-                   dense ? " (two per SIMD)" : "", lds_bytes);
-    b->wr_last_stages = stages;
-    b->wr_last_dense = dense;
-  }
   a.n_groups = n_groups;
   a.in = d_in;
   a.out = d_out;
@@ -386,19 +258,45 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
   a.bank_member = groups[0]->d_bank_member.get(); // (a bank batch has one group: groups[0]->d_wr_blob is [members][bank_stride])
   a.bank_stride = groups[0]->bank_stride;
   // every group on the model's own code object (they share one: build_model), or every group on the ahead-of-time kernel
-  if (stages == 2) // (the kernels read a two-wave launch's cut from [1]: WrGroup::split_op)
-    for (int k = 0; k < n_groups; k++)
-      a.g[k].split_op[1] = groups[k]->plan->wr.split_op[3];
   const std::string& module = groups[0]->plan->wr.jit_module;
   for (int k = 1; k < n_groups; k++)
     if (groups[k]->plan->wr.jit_module != module)
       return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_wn_reg_kernel: the groups of one launch run different code objects");
+  const WrJitFunctions jit = module.empty() ? WrJitFunctions() : wr_jit_functions(module, b->device);
+  if (jit.rc != NAM_HIP_OK)
+    return jit.rc;
+  // 2. how many wavefronts per stream, and which build of them (launch_policy.h): more than one only when the launch holds more
+  // than one buffer
+  // (a session whose caller flushes after EVERY buffer is a series of one-buffer calls: nothing for a pipeline to overlap)
+  const bool session = ctx.session_kind != PERSIST_NONE;
+  const bool one_buffer_bursts = session && !b->pipe_session && b->ps.one_buffer_bursts();
+  WrShapeQuery q;
+  q.total = total;
+  q.lds_bytes = lds_bytes;
+  q.cus = b->n_cus;
+  q.max_stages = b->wr_max_stages;
+  q.can_split = can_split;
+  q.can_split4 = can_split4;
+  q.dense_forms = jit.dense_forms();
+  q.multi_buffer = !b->no_pipe && !ctx.hints.one_buffer_call && !one_buffer_bursts && (session || n_frames > kBlock);
+  const WrLaunchShape shape = wr_launch_shape(q);
+  const int stages = shape.stages;
+  if (q.multi_buffer)
+  {
+    if (stats_on() && (stages != b->wr_last_stages || shape.dense != b->wr_last_dense))
+      std::fprintf(stderr, "nam_hip nam_wn_reg_kernel: %d workgroups as %d wavefront(s) per stream%s, %d bytes of LDS each\n", total, stages,
+                   shape.dense ? " (two per SIMD)" : "", shape.lds_bytes);
+    b->wr_last_stages = stages;
+    b->wr_last_dense = shape.dense;
+  }
+  // 3. the launch, as `stages` wavefronts per stream
+  lds_bytes = shape.lds_bytes;
+  if (stages == 2) // (the kernels read a two-wave launch's cut from [1]: WrGroup::split_op)
+    for (int k = 0; k < n_groups; k++)
+      a.g[k].split_op[1] = groups[k]->plan->wr.split_op[3];
   if (!module.empty())
   {
-    void* fn = nullptr;
-    const int rc = wr_jit_function(module, b->device, stages, &fn, dense);
-    if (rc != NAM_HIP_OK)
-      return rc;
+    void* const fn = jit.pick(stages, shape.dense);
     NAM_HIP_CHECK(launch_wn_reg_jit(fn, a, total, lds_bytes, stages, LaunchStream(s, ctx.retired)));
     return NAM_HIP_OK;
   }
@@ -734,14 +632,8 @@ int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const
     common_args(a, g, d_map, d_in, d_out, n_frames, io_stride);
     return launch_lstm_family(b, g, fn, a, n, s, ctx);
   }
-  // the op program and the A1 kernels of a channel-padded model keep different ring layouts: a change of kernel
-  // family is only legal on freshly reset state
-  const int fam = state_family_of(p, family_for_launch(b, g, n_frames, ctx));
-  if (g.state_family >= 0 && g.state_family != fam)
-    return fail(NAM_HIP_ERR_INVALID_ARGUMENT,
-                "kernel change crosses state layouts (the op program's rings, the A1 kernels' zero-padded rings and "
-                "nam_wn_reg_kernel's conv-input histories differ): call nam_hip_batch_reset before switching");
-  g.state_family = fam;
+  if (const int rc = claim_state_family(g, state_family_of(p, family_for_launch(b, g, n_frames, ctx))))
+    return rc;
   if (fn == FN_WN_REG)
   {
     WidthGroup* one[1] = {&g};
@@ -792,8 +684,8 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
     {
       // a state cached by the same kernel over the same number of frames: copy it (every stream's is identical)
       const int kernel = kernel_for_launch(b, g, frames);
-      const int fam = state_family_of(p, kernel);
-      if (g.prewarm_kernel == kernel && g.prewarm_len == frames && (all || g.state_family < 0 || g.state_family == fam))
+      const StateFamily fam = state_family_of(p, kernel);
+      if (g.prewarm_kernel == kernel && g.prewarm_len == frames && (all || g.state_family == STATE_FRESH || g.state_family == fam))
       {
         NAM_HIP_CHECK(launch_fill_state(g.d_state.get(), g.state_stride, d_map, n, g.d_prewarm.get(), p.state_floats, p.state_floats, b->stream.get()));
         g.state_family = fam;
@@ -802,7 +694,7 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
     }
     NAM_HIP_CHECK(launch_fill_state(g.d_state.get(), g.state_stride, d_map, n, nullptr, 0, p.state_floats, b->stream.get()));
     if (all)
-      g.state_family = -1; // every stream of the group is zeroed: either layout may follow
+      g.state_family = STATE_FRESH; // every stream of the group is zeroed: either layout may follow
   }
   if (frames > 0)
   {

@@ -9,9 +9,9 @@ namespace api
 
 // ---- persistent block mode -------------------------------------------------------------------------------------
 // the state layout the session's kernel keeps (WaveNets only)
-int persist_family(const nam_hip_batch* b, const WidthGroup& g)
+StateFamily persist_family(const nam_hip_batch* b, const WidthGroup& g)
 {
-  return persist_kind(b) == PERSIST_WN_REG ? 2 : state_family_of(*g.plan, NAM_HIP_KERNEL_A1_IL);
+  return persist_kind(b) == PERSIST_WN_REG ? STATE_WN_REG : state_family_of(*g.plan, NAM_HIP_KERNEL_A1_IL);
 }
 
 // Which kernel a persistent session of this batch would run (PERSIST_NONE: the mode does not apply). Every workgroup
@@ -31,13 +31,12 @@ int persist_kind(const nam_hip_batch* b)
     const WrGroupList gs = wr_groups(const_cast<nam_hip_batch*>(b));
     if (gs.n > 0)
     {
-      int lds = 1;
+      int lds = 0;
       for (int k = 0; k < gs.n; k++)
         lds = std::max(lds, gs.g[k]->plan->wr.lds_bytes);
-      const int per_cu = std::min(4, (160 * 1024) / (lds + 512));
       // (more workgroups than the chip holds at once take turns, as below: each turn moves its streams' LDS images in and
       // out once and consumes every command that is there)
-      return b->n_streams <= kPersistTurns * per_cu * cus ? PERSIST_WN_REG : PERSIST_NONE;
+      return b->n_streams <= wr_stream_bound(lds, b->n_cus) ? PERSIST_WN_REG : PERSIST_NONE;
     }
   }
   if ((int)g.streams.size() != b->n_streams || g.d_map)
@@ -104,7 +103,7 @@ static int persist_launch(nam_hip_batch* b, CallHints hints, int grace_us, long 
     // ... and linger: a workgroup that finds itself up to date when a launch starts (another one's backlog was the reason for
     // the launch) must not leave at once — the commands to come would find it gone, and the rest of the launch would have to
     // linger and leave before the next launch could pick it up again
-    if (ps.cmd_done_published && ps.host_store_ok && ps.n_wg <= b->n_cus)
+    if (session_lingers(b))
     {
       ps.grace = std::max(ps.grace, session_linger_ticks(b));
       // "a workgroup of this launch has left" (il_common.h: session_leaving; p_cmd_count[mask + 2] = [kPRing + 1]): none yet
@@ -169,7 +168,7 @@ int persist_wait(nam_hip_batch* b, const SessionCaller& caller, unsigned target,
   if (!ps.active)
     return NAM_HIP_OK;
   bool told_leave = false;
-  if (whole && ps.outstanding && ps.cmd_done_published && ps.host_store_ok && ps.n_wg <= b->n_cus)
+  if (whole && ps.outstanding && session_lingers(b))
   {
     // a lingering launch: tell it that nothing follows command `seq` (kPRingTail)
     __atomic_store_n(&ps.d_ring.get()[kPRing], (unsigned long long)ps.seq, __ATOMIC_RELEASE);

@@ -6,7 +6,7 @@
 // model gets the same source compiled for exactly its own shapes the first time it is loaded (seconds; cached by a hash
 // of the shape tables, the kernel sources and the compiler, so the second load of any model with the same shapes — in
 // any process — is a file lookup).
-#include "wr_jit.h"
+#include "api_internal.h" // (NAM_HIP_CHECK for the code-object cache; wr_jit.h)
 
 #include <atomic>
 #include <dlfcn.h>
@@ -240,6 +240,60 @@ std::string wr_jit_build(const WrShapeSet& shapes, std::string& why)
     }
   }
   return out;
+}
+
+namespace
+{
+struct LoadedModule : WrJitFunctions
+{
+  std::string path;
+  int device = 0;
+  hipModule_t module = nullptr;
+};
+int load_module(LoadedModule& e, const std::string& path)
+{
+  NAM_HIP_CHECK(hipModuleLoad(&e.module, path.c_str()));
+  NAM_HIP_CHECK(hipModuleGetFunction(&e.fn, e.module, "nam_wn_reg_jit"));
+  NAM_HIP_CHECK(hipModuleGetFunction(&e.fn2, e.module, "nam_wn_reg_jit2"));
+  NAM_HIP_CHECK(hipModuleGetFunction(&e.fn4, e.module, "nam_wn_reg_jit4"));
+  // more than the default 64 KB of dynamic LDS per workgroup (long dilations: up to 156 KB of rings)
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn2), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn4), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
+  static const bool dense_on = [] { const char* v = std::getenv("NAM_HIP_WR_DENSE"); return !(v && v[0] == '0'); }();
+  for (int q = 0; q < 2 && dense_on; q++)
+  {
+    hipFunction_t f = nullptr;
+    if (hipModuleGetFunction(&f, e.module, q == 0 ? "nam_wn_reg_jit2d" : "nam_wn_reg_jit4d") != hipSuccess || !f)
+      continue;
+    int scratch = 1, regs = 1 << 20;
+    if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) != hipSuccess
+        || hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, f) != hipSuccess || scratch > 32 || regs > 256)
+      continue; // (spilled more than a handful of registers, or not a two-per-SIMD build after all: the one-wave-per-SIMD form serves)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, kWrMaxLdsBytes);
+    (q == 0 ? e.fn2d : e.fn4d) = f;
+  }
+  (void)hipGetLastError();
+  return NAM_HIP_OK;
+}
+} // namespace
+
+WrJitFunctions wr_jit_functions(const std::string& path, int device)
+{
+  static std::vector<LoadedModule> cache;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  for (const LoadedModule& e : cache)
+    if (e.device == device && e.path == path)
+      return e;
+  LoadedModule e;
+  e.path = path;
+  e.device = device;
+  e.rc = load_module(e, path);
+  if (e.rc != NAM_HIP_OK)
+    return WrJitFunctions{e.rc};
+  cache.push_back(e);
+  return e;
 }
 
 } // namespace namhip
