@@ -1,5 +1,6 @@
 // plan_wr.cpp — nam_wn_reg_kernel's plan: the macro-op program, padded dense / matrix-form weights, the shape sets and the
-// header of the per-model compile, the cuts of the two- / four-wave launches. See plan_internal.h.
+// header of the per-model compile, the cuts of the two- / four-wave launches. See plan_internal.h. Every byte this file decides is
+// pinned on the host: tests/test_plan_pin.py against profiles/plan_wr/parent_table.txt.
 #include "plan_internal.h"
 
 #include <algorithm>
@@ -14,6 +15,29 @@ namespace namhip
 // --------------------------------------------------------------------------------------------
 namespace
 {
+// dense [in_n][row] (row = pad4(outputs)) -> the matrix form [output % 4][output quad][in_stride] (kernel_wn_reg.hip: WrMatM, WrFilm):
+// class i of quad q = output 4 q + i, its weights over the inputs in order. Columns behind in_n stay as they are (zero: never multiplied).
+void to_matrix_form(float* dst, const float* src, int in_n, int row, int in_stride)
+{
+  const int Q = row / 4;
+  for (int cls = 0; cls < 4; cls++)
+    for (int q = 0; q < Q; q++)
+      for (int c = 0; c < in_n; c++)
+        dst[(size_t)(cls * Q + q) * in_stride + c] = src[(size_t)c * row + 4 * q + cls];
+}
+
+// a net's flat weight stream, read front to back (WrBuilder::net checks that it was consumed to the end)
+struct Stream
+{
+  const float *p, *end;
+  float next() { return *(p++); }
+  void take(float* dst, int n)
+  {
+    for (int i = 0; i < n; i++)
+      dst[i] = *(p++);
+  }
+};
+
 struct WrBuilder
 {
   WrPlan& wr;
@@ -90,6 +114,15 @@ struct WrBuilder
     hist += wr_pad4(C * R);
     return off;
   }
+  // an op with history: the next slot (one write position per ring), its ring of (K - 1) * dil + 64 frames of C channels
+  void give_ring(WrOp& op, int C, int K, int dil)
+  {
+    op.slot = (int)ring_of_slot.size();
+    op.hist = ring_area(C, K, dil); // + the ring area's base, added once the weights and tables are complete (wr_lay_tables)
+    op.ring = (K - 1) * dil + kBlock;
+    op.dil = dil;
+    wr.n_layers++;
+  }
   int table(const std::vector<Entry>& t)
   {
     const int off = reserve((int)t.size() * 4);
@@ -120,14 +153,14 @@ struct WrBuilder
   }
   // dense, transposed [K * cin][pad4(cout)] at `dst` (row = tap * cin + in), from the reference's stream order
   // (groups, out, in, tap); `out0` / `out_n`: only outputs [out0, out0 + out_n) of the stream's `cout` land here, as
-  // columns 0.. (a FiLM's scale and shift halves are two matrices)
-  void dense(float* dst, const float*& w, int cin, int cout, int K, int groups, int out0 = 0, int out_n = -1, bool advance = true)
+  // columns 0.. (a FiLM's scale and shift halves are two matrices: the first is read without advancing)
+  void dense(float* dst, Stream& s, int cin, int cout, int K, int groups, int out0 = 0, int out_n = -1, bool advance = true)
   {
     if (out_n < 0)
       out_n = cout;
     const int row = wr_pad4(out_n);
     const int opg = cout / groups, ipg = cin / groups;
-    const float* p = w;
+    const float* p = s.p;
     for (int g = 0; g < groups; g++)
       for (int i = 0; i < opg; i++)
         for (int j = 0; j < ipg; j++)
@@ -138,19 +171,28 @@ struct WrBuilder
               dst[(size_t)(k * cin + g * ipg + j) * row + o] = *p;
           }
     if (advance)
-      w = p;
+      s.p = p;
   }
-  void act_block(float* dst, const ActSpec& a, int rows_n)
+  // the next matrix of the stream, one per tap, in the matrix form: `k_taps` x [4][pad4(out_n) / 4][pad4(in_n)]
+  void matrix(float* dst, Stream& s, int in_n, int out_n, int k_taps, int groups)
+  {
+    const int o4 = wr_pad4(out_n), i4 = wr_pad4(in_n);
+    std::vector<float> t((size_t)k_taps * in_n * o4, 0.0f);
+    dense(t.data(), s, in_n, out_n, k_taps, groups); // [tap * in_n + input][o4]
+    for (int k = 0; k < k_taps; k++)
+      to_matrix_form(dst + (size_t)k * o4 * i4, &t[(size_t)k * in_n * o4], in_n, o4, i4);
+  }
+  void act_block(float* dst, const ActSpec& a)
   {
     for (int i = 0; i < 4; i++)
       dst[i] = a.p[i];
     if (a.type == ACT_PRELU && !a.slopes.empty())
       for (int c = 0; c < 16; c++)
         dst[4 + c] = a.slopes[(size_t)c % a.slopes.size()];
-    (void)rows_n;
   }
 
-  void net(const WaveNetSpec& wn, bool nested)
+  // ---- what a net, an array, a layer must be: `why` is the FIRST of these a model meets (the order is pinned with the texts) ----
+  void refuse_net(const WaveNetSpec& wn, bool nested)
   {
     if (wn.with_head && (policy != JIT || !dyn || nested))
       throw Unsupported("a post-stack head (no ahead-of-time shapes: it needs the per-model compile)");
@@ -158,280 +200,270 @@ struct WrBuilder
       throw Unsupported("more than 8 input / output channels");
     if ((long)wn.weights.size() != wn.expected_weight_count())
       throw std::runtime_error("plan: WaveNet weight count mismatch");
-    int cond_dim = wn.in_channels;
-    if (wn.condition_dsp)
+  }
+  void refuse_array(const WaveNetSpec& wn, size_t ai, int cond_dim)
+  {
+    const LayerArraySpec& A = wn.arrays[ai];
+    if (A.condition_size != cond_dim)
+      throw std::runtime_error("plan: condition_size does not match the condition signal");
+    if (!A.layer1x1_active && policy != JIT)
+      throw Unsupported("a layer without its 1x1"); // (compiled per model: the ahead-of-time shapes all have one)
+    if (A.head_kernel_size != 1 && policy != JIT)
+      throw Unsupported("a head rechannel with a kernel"); // (compiled per model only)
+    if (ai > 0 && wn.arrays[ai - 1].head_size != A.head_output_size())
+      throw std::runtime_error("plan: head sizes of consecutive arrays do not chain");
+  }
+  struct Layer // one layer of an array as the planner sees it
+  {
+    const LayerArraySpec& A;
+    const ActSpec &a1, &a2;
+    int cond, C, B, K, dil, h1o, gm;
+    bool G;
+    int zc, flags; // conv outputs (2 B when gating); WrOp::flags
+  };
+  Layer describe(const LayerArraySpec& A, int l, int cond_dim)
+  {
+    const int gm = A.gating_modes[l];
+    const bool G = gm != GATING_NONE;
+    int flags = gm == GATING_BLENDED ? (1 << 16) : 0;
+    for (int k = 0; k < FILM_COUNT; k++)
+      if (A.film[k].active && !(k == FILM_HEAD1X1_POST && !A.head1x1_active))
+        flags |= (1 << k) | (A.film[k].shift ? 1 << (8 + k) : 0);
+    return Layer{A, A.activations[l], A.secondary_activations[l], cond_dim, A.channels, A.bottleneck, A.kernel_sizes[l], A.dilations[l],
+                 A.head1x1_active ? A.head1x1_out : 0, gm, G, G ? 2 * A.bottleneck : A.bottleneck, flags};
+  }
+  void refuse_layer(const Layer& y)
+  {
+    if (y.a1.type == ACT_LUT || (y.G && y.a2.type == ACT_LUT))
+      throw Unsupported("a look-up-table activation");
+    // Activation::apply on the flat buffer indexes PReLU slopes by frame * rows + row (activations.h:283-297):
+    // only frame-independent when the slope count divides the row count
+    if (!y.G && y.a1.type == ACT_PRELU && !y.a1.slopes.empty() && y.zc % (int)y.a1.slopes.size() != 0)
+      throw Unsupported("a PReLU whose slope count does not divide the channel count");
+    if (y.zc > 16 || y.C > kWrRegs || y.A.head_output_size() > kWrRegs || y.cond > kWrRegs)
+      throw Unsupported("a layer wider than the register files");
+    // the layer keeps its whole conv matrix in registers while the taps arrive ([K * C][pad4(zc)] floats per lane)
+    // (its taps stay in registers for the whole layer: K * C floats per lane)
+    if (y.K * y.C > 64)
+      throw Unsupported("a conv of more than 64 tap inputs (kernel size " + std::to_string(y.K) + " x " + std::to_string(y.C) + " channels)");
+  }
+
+  // ---- weight blocks ----
+  // a PLAIN layer's block (plan.h: wr_plain_layout). Conv and layer1x1 in the matrix form: row `o` of the block = output o's weights
+  // over the inputs in order (zero rows for o >= C, zero columns behind the last input: never multiplied)
+  int pack_plain(const Layer& y, Stream& s)
+  {
+    const WrPlainLayout P = wr_plain_layout(y.C);
+    const int off = reserve(P.total);
+    float* d = &wr.blob[(size_t)off];
+    float t[12 * 4] = {0};
+    dense(t, s, y.C, y.C, 3, y.A.groups_input); // [tap * C + channel][4 outputs]
+    to_matrix_form(d + P.conv, t, 3 * y.C, 4, wr_pad4(3 * y.C));
+    s.take(d + P.conv_b, y.C);
+    dense(d + P.mixin, s, 1, y.C, 1, y.A.groups_input_mixin);
+    std::fill(t, t + 16, 0.0f);
+    dense(t, s, y.C, y.C, 1, y.A.layer1x1_groups);
+    to_matrix_form(d + P.l1, t, y.C, 4, 4);
+    s.take(d + P.l1_b, y.C);
+    return off;
+  }
+  // a layer's active FiLMs: Conv1x1(cond -> outc, groups) + bias each; outputs [0, D) scale, [D, 2D) shift: two matrices, two
+  // bias vectors. Returns the floats that lie in the matrix form (half the instructions per weight: wr_op_costs)
+  int pack_films(const Layer& y, const WrLayerLayout& L, float* d, Stream& s)
+  {
+    const int dims[FILM_COUNT] = {y.C, y.zc, y.cond, y.zc, y.zc, y.B, y.C, y.h1o};
+    int matrix_floats = 0;
+    std::vector<float> t;
+    for (int k = 0; k < FILM_COUNT; k++)
     {
-      if (nested)
-        throw Unsupported("a condition_dsp inside a condition_dsp");
-      if (wn.condition_dsp->arch != ARCH_WAVENET)
-        throw Unsupported("a condition_dsp that is not a WaveNet");
-      const WaveNetSpec& c = wn.condition_dsp->wavenet;
-      if (c.in_channels != wn.in_channels)
-        throw Unsupported("a condition_dsp with another input width");
-      net(c, true);
-      cond_dim = c.out_channels();
-      WrOp& op = push(WR_SET_COND);
-      op.n_out = cond_dim;
-      op.scale = c.weights.back(); // model.cpp:670 — the last weight is the head scale
+      if (!((y.flags >> k) & 1))
+        continue;
+      const FilmSpec& F = y.A.film[k];
+      const int D = dims[k], n_mat = F.shift ? 2 : 1, outc = n_mat * D, D4 = wr_pad4(D);
+      dense(d + L.film[k], s, y.cond, outc, 1, F.groups, 0, D, !F.shift);
+      if (F.shift)
+        dense(d + L.film[k] + y.cond * D4, s, y.cond, outc, 1, F.groups, D, D);
+      if (wr_film_matrix_form(y.cond))
+      {
+        matrix_floats += n_mat * y.cond * D4;
+        for (int m = 0; m < n_mat; m++) // [cond][pad4(D)] -> [lane class][output quad][cond]
+        {
+          float* mat = d + L.film[k] + m * y.cond * D4;
+          t.assign(mat, mat + y.cond * D4);
+          to_matrix_form(mat, t.data(), y.cond, D4, y.cond);
+        }
+      }
+      float* bias = d + L.film[k] + 2 * y.cond * D4;
+      s.take(bias, D);
+      if (F.shift)
+        s.take(bias + D4, D);
     }
-    const float* w = wn.weights.data();
+    return matrix_floats;
+  }
+  // a full layer's block (plan.h: wr_layer_layout); the flat stream order is conv, mixin, layer1x1, head1x1, then the 8 FiLMs
+  // (model.cpp:152-181)
+  int pack_full(const Layer& y, Stream& s, int& film_matrix_floats)
+  {
+    const WrLayerLayout L = wr_layer_layout(y.cond, y.C, y.B, y.G, y.K, y.h1o);
+    const int off = reserve(L.total);
+    float* d = &wr.blob[(size_t)off];
+    matrix(d + L.conv, s, y.C, y.zc, y.K, y.A.groups_input);
+    s.take(d + L.conv_b, y.zc);
+    dense(d + L.mixin, s, y.cond, y.zc, 1, y.A.groups_input_mixin);
+    if (y.A.layer1x1_active)
+    {
+      matrix(d + L.l1, s, y.B, y.C, 1, y.A.layer1x1_groups);
+      s.take(d + L.l1_b, y.C);
+    }
+    if (y.A.head1x1_active)
+    {
+      matrix(d + L.h1, s, y.B, y.h1o, 1, y.A.head1x1_groups);
+      s.take(d + L.h1_b, y.h1o);
+    }
+    film_matrix_floats = pack_films(y, L, d, s);
+    act_block(d + L.act, y.a1);
+    if (y.G)
+      act_block(d + L.act2, y.a2);
+    return off;
+  }
+
+  // ---- ops ----
+  void array_begin(const LayerArraySpec& A, bool first, Stream& s)
+  {
+    WrOp& op = push(WR_ARRAY_BEGIN);
+    op.flags = first ? 1 : 0;
+    op.n_in = A.input_size;
+    op.n_out = A.channels;
+    op.shape = shape_pair(A.input_size, A.channels);
+    if (op.shape < 0)
+      throw Unsupported("a rechannel of " + std::to_string(A.input_size) + " -> " + std::to_string(A.channels));
+    const int off = reserve(A.input_size * wr_pad4(A.channels));
+    wr.ops.back().w = off;
+    dense(&wr.blob[(size_t)off], s, A.input_size, A.channels, 1, 1);
+  }
+  void layer(const LayerArraySpec& A, int l, int cond_dim, Stream& s)
+  {
+    const Layer y = describe(A, l, cond_dim);
+    refuse_layer(y);
+    // a PLAIN layer (no gating, FiLM or head1x1; condition size 1, kernel size 3, at most four channels, a
+    // parameterless activation) joins a WR_RUN and takes the compact weight block
+    const bool plain = y.cond == 1 && y.B == y.C && y.C <= 4 && !y.G && y.K == 3 && y.h1o == 0 && y.flags == 0 && A.layer1x1_active
+                       && (y.a1.type == ACT_RELU || y.a1.type == ACT_TANH || y.a1.type == ACT_FASTTANH);
+    const int run_shape = plain ? shape_run(y.C, y.a1.type) : -1;
+    const int shape = run_shape >= 0 ? -1
+                                     : shape_layer(y.cond, y.C, y.B, y.G, y.K, y.h1o, y.flags, y.a1.type,
+                                                   y.G ? y.a2.type : (int)ACT_IDENTITY, A.layer1x1_active);
+    if (shape < 0 && run_shape < 0)
+      throw Unsupported("layer shape cond=" + std::to_string(y.cond) + " C=" + std::to_string(y.C) + " B=" + std::to_string(y.B)
+                        + (y.G ? " gating" : "") + " K=" + std::to_string(y.K) + " head1x1=" + std::to_string(y.h1o));
+    int film_matrix_floats = 0;
+    const int off = run_shape >= 0 ? pack_plain(y, s) : pack_full(y, s, film_matrix_floats);
+    WrOp& op = push(WR_LAYER);
+    op.shape = shape;
+    op.w = off;
+    op.pad[0] = y.zc + (y.G ? y.B : 0); // (planner only, like pad[1]: wr_program_cuts — activation evaluations per frame)
+    op.pad[1] = film_matrix_floats;
+    op.run = run_shape + 1;
+    give_ring(op, y.C, y.K, y.dil);
+    op.flags = y.flags;
+    op.act = y.a1.type;
+    op.act2 = y.G ? y.a2.type : ACT_IDENTITY;
+  }
+  // the head rechannel: [K_h * HO][pad4(head size)] (row = tap * HO + input) + bias. With taps (K_h > 1) it is a Conv1D over the
+  // head accumulator, which then has a ring of its own
+  void array_end(const LayerArraySpec& A, Stream& s)
+  {
+    const int HO = A.head_output_size(), KH = A.head_kernel_size, hs4 = wr_pad4(A.head_size);
+    const bool taps = KH != 1;
+    if (taps && (KH * HO > 64 || KH * HO * hs4 > 320))
+      throw Unsupported("a head rechannel of more than 64 tap inputs / 320 weights");
+    const int shape = taps ? dyn->head(HO, A.head_size, KH) : shape_pair(HO, A.head_size);
+    if (shape < 0)
+      throw Unsupported("a head rechannel of " + std::to_string(HO) + " -> " + std::to_string(A.head_size));
+    const int off = reserve(KH * HO * hs4 + hs4);
+    dense(&wr.blob[(size_t)off], s, HO, A.head_size, KH, 1);
+    if (A.head_bias)
+      s.take(&wr.blob[(size_t)off + (size_t)KH * HO * hs4], A.head_size);
+    WrOp& op = push(taps ? WR_ARRAY_END_K : WR_ARRAY_END);
+    op.flags = A.head_bias ? 1 : 0;
+    op.n_in = HO;
+    op.n_out = A.head_size;
+    op.shape = shape;
+    op.w = off;
+    if (taps)
+      give_ring(op, HO, KH, A.head_dilation);
+  }
+  // the post-stack head (model.cpp:21-103, applied :854-866): activation + Conv1D per entry of kernel_sizes, on the
+  // last array's head output times head_scale (which follows the head's weights in the stream). Returns its first op
+  size_t post_head(const WaveNetSpec& wn, Stream& s)
+  {
+    const PostHeadSpec& H = wn.head;
+    if (H.in_channels != wn.arrays.back().head_size || H.kernel_sizes.empty())
+      throw Unsupported("a post-stack head whose input is not the last array's head output");
+    const size_t first = wr.ops.size();
+    int cin = H.in_channels;
+    for (size_t i = 0; i < H.kernel_sizes.size(); i++)
+    {
+      const int cout = (i + 1 == H.kernel_sizes.size()) ? H.out_channels : H.channels;
+      const int K = H.kernel_sizes[i], mat = K * cin * wr_pad4(cout);
+      if (cin > kWrRegs || cout > kWrRegs || K * cin > 64 || mat > 320)
+        throw Unsupported("a post-stack head layer of more than 8 channels / 64 tap inputs / 320 weights");
+      if (H.activation.type == ACT_LUT)
+        throw Unsupported("a lookup-table activation in the post-stack head");
+      const int off = reserve(mat + wr_pad4(cout) + kWrActFloats);
+      dense(&wr.blob[(size_t)off], s, cin, cout, K, 1);
+      s.take(&wr.blob[(size_t)off + mat], cout); // Conv1D bias (always: set_size_(cin, cout, k, true, 1, 1))
+      act_block(&wr.blob[(size_t)off + mat + wr_pad4(cout)], H.activation);
+      WrOp& op = push(WR_POST_HEAD);
+      op.n_in = cin;
+      op.n_out = cout;
+      op.shape = dyn->post(cin, cout, K, H.activation.type);
+      op.w = off;
+      op.act = H.activation.type;
+      op.scale = 1.0f;
+      op.dil = 1;
+      if (K > 1)
+        give_ring(op, cin, K, 1);
+      cin = cout;
+    }
+    return first;
+  }
+  // the nested condition_dsp first (its head output becomes the condition); returns the condition's size
+  int condition(const WaveNetSpec& wn, bool nested)
+  {
+    if (!wn.condition_dsp)
+      return wn.in_channels;
+    if (nested)
+      throw Unsupported("a condition_dsp inside a condition_dsp");
+    if (wn.condition_dsp->arch != ARCH_WAVENET)
+      throw Unsupported("a condition_dsp that is not a WaveNet");
+    const WaveNetSpec& c = wn.condition_dsp->wavenet;
+    if (c.in_channels != wn.in_channels)
+      throw Unsupported("a condition_dsp with another input width");
+    net(c, true);
+    WrOp& op = push(WR_SET_COND);
+    op.n_out = c.out_channels();
+    op.scale = c.weights.back(); // model.cpp:670 — the last weight is the head scale
+    return op.n_out;
+  }
+
+  void net(const WaveNetSpec& wn, bool nested)
+  {
+    refuse_net(wn, nested);
+    const int cond_dim = condition(wn, nested);
+    Stream s{wn.weights.data(), wn.weights.data() + wn.weights.size()};
     for (size_t ai = 0; ai < wn.arrays.size(); ai++)
     {
       const LayerArraySpec& A = wn.arrays[ai];
-      const int C = A.channels, B = A.bottleneck, HO = A.head_output_size();
-      if (A.condition_size != cond_dim)
-        throw std::runtime_error("plan: condition_size does not match the condition signal");
-      if (!A.layer1x1_active && policy != JIT)
-        throw Unsupported("a layer without its 1x1"); // (compiled per model: the ahead-of-time shapes all have one)
-      if (A.head_kernel_size != 1 && policy != JIT)
-        throw Unsupported("a head rechannel with a kernel"); // (compiled per model only)
-      if (ai > 0 && wn.arrays[ai - 1].head_size != HO)
-        throw std::runtime_error("plan: head sizes of consecutive arrays do not chain");
-      {
-        WrOp& op = push(WR_ARRAY_BEGIN);
-        op.flags = ai == 0 ? 1 : 0;
-        op.n_in = A.input_size;
-        op.n_out = C;
-        op.shape = shape_pair(A.input_size, C);
-        if (op.shape < 0)
-          throw Unsupported("a rechannel of " + std::to_string(A.input_size) + " -> " + std::to_string(C));
-        const int off = reserve(A.input_size * wr_pad4(C));
-        wr.ops.back().w = off;
-        dense(&wr.blob[(size_t)off], w, A.input_size, C, 1, 1);
-      }
+      refuse_array(wn, ai, cond_dim);
+      array_begin(A, ai == 0, s);
       for (int l = 0; l < A.num_layers(); l++)
-      {
-        const int gm = A.gating_modes[l];
-        const bool G = gm != GATING_NONE;
-        const int zc = G ? 2 * B : B, K = A.kernel_sizes[l], dil = A.dilations[l];
-        const int h1o = A.head1x1_active ? A.head1x1_out : 0;
-        const ActSpec& a1 = A.activations[l];
-        const ActSpec& a2 = A.secondary_activations[l];
-        if (a1.type == ACT_LUT || (G && a2.type == ACT_LUT))
-          throw Unsupported("a look-up-table activation");
-        // Activation::apply on the flat buffer indexes PReLU slopes by frame * rows + row (activations.h:283-297):
-        // only frame-independent when the slope count divides the row count
-        if (!G && a1.type == ACT_PRELU && !a1.slopes.empty() && zc % (int)a1.slopes.size() != 0)
-          throw Unsupported("a PReLU whose slope count does not divide the channel count");
-        if (zc > 16 || C > kWrRegs || HO > kWrRegs || cond_dim > kWrRegs)
-          throw Unsupported("a layer wider than the register files");
-        // the layer keeps its whole conv matrix in registers while the taps arrive ([K * C][pad4(zc)] floats per lane)
-        // (its taps stay in registers for the whole layer: K * C floats per lane)
-        if (K * C > 64)
-          throw Unsupported("a conv of more than 64 tap inputs (kernel size " + std::to_string(K) + " x " + std::to_string(C) + " channels)");
-        int flags = gm == GATING_BLENDED ? (1 << 16) : 0;
-        for (int k = 0; k < FILM_COUNT; k++)
-          if (A.film[k].active && !(k == FILM_HEAD1X1_POST && !A.head1x1_active))
-            flags |= (1 << k) | (A.film[k].shift ? 1 << (8 + k) : 0);
-        // a PLAIN layer (no gating, FiLM or head1x1; condition size 1, kernel size 3, at most four channels, a
-        // parameterless activation) joins a WR_RUN and takes the compact weight block
-        const bool plain = cond_dim == 1 && B == C && C <= 4 && !G && K == 3 && h1o == 0 && flags == 0 && A.layer1x1_active
-                           && (a1.type == ACT_RELU || a1.type == ACT_TANH || a1.type == ACT_FASTTANH);
-        const int run_shape = plain ? shape_run(C, a1.type) : -1;
-        const int shape = run_shape >= 0 ? -1
-                                         : shape_layer(cond_dim, C, B, G, K, h1o, flags, a1.type, G ? a2.type : (int)ACT_IDENTITY,
-                                                       A.layer1x1_active);
-        if (shape < 0 && run_shape < 0)
-          throw Unsupported("layer shape cond=" + std::to_string(cond_dim) + " C=" + std::to_string(C) + " B=" + std::to_string(B)
-                            + (G ? " gating" : "") + " K=" + std::to_string(K) + " head1x1=" + std::to_string(h1o));
-        int off = 0;
-        int film_matrix_floats = 0; // this layer's FiLM weights that lie in the matrix form (half the instructions per weight)
-        if (run_shape >= 0)
-        {
-          const WrPlainLayout P = wr_plain_layout(C);
-          off = reserve(P.total);
-          float* d = &wr.blob[(size_t)off];
-          // conv and layer1x1 in the matrix form: row `o` of the block = output o's weights over the inputs in order (zero rows
-          // for o >= C, zero columns behind the last input: never multiplied)
-          float t[12 * 4] = {0};
-          dense(t, w, C, C, 3, A.groups_input); // [tap * C + channel][4 outputs]
-          const int in4 = wr_pad4(3 * C);
-          for (int o = 0; o < 4; o++)
-            for (int j = 0; j < 3 * C; j++)
-              d[P.conv + o * in4 + j] = t[j * 4 + o];
-          for (int i = 0; i < C; i++)
-            d[P.conv_b + i] = *(w++);
-          dense(d + P.mixin, w, 1, C, 1, A.groups_input_mixin);
-          std::fill(t, t + 16, 0.0f);
-          dense(t, w, C, C, 1, A.layer1x1_groups);
-          for (int o = 0; o < 4; o++)
-            for (int j = 0; j < C; j++)
-              d[P.l1 + o * 4 + j] = t[j * 4 + o];
-          for (int i = 0; i < C; i++)
-            d[P.l1_b + i] = *(w++);
-        }
-        else
-        {
-          const WrLayerLayout L = wr_layer_layout(cond_dim, C, B, G, K, h1o);
-          off = reserve(L.total);
-          float* d = &wr.blob[(size_t)off];
-          // the flat stream order is conv, mixin, layer1x1, head1x1, then the 8 FiLMs (model.cpp:152-181)
-          // [in][pad4(out)] (dense) -> the matrix form [output row % 4][quad][pad4(in)] (kernel_wn_reg.hip: WrMatM)
-          std::vector<float> tm;
-          auto matrix_form = [&](float* dst, int in_n, int out_n, int k_taps, int groups) {
-            const int o4 = wr_pad4(out_n), i4 = wr_pad4(in_n), Q = o4 / 4;
-            tm.assign((size_t)k_taps * in_n * o4, 0.0f);
-            dense(tm.data(), w, in_n, out_n, k_taps, groups); // [tap * in_n + input][o4]
-            for (int k = 0; k < k_taps; k++)
-              for (int cls = 0; cls < 4; cls++)
-                for (int q = 0; q < Q; q++)
-                  for (int c = 0; c < in_n; c++)
-                    dst[(size_t)k * o4 * i4 + (size_t)(cls * Q + q) * i4 + c] = tm[(size_t)(k * in_n + c) * o4 + 4 * q + cls];
-          };
-          matrix_form(d + L.conv, C, zc, K, A.groups_input);
-          for (int i = 0; i < zc; i++)
-            d[L.conv_b + i] = *(w++);
-          dense(d + L.mixin, w, cond_dim, zc, 1, A.groups_input_mixin);
-          if (A.layer1x1_active)
-          {
-            matrix_form(d + L.l1, B, C, 1, A.layer1x1_groups);
-            for (int i = 0; i < C; i++)
-              d[L.l1_b + i] = *(w++);
-          }
-          if (A.head1x1_active)
-          {
-            matrix_form(d + L.h1, B, h1o, 1, A.head1x1_groups);
-            for (int i = 0; i < h1o; i++)
-              d[L.h1_b + i] = *(w++);
-          }
-          const int dims[FILM_COUNT] = {C, zc, cond_dim, zc, zc, B, C, h1o};
-          for (int k = 0; k < FILM_COUNT; k++)
-          {
-            bool on = A.film[k].active;
-            if (k == FILM_HEAD1X1_POST && !A.head1x1_active)
-              on = false;
-            if (!on)
-              continue;
-            const int D = dims[k], outc = (A.film[k].shift ? 2 : 1) * D, D4 = wr_pad4(D);
-            // Conv1x1(cond -> outc, groups) + bias; outputs [0, D) scale, [D, 2D) shift: two matrices, two bias vectors
-            dense(d + L.film[k], w, cond_dim, outc, 1, A.film[k].groups, 0, D, !A.film[k].shift);
-            if (A.film[k].shift)
-              dense(d + L.film[k] + cond_dim * D4, w, cond_dim, outc, 1, A.film[k].groups, D, D);
-            if (wr_film_matrix_form(cond_dim))
-            {
-              film_matrix_floats += (A.film[k].shift ? 2 : 1) * cond_dim * D4;
-              // [cond][pad4(D)] -> [lane class][output quad][cond]: class i of quad q = row 4 q + i, its weights for inputs 0 .. cond - 1
-              const int Q = D4 / 4;
-              std::vector<float> t((size_t)cond_dim * D4);
-              for (int m = 0; m < (A.film[k].shift ? 2 : 1); m++)
-              {
-                float* mat = d + L.film[k] + m * cond_dim * D4;
-                std::copy(mat, mat + cond_dim * D4, t.begin());
-                for (int cls = 0; cls < 4; cls++)
-                  for (int q = 0; q < Q; q++)
-                    for (int c = 0; c < cond_dim; c++)
-                      mat[(cls * Q + q) * cond_dim + c] = t[(size_t)c * D4 + 4 * q + cls];
-              }
-            }
-            float* bias = d + L.film[k] + 2 * cond_dim * D4;
-            for (int i = 0; i < D; i++)
-              bias[i] = *(w++);
-            if (A.film[k].shift)
-              for (int i = 0; i < D; i++)
-                bias[D4 + i] = *(w++);
-          }
-          act_block(d + L.act, a1, zc);
-          if (G)
-            act_block(d + L.act2, a2, B);
-        }
-        WrOp& op = push(WR_LAYER);
-        op.shape = shape;
-        op.w = off;
-        op.pad[0] = zc + (G ? B : 0); // (planner only, like pad[1]: wr_program_cuts — activation evaluations per frame)
-        op.pad[1] = film_matrix_floats;
-        op.slot = (int)ring_of_slot.size();
-        op.run = run_shape + 1;
-        op.hist = ring_area(C, K, dil); // + the ring area's base, added once the weights and tables are complete
-        op.ring = (K - 1) * dil + kBlock;
-        op.dil = dil;
-        op.flags = flags;
-        op.act = a1.type;
-        op.act2 = G ? a2.type : ACT_IDENTITY;
-        wr.n_layers++;
-      }
-      if (A.head_kernel_size == 1)
-      {
-        WrOp& op = push(WR_ARRAY_END);
-        op.flags = A.head_bias ? 1 : 0;
-        op.n_in = HO;
-        op.n_out = A.head_size;
-        op.shape = shape_pair(HO, A.head_size);
-        if (op.shape < 0)
-          throw Unsupported("a head rechannel of " + std::to_string(HO) + " -> " + std::to_string(A.head_size));
-        const int off = reserve(HO * wr_pad4(A.head_size) + wr_pad4(A.head_size));
-        wr.ops.back().w = off;
-        dense(&wr.blob[(size_t)off], w, HO, A.head_size, 1, 1);
-        if (A.head_bias)
-          for (int i = 0; i < A.head_size; i++)
-            wr.blob[(size_t)off + (size_t)HO * wr_pad4(A.head_size) + i] = *(w++);
-      }
-      else
-      {
-        // a Conv1D over the head accumulator: [K_h * HO][pad4(head size)] (row = tap * HO + input) + bias, its own ring
-        const int KH = A.head_kernel_size;
-        if (KH * HO > 64 || KH * HO * wr_pad4(A.head_size) > 320)
-          throw Unsupported("a head rechannel of more than 64 tap inputs / 320 weights");
-        const int off = reserve(KH * HO * wr_pad4(A.head_size) + wr_pad4(A.head_size));
-        dense(&wr.blob[(size_t)off], w, HO, A.head_size, KH, 1);
-        if (A.head_bias)
-          for (int i = 0; i < A.head_size; i++)
-            wr.blob[(size_t)off + (size_t)KH * HO * wr_pad4(A.head_size) + i] = *(w++);
-        WrOp& op = push(WR_ARRAY_END_K);
-        op.flags = A.head_bias ? 1 : 0;
-        op.n_in = HO;
-        op.n_out = A.head_size;
-        op.shape = dyn->head(HO, A.head_size, KH);
-        op.w = off;
-        op.slot = (int)ring_of_slot.size();
-        op.hist = ring_area(HO, KH, A.head_dilation); // + the ring area's base, below
-        op.ring = (KH - 1) * A.head_dilation + kBlock;
-        op.dil = A.head_dilation;
-        wr.n_layers++; // (a slot: one write position per ring)
-      }
+        layer(A, l, cond_dim, s);
+      array_end(A, s);
     }
-    // the post-stack head (model.cpp:21-103, applied :854-866): activation + Conv1D per entry of kernel_sizes, on the
-    // last array's head output times head_scale; head_scale itself follows the head's weights in the stream
-    size_t first_post = 0;
-    if (wn.with_head)
-    {
-      const PostHeadSpec& H = wn.head;
-      if (H.in_channels != wn.arrays.back().head_size || H.kernel_sizes.empty())
-        throw Unsupported("a post-stack head whose input is not the last array's head output");
-      first_post = wr.ops.size();
-      int cin = H.in_channels;
-      for (size_t i = 0; i < H.kernel_sizes.size(); i++)
-      {
-        const int cout = (i + 1 == H.kernel_sizes.size()) ? H.out_channels : H.channels;
-        const int K = H.kernel_sizes[i];
-        if (cin > kWrRegs || cout > kWrRegs || K * cin > 64 || K * cin * wr_pad4(cout) > 320)
-          throw Unsupported("a post-stack head layer of more than 8 channels / 64 tap inputs / 320 weights");
-        if (H.activation.type == ACT_LUT)
-          throw Unsupported("a lookup-table activation in the post-stack head");
-        const int off = reserve(K * cin * wr_pad4(cout) + wr_pad4(cout) + kWrActFloats);
-        dense(&wr.blob[(size_t)off], w, cin, cout, K, 1);
-        for (int o = 0; o < cout; o++) // Conv1D bias (always: set_size_(cin, cout, k, true, 1, 1))
-          wr.blob[(size_t)off + (size_t)K * cin * wr_pad4(cout) + o] = *(w++);
-        act_block(&wr.blob[(size_t)off + (size_t)K * cin * wr_pad4(cout) + wr_pad4(cout)], H.activation, cin);
-        WrOp& op = push(WR_POST_HEAD);
-        op.n_in = cin;
-        op.n_out = cout;
-        op.shape = dyn->post(cin, cout, K, H.activation.type);
-        op.w = off;
-        op.act = H.activation.type;
-        op.scale = 1.0f;
-        op.dil = 1;
-        if (K > 1)
-        {
-          op.slot = (int)ring_of_slot.size();
-          op.hist = ring_area(cin, K, 1); // + the ring area's base, below
-          op.ring = (K - 1) + kBlock;
-          wr.n_layers++;
-        }
-        cin = cout;
-      }
-    }
-    const float head_scale = *(w++);
-    if (w != wn.weights.data() + wn.weights.size())
+    const size_t first_post = wn.with_head ? post_head(wn, s) : 0;
+    const float head_scale = s.next();
+    if (s.p != s.end)
       throw std::runtime_error("plan: internal error, weight stream not fully consumed (register-resident plan)");
     if (wn.with_head)
       wr.ops[first_post].scale = head_scale;
@@ -622,15 +654,15 @@ std::string WrShapeSet::header_text(bool mask_scales) const
   return ss.str();
 }
 
-// Two- / four-stage launches (kernel_wn_reg.hip, NST) cut the program where the work balances; an op's weights are a fair
-// measure of its arithmetic (every weight is one multiply-add per frame): op i owns the blob from its offset to the next
-// larger one (`weights_end`: the first table behind the weights). split[q], q = 0 .. 2 = the cut closest to (q + 1) / 4 of the work
-// (four wavefronts per stream); split[3] = the TWO-wave cut, which also counts an activation evaluation as sixteen weights (ten
-// vector instructions, two of them at a quarter of the rate: a gated 12-row layer of a condition_dsp is a third activations) —
-// calibrated on config 4, same-box: the second of two waves from op 5 / 6 / 7 / 8 on reads 4.49 / 4.23 / 4.58 / 5.84 us per step
-// (the term picks 6); with the same term the four-wave cuts become {2, 6, 11} and 256 streams read 3.68 us instead of 3.14 for
-// {2, 7, 12}: four short parts are dominated by their matrix work, two long ones are not.
-static void wr_program_cuts(const std::vector<WrOp>& ops, int weights_end, int split[4])
+// ---- the cost model of the cuts: here and nowhere else ----
+// An op's weights are a fair measure of its arithmetic (every weight is one multiply-add per frame): op i owns the blob from its
+// offset to the next larger one (`weights_end`: the first table behind the weights), and costs that many floats + 8.
+// `film_discount`: a FiLM matrix in the matrix form (kernel_wn_reg.hip: WrFilm) costs one matrix instruction per four weights and
+// one LDS read per sixteen, against one packed FMA per two and one read per four: 0.45 of its weights. The two callers DIFFER on
+// purpose: wr_program_cuts counts the discount, wr_cut_runs does not (it never did; giving it one moves sub-run boundaries, which
+// is a change of behaviour to be measured, not tidied). What holds the difference: the table lines of pin_run_and_film.nam
+// (tests/test_plan_pin.py), the one model whose sub-runs move with it.
+static std::vector<long> wr_op_costs(const std::vector<WrOp>& ops, int weights_end, bool film_discount)
 {
   auto weighs = [](const WrOp& op) {
     return op.type == WR_LAYER || op.type == WR_RUN || op.type == WR_ARRAY_BEGIN || op.type == WR_ARRAY_END || op.type == WR_ARRAY_END_K
@@ -643,150 +675,275 @@ static void wr_program_cuts(const std::vector<WrOp>& ops, int weights_end, int s
   ws.push_back(weights_end);
   std::sort(ws.begin(), ws.end());
   std::vector<long> cost(ops.size(), 8);
-  long total = 0;
   for (size_t i = 0; i < ops.size(); i++)
+    if (weighs(ops[i]))
+    {
+      const auto nx = std::upper_bound(ws.begin(), ws.end(), ops[i].w);
+      cost[i] += nx != ws.end() ? *nx - ops[i].w : 0;
+      if (film_discount && ops[i].type == WR_LAYER)
+        cost[i] -= (long)ops[i].pad[1] * 55 / 100;
+    }
+  return cost;
+}
+static long wr_total(const std::vector<long>& cost)
+{
+  long total = 0;
+  for (long c : cost)
+    total += c;
+  return total;
+}
+// the boundary (m = in front of element m, 1 <= m < n) closest to num / den of `total`; 0 when there is none
+static size_t wr_closest_boundary(const std::vector<long>& cost, long total, long num, long den)
+{
+  long acc = 0, best = -1;
+  size_t at = 0;
+  for (size_t m = 1; m < cost.size(); m++)
   {
-    const auto& op = ops[i];
-    if (weighs(op))
+    acc += cost[m - 1];
+    const long d = std::labs(den * acc - num * total);
+    if (best < 0 || d < best)
     {
-      const auto nx = std::upper_bound(ws.begin(), ws.end(), op.w);
-      cost[i] += nx != ws.end() ? *nx - op.w : 0;
-      // a FiLM matrix in the matrix form (kernel_wn_reg.hip: WrFilm) costs one matrix instruction per four weights and one LDS
-      // read per sixteen, against one packed FMA per two and one read per four: 0.45 of its weights
-      if (op.type == WR_LAYER)
-        cost[i] -= (long)op.pad[1] * 55 / 100;
+      best = d;
+      at = m;
     }
-    total += cost[i];
   }
-  auto cut_at = [&](const std::vector<long>& c, long tot, int num, int den) { // the cut closest to num / den of the work
-    long acc = 0, best = -1;
-    int at = 0;
-    for (size_t m = 1; m < ops.size(); m++)
-    {
-      acc += c[m - 1];
-      const long d = std::labs(den * acc - num * tot);
-      if (best < 0 || d < best)
-      {
-        best = d;
-        at = (int)m;
-      }
-    }
-    return at;
-  };
+  return at;
+}
+
+// Two- / four-stage launches (kernel_wn_reg.hip, NST) cut the program where the work balances (wr_op_costs). split[q], q = 0 .. 2 =
+// the cut closest to (q + 1) / 4 of the work (four wavefronts per stream); split[3] = the TWO-wave cut, which also counts an
+// activation evaluation as sixteen weights (ten vector instructions, two of them at a quarter of the rate: a gated 12-row layer of
+// a condition_dsp is a third activations) — calibrated on config 4, same-box: the second of two waves from op 5 / 6 / 7 / 8 on reads
+// 4.49 / 4.23 / 4.58 / 5.84 us per step (the term picks 6); with the same term the four-wave cuts become {2, 6, 11} and 256 streams
+// read 3.68 us instead of 3.14 for {2, 7, 12}: four short parts are dominated by their matrix work, two long ones are not.
+static void wr_program_cuts(const std::vector<WrOp>& ops, int weights_end, int split[4])
+{
+  std::vector<long> cost = wr_op_costs(ops, weights_end, true);
   for (int q = 0; q < 3; q++)
-    split[q] = cut_at(cost, total, q + 1, 4);
-  std::vector<long> cost2 = cost;
-  long total2 = total;
+    split[q] = (int)wr_closest_boundary(cost, wr_total(cost), q + 1, 4);
   for (size_t i = 0; i < ops.size(); i++)
     if (ops[i].type == WR_LAYER)
+      cost[i] += 16l * ops[i].pad[0];
+  split[3] = (int)wr_closest_boundary(cost, wr_total(cost), 1, 2);
+}
+
+// A WR_RUN is ONE op to the walked program (one dispatch for ten layers) and so could not be cut across the wavefronts of a two- /
+// four-stage launch: `ops` with every run cut at the quartile points of the program's work that fall inside it (sub-runs: their
+// layers' weights and ring records are consecutive; a sub-run costs one more exposed weight fetch, which is why the one-wavefront
+// form keeps the whole run). Costs WITHOUT the FiLM discount (wr_op_costs), a run's spread evenly over its layers.
+static std::vector<WrOp> wr_cut_runs(const std::vector<WrOp>& ops, int weights_end)
+{
+  const std::vector<long> cost = wr_op_costs(ops, weights_end, false);
+  // atoms: every op, a run layer by layer
+  std::vector<size_t> atom_op;
+  std::vector<int> atom_layer; // -1: not a run
+  std::vector<long> atom_cost;
+  for (size_t i = 0; i < ops.size(); i++)
+  {
+    const bool run = ops[i].type == WR_RUN && ops[i].n_in >= 2;
+    for (int l = 0; l < (run ? ops[i].n_in : 1); l++)
     {
-      cost2[i] += 16l * ops[i].pad[0];
-      total2 += 16l * ops[i].pad[0];
+      atom_op.push_back(i);
+      atom_layer.push_back(run ? l : -1);
+      atom_cost.push_back(run ? cost[i] / ops[i].n_in : cost[i]);
     }
-  split[3] = cut_at(cost2, total2, 1, 2);
+  }
+  const long total = wr_total(cost); // (of the ops, not of the atoms: a run's cost / layers rounds down)
+  std::vector<std::vector<int>> starts(ops.size()); // per run: the layers a sub-run starts at
+  for (int q = 1; q <= 3; q++)
+  {
+    const size_t at = wr_closest_boundary(atom_cost, total, q, 4);
+    if (at > 0 && atom_layer[at] > 0) // the boundary lies inside a run: in front of this layer
+      starts[atom_op[at]].push_back(atom_layer[at]);
+  }
+  std::vector<WrOp> cut;
+  for (size_t i = 0; i < ops.size(); i++)
+  {
+    const WrOp& o = ops[i];
+    if (starts[i].empty())
+    {
+      cut.push_back(o);
+      continue;
+    }
+    std::vector<int> at = starts[i];
+    at.push_back(0);
+    at.push_back(o.n_in);
+    std::sort(at.begin(), at.end());
+    at.erase(std::unique(at.begin(), at.end()), at.end());
+    for (size_t k = 0; k + 1 < at.size(); k++)
+    {
+      WrOp sub = o;
+      sub.w = o.w + at[k] * o.n_out; // (n_out: the layers' weight stride)
+      sub.n_in = at[k + 1] - at[k];
+      sub.pad[0] = o.pad[0] + at[k];
+      cut.push_back(sub);
+    }
+  }
+  return cut;
+}
+
+// The program of a finished plan as the per-model code object holds it, twice: as it is (one wavefront per stream), and with its
+// runs cut and the cuts taken again. `first_rec`: where the plan's run records go in the shape set's
+static WrShapeSet::Program wr_program_of(const WrPlan& wr, int first_rec)
+{
+  WrShapeSet::Program pr;
+  pr.ops = wr.ops;
+  pr.ops_cut = wr_cut_runs(wr.ops, wr.tab_rows);
+  wr_program_cuts(pr.ops_cut, wr.tab_rows, pr.split_op);
+  if (const char* e = std::getenv("NAM_HIP_WR_CUT2")) // (developer switch: the two-wave cut at this op, for A/B runs of the cost model)
+    pr.split_op[3] = std::min(std::max(std::atoi(e), 1), (int)pr.ops_cut.size() - 1);
+  pr.first_rec = first_rec;
+  return pr;
+}
+
+// ---- one attempt under one shape policy (build_wr_with), in its four steps ----
+struct WrFusedRun
+{
+  size_t op; // index of the WR_RUN op
+  int table; // blob float offset of its records
+  std::vector<WrOp> layers;
+};
+// consecutive plain layers of one shape (weight blocks at the layout's stride) become one WR_RUN
+static std::vector<WrFusedRun> wr_fuse_runs(WrBuilder& b)
+{
+  WrPlan& wr = b.wr;
+  std::vector<WrFusedRun> runs;
+  std::vector<WrOp> fused;
+  for (size_t i = 0; i < wr.ops.size();)
+  {
+    const WrOp& o = wr.ops[i];
+    if (o.type != WR_LAYER || o.run <= 0)
+    {
+      fused.push_back(o);
+      i++;
+      continue;
+    }
+    size_t j = i + 1;
+    while (j < wr.ops.size() && wr.ops[j].type == WR_LAYER && wr.ops[j].run == o.run
+           && wr.ops[j].w - wr.ops[j - 1].w == wr.ops[i + 1].w - o.w)
+      j++;
+    WrOp r;
+    std::memset(&r, 0, sizeof(r));
+    r.type = WR_RUN;
+    r.shape = o.run - 1;
+    r.w = o.w;
+    r.n_in = (int)(j - i);
+    r.n_out = j - i > 1 ? wr.ops[i + 1].w - o.w : 0; // weight stride (floats)
+    r.act = o.act;
+    runs.push_back({fused.size(), b.reserve((int)(j - i) * 4), std::vector<WrOp>(wr.ops.begin() + (long)i, wr.ops.begin() + (long)j)});
+    fused.push_back(r);
+    i = j;
+  }
+  wr.ops = std::move(fused);
+  for (const auto& o : wr.ops)
+  {
+    wr.has_layers = wr.has_layers || o.type == WR_LAYER;
+    wr.has_runs = wr.has_runs || o.type == WR_RUN;
+    wr.has_rt_layers = wr.has_rt_layers || (o.type == WR_LAYER && b.policy != WrBuilder::JIT && !wr_layer_shape_is_exact(o.shape));
+  }
+  return runs;
+}
+// the four tables behind the weights; LDS is weights, tables, program | rings: every ring offset gets the rings' base, returned
+static int wr_lay_tables(WrBuilder& b)
+{
+  static_assert(sizeof(WrBuilder::Entry) == 16, "table entries are int4");
+  WrPlan& wr = b.wr;
+  wr.tab_rows = b.table(b.rows);
+  wr.n_rows = (int)b.rows.size();
+  wr.tab_pf = b.table(b.pf);
+  wr.n_pf = (int)b.pf.size();
+  wr.tab_ring = b.reserve((int)b.ring_of_slot.size());
+  if (!b.ring_of_slot.empty())
+    std::memcpy(&wr.blob[(size_t)wr.tab_ring], b.ring_of_slot.data(), b.ring_of_slot.size() * sizeof(int32_t));
+  wr.tab_ops = b.reserve((int)wr.ops.size() * 16); // the macro-ops themselves: fetched from LDS, one op ahead
+  const int hist_base = (int)wr.blob.size();
+  for (auto& op : wr.ops)
+    if (op.type == WR_LAYER || op.type == WR_ARRAY_END_K || (op.type == WR_POST_HEAD && op.ring > 0))
+      op.hist += hist_base;
+  return hist_base;
+}
+static void wr_write_run_records(WrPlan& wr, const std::vector<WrFusedRun>& runs, int hist_base)
+{
+  for (const auto& run : runs)
+  {
+    wr.ops[run.op].hist = run.table;
+    wr.ops[run.op].pad[0] = (int32_t)wr.run_recs.size(); // (the program compiled in: first record of this run)
+    for (size_t l = 0; l < run.layers.size(); l++)
+    {
+      const WrOp& o = run.layers[l];
+      const int32_t rec[4] = {o.w, o.hist + hist_base, o.ring, o.dil | (o.slot << 24)};
+      std::memcpy(&wr.blob[(size_t)run.table + 4 * l], rec, sizeof(rec));
+      wr.run_recs.push_back({rec[0], rec[1], rec[2], rec[3]});
+    }
+  }
+}
+// WrPlan::structure_key: the walked program without its scales, the int tables behind the weights (rows | pf | ring), the
+// WR_RUN records, the cuts
+static unsigned long long wr_structure_key(const WrPlan& wr)
+{
+  unsigned long long h = wr_hash_seed;
+  for (WrOp o : wr.ops)
+  {
+    o.scale = 0.0f;
+    h = wr_hash(&o, sizeof(o), h);
+  }
+  h = wr_hash(&wr.blob[(size_t)wr.tab_rows], (size_t)(wr.tab_ops - wr.tab_rows) * sizeof(float), h);
+  if (!wr.run_recs.empty())
+    h = wr_hash(wr.run_recs.data(), wr.run_recs.size() * sizeof(wr.run_recs[0]), h);
+  return wr_hash(wr.split_op, sizeof(wr.split_op), h);
 }
 
 // One attempt under one shape policy; throws WrBuilder::Unsupported
 static void build_wr_with(const WaveNetSpec& wn, WrPlan& wr, WrBuilder::Policy policy, WrShapeSet* dyn)
 {
+  WrBuilder b(wr, policy, dyn);
+  b.net(wn, false);
+  const std::vector<WrFusedRun> runs = wr_fuse_runs(b);
+  const int hist_base = wr_lay_tables(b);
+  wr_write_run_records(wr, runs, hist_base);
+  std::memcpy(&wr.blob[(size_t)wr.tab_ops], wr.ops.data(), wr.ops.size() * sizeof(WrOp));
+  wr_program_cuts(wr.ops, wr.tab_rows, wr.split_op);
+  wr.structure_key = wr_structure_key(wr);
+  wr.hist_floats = b.hist;
+  wr.state_floats = (kWrPosInts + b.hist + 63) / 64 * 64;
+  wr.lds_bytes = (hist_base + wr.hist_floats) * 4;
+  if (wr.lds_bytes > kWrMaxLdsBytes)
+    throw WrBuilder::Unsupported("more than 156 KB of weights and rings");
+  wr.ok = true;
+}
+
+// `why`: the first refusal, or the per-model policy's
+static bool wr_attempt(const WaveNetSpec& wn, WrBuilder::Policy policy, WrShapeSet* dyn, WrPlan& wr, std::string& why)
+{
+  try
   {
-    WrBuilder b(wr, policy, dyn);
-    b.net(wn, false);
-    static_assert(sizeof(WrBuilder::Entry) == 16, "table entries are int4");
-    // consecutive plain layers of one shape (weight blocks at the layout's stride) become one WR_RUN
-    struct Run
-    {
-      size_t op; // index of the WR_RUN op
-      int table; // blob float offset of its records
-      std::vector<WrOp> layers;
-    };
-    std::vector<Run> runs;
-    {
-      std::vector<WrOp> fused;
-      for (size_t i = 0; i < wr.ops.size();)
-      {
-        const WrOp& o = wr.ops[i];
-        if (o.type != WR_LAYER || o.run <= 0)
-        {
-          fused.push_back(o);
-          i++;
-          continue;
-        }
-        size_t j = i + 1;
-        while (j < wr.ops.size() && wr.ops[j].type == WR_LAYER && wr.ops[j].run == o.run
-               && wr.ops[j].w - wr.ops[j - 1].w == wr.ops[i + 1].w - o.w)
-          j++;
-        WrOp r;
-        std::memset(&r, 0, sizeof(r));
-        r.type = WR_RUN;
-        r.shape = o.run - 1;
-        r.w = o.w;
-        r.n_in = (int)(j - i);
-        r.n_out = j - i > 1 ? wr.ops[i + 1].w - o.w : 0; // weight stride (floats)
-        r.act = o.act;
-        Run run;
-        run.op = fused.size();
-        run.table = b.reserve((int)(j - i) * 4);
-        run.layers.assign(wr.ops.begin() + (long)i, wr.ops.begin() + (long)j);
-        runs.push_back(std::move(run));
-        fused.push_back(r);
-        i = j;
-      }
-      wr.ops = std::move(fused);
-      for (const auto& o : wr.ops)
-      {
-        wr.has_layers = wr.has_layers || o.type == WR_LAYER;
-        wr.has_runs = wr.has_runs || o.type == WR_RUN;
-        wr.has_rt_layers = wr.has_rt_layers || (o.type == WR_LAYER && policy != WrBuilder::JIT && !wr_layer_shape_is_exact(o.shape));
-      }
-    }
-    wr.tab_rows = b.table(b.rows);
-    wr.n_rows = (int)b.rows.size();
-    wr.tab_pf = b.table(b.pf);
-    wr.n_pf = (int)b.pf.size();
-    wr.tab_ring = b.reserve((int)b.ring_of_slot.size());
-    if (!b.ring_of_slot.empty())
-      std::memcpy(&wr.blob[(size_t)wr.tab_ring], b.ring_of_slot.data(), b.ring_of_slot.size() * sizeof(int32_t));
-    wr.tab_ops = b.reserve((int)wr.ops.size() * 16); // the macro-ops themselves: fetched from LDS, one op ahead
-    const int hist_base = (int)wr.blob.size(); // LDS: weights, tables, program | rings
-    for (auto& op : wr.ops)
-      if (op.type == WR_LAYER || op.type == WR_ARRAY_END_K || (op.type == WR_POST_HEAD && op.ring > 0))
-        op.hist += hist_base;
-    for (const auto& run : runs)
-    {
-      wr.ops[run.op].hist = run.table;
-      wr.ops[run.op].pad[0] = (int32_t)wr.run_recs.size(); // (the program compiled in: first record of this run)
-      for (size_t l = 0; l < run.layers.size(); l++)
-      {
-        const WrOp& o = run.layers[l];
-        const int32_t rec[4] = {o.w, o.hist + hist_base, o.ring, o.dil | (o.slot << 24)};
-        std::memcpy(&wr.blob[(size_t)run.table + 4 * l], rec, sizeof(rec));
-        wr.run_recs.push_back({rec[0], rec[1], rec[2], rec[3]});
-      }
-    }
-    std::memcpy(&wr.blob[(size_t)wr.tab_ops], wr.ops.data(), wr.ops.size() * sizeof(WrOp));
-    wr_program_cuts(wr.ops, wr.tab_rows, wr.split_op);
-    {
-      // WrPlan::structure_key: the walked program without its scales, the int tables behind the weights (rows | pf | ring), the
-      // WR_RUN records, the cuts
-      unsigned long long h = wr_hash_seed;
-      for (WrOp o : wr.ops)
-      {
-        o.scale = 0.0f;
-        h = wr_hash(&o, sizeof(o), h);
-      }
-      h = wr_hash(&wr.blob[(size_t)wr.tab_rows], (size_t)(wr.tab_ops - wr.tab_rows) * sizeof(float), h);
-      if (!wr.run_recs.empty())
-        h = wr_hash(wr.run_recs.data(), wr.run_recs.size() * sizeof(wr.run_recs[0]), h);
-      wr.structure_key = wr_hash(wr.split_op, sizeof(wr.split_op), h);
-    }
-    wr.hist_floats = b.hist;
-    wr.state_floats = (kWrPosInts + b.hist + 63) / 64 * 64;
-    wr.lds_bytes = (hist_base + wr.hist_floats) * 4;
-    if (wr.lds_bytes > kWrMaxLdsBytes)
-      throw WrBuilder::Unsupported("more than 156 KB of weights and rings");
-    wr.ok = true;
+    WrPlan w;
+    build_wr_with(wn, w, policy, dyn);
+    wr = std::move(w);
+    return true;
   }
+  catch (const WrBuilder::Unsupported& e)
+  {
+    if (why.empty() || policy == WrBuilder::JIT)
+      why = e.what();
+    return false;
+  }
+}
+// the per-model build: the plan's shapes, program and run records join the caller's set only if the plan succeeds
+static bool wr_attempt_jit(const WaveNetSpec& wn, WrShapeSet* jit_shapes, WrPlan& wr, std::string& why)
+{
+  if (!jit_shapes)
+    return false;
+  WrShapeSet trial = *jit_shapes;
+  if (!wr_attempt(wn, WrBuilder::JIT, &trial, wr, why))
+    return false;
+  WrShapeSet::Program pr = wr_program_of(wr, (int)trial.run_recs.size());
+  trial.run_recs.insert(trial.run_recs.end(), wr.run_recs.begin(), wr.run_recs.end());
+  wr.program = (int)trial.programs.size();
+  trial.programs.push_back(std::move(pr));
+  *jit_shapes = std::move(trial);
+  wr.jit = true;
+  return true;
 }
 
 // nam_wn_reg_kernel's plan: with the fully described ahead-of-time shapes if the model consists of them (the shipped
@@ -794,143 +951,14 @@ static void build_wr_with(const WaveNetSpec& wn, WrPlan& wr, WrBuilder::Policy p
 // then compiled for them: wr_jit.cpp); else with the run-time-flag instantiations; else not at all (`why` says why).
 void build_wr(const WaveNetSpec& wn, Plan& plan, WrShapeSet* jit_shapes)
 {
-  WrPlan wr;
-  std::string why;
-  bool done = false;
-  auto attempt = [&](WrBuilder::Policy policy, WrShapeSet* dyn) {
-    if (done)
-      return;
-    try
-    {
-      WrPlan w;
-      build_wr_with(wn, w, policy, dyn);
-      wr = std::move(w);
-      done = true;
-    }
-    catch (const WrBuilder::Unsupported& e)
-    {
-      if (why.empty() || policy == WrBuilder::JIT)
-        why = e.what();
-    }
-  };
   // Round 6: with a shape set on offer the per-model build comes FIRST — it compiles the plan's program in (every op a
   // constant expression: WrShapeSet::programs), which beats the ahead-of-time kernels walking the same program as data even
   // where they hold every shape (configs 4 and 5 of the bench: profiles/r06). NAM_HIP_WR_PROGRAM=0: round 5's order.
   static const bool program_first = [] { const char* e = std::getenv("NAM_HIP_WR_PROGRAM"); return !(e && e[0] == '0'); }();
-  auto attempt_jit = [&]() {
-    if (done || !jit_shapes)
-      return;
-    WrShapeSet trial = *jit_shapes; // (only a plan that succeeds leaves its shapes in the caller's set)
-    attempt(WrBuilder::JIT, &trial);
-    if (done)
-    {
-      WrShapeSet::Program pr;
-      // the program as the code object holds it, twice: as it is (one wavefront per stream), and — a WR_RUN is ONE op to the
-      // walked program (one dispatch for ten layers) and so could not be cut across the wavefronts of a two- / four-stage
-      // launch — with every run cut at the quartile points of the program's work that fall inside it (sub-runs: their layers'
-      // weights and ring records are consecutive; a sub-run costs one more exposed weight fetch, which is why the one-wavefront
-      // form keeps the whole run) and the cuts taken again
-      pr.ops = wr.ops;
-      {
-        // cost of every op as wr_program_cuts counts it (weights + 8), a run's layer by layer; the quartile points of the total
-        std::vector<WrOp> probe = wr.ops;
-        long total = 0;
-        std::vector<long> cost(wr.ops.size(), 8);
-        {
-          std::vector<int> ws;
-          auto weighs = [](const WrOp& op) {
-            return op.type == WR_LAYER || op.type == WR_RUN || op.type == WR_ARRAY_BEGIN || op.type == WR_ARRAY_END || op.type == WR_ARRAY_END_K
-                   || op.type == WR_POST_HEAD;
-          };
-          for (const auto& op : wr.ops)
-            if (weighs(op))
-              ws.push_back(op.w);
-          ws.push_back(wr.tab_rows);
-          std::sort(ws.begin(), ws.end());
-          for (size_t i = 0; i < wr.ops.size(); i++)
-          {
-            if (weighs(wr.ops[i]))
-            {
-              const auto nx = std::upper_bound(ws.begin(), ws.end(), wr.ops[i].w);
-              cost[i] += nx != ws.end() ? *nx - wr.ops[i].w : 0;
-            }
-            total += cost[i];
-          }
-        }
-        // atoms: every op, a run layer by layer; the atom boundary closest to each quartile point of the total
-        struct Atom
-        {
-          size_t op;
-          int layer; // -1: not a run
-          long cost;
-        };
-        std::vector<Atom> atoms;
-        for (size_t i = 0; i < wr.ops.size(); i++)
-        {
-          const WrOp& o = wr.ops[i];
-          if (o.type == WR_RUN && o.n_in >= 2)
-            for (int l = 0; l < o.n_in; l++)
-              atoms.push_back({i, l, cost[i] / o.n_in});
-          else
-            atoms.push_back({i, -1, cost[i]});
-        }
-        std::vector<std::vector<int>> cuts(wr.ops.size()); // per run: the layers a sub-run starts at
-        for (int q = 1; q <= 3; q++)
-        {
-          long acc = 0, best = -1;
-          size_t best_at = 0;
-          for (size_t k = 1; k < atoms.size(); k++)
-          {
-            acc += atoms[k - 1].cost;
-            const long d = std::labs(4 * acc - (long)q * total);
-            if (best < 0 || d < best)
-            {
-              best = d;
-              best_at = k;
-            }
-          }
-          if (best_at > 0 && atoms[best_at].layer > 0) // the boundary lies inside a run: in front of this layer
-            cuts[atoms[best_at].op].push_back(atoms[best_at].layer);
-        }
-        for (size_t i = 0; i < wr.ops.size(); i++)
-        {
-          const WrOp& o = wr.ops[i];
-          if (o.type != WR_RUN || o.n_in < 2 || cuts[i].empty())
-          {
-            pr.ops_cut.push_back(o);
-            continue;
-          }
-          std::vector<int> at = cuts[i];
-          at.push_back(0);
-          at.push_back(o.n_in);
-          std::sort(at.begin(), at.end());
-          at.erase(std::unique(at.begin(), at.end()), at.end());
-          for (size_t k = 0; k + 1 < at.size(); k++)
-          {
-            WrOp sub = o;
-            sub.w = o.w + at[k] * o.n_out; // (n_out: the layers' weight stride)
-            sub.n_in = at[k + 1] - at[k];
-            sub.pad[0] = o.pad[0] + at[k];
-            pr.ops_cut.push_back(sub);
-          }
-        }
-      }
-      wr_program_cuts(pr.ops_cut, wr.tab_rows, pr.split_op);
-      if (const char* e = std::getenv("NAM_HIP_WR_CUT2")) // (developer switch: the two-wave cut at this op, for A/B runs of the cost model)
-        pr.split_op[3] = std::min(std::max(std::atoi(e), 1), (int)pr.ops_cut.size() - 1);
-      pr.first_rec = (int)trial.run_recs.size();
-      trial.run_recs.insert(trial.run_recs.end(), wr.run_recs.begin(), wr.run_recs.end());
-      wr.program = (int)trial.programs.size();
-      trial.programs.push_back(std::move(pr));
-      *jit_shapes = std::move(trial);
-      wr.jit = true;
-    }
-  };
-  if (program_first)
-    attempt_jit();
-  attempt(WrBuilder::AOT_EXACT_ONLY, nullptr);
-  attempt_jit();
-  attempt(WrBuilder::AOT_ANY, nullptr);
+  WrPlan wr;
+  std::string why;
+  const bool done = (program_first && wr_attempt_jit(wn, jit_shapes, wr, why)) || wr_attempt(wn, WrBuilder::AOT_EXACT_ONLY, nullptr, wr, why)
+                    || wr_attempt_jit(wn, jit_shapes, wr, why) || wr_attempt(wn, WrBuilder::AOT_ANY, nullptr, wr, why);
   if (!done)
   {
     wr = WrPlan{};
