@@ -342,6 +342,33 @@ public:
     }
   }
   int GetStreamModel(int stream) const { return mBank ? mMembers.at((size_t)stream) : 0; }
+  // Stream slots (not in the reference; include/nam_hip.h). RestartStreams: the listed streams (nullptr: all) start over as a new
+  // player's — bit for bit the state of a newly built BatchDSP after Reset with `prewarm`; an LSTM stream gets its h0 / c0 back,
+  // which Reset leaves alone. Every other stream is untouched (nam_hip_batch_restart_streams).
+  void RestartStreams(const int* stream_ids, int n, bool prewarm)
+  {
+    detail::check(nam_hip_batch_restart_streams(mBatch.get(), stream_ids, n, prewarm ? 1 : 0));
+  }
+  // One stream's state as an opaque, self-describing blob: a rewind, a checkpoint, or — Get here, Set on another BatchDSP of the
+  // same model or bank — a move (nam_hip_batch_get_stream_state / nam_hip_batch_set_stream_state)
+  std::vector<unsigned char> GetStreamState(int stream)
+  {
+    const int64_t n = nam_hip_batch_stream_state_size(mBatch.get(), stream);
+    detail::check((int)(n < 0 ? n : 0));
+    std::vector<unsigned char> blob((size_t)n);
+    int64_t size = 0;
+    detail::check(nam_hip_batch_get_stream_state(mBatch.get(), stream, blob.data(), n, &size));
+    blob.resize((size_t)size);
+    return blob;
+  }
+  // The stream takes the blob's width and bank member and continues exactly as the source stream would have; a blob that does
+  // not fit throws (std::runtime_error naming the field) and changes nothing.
+  void SetStreamState(int stream, const std::vector<unsigned char>& blob)
+  {
+    detail::check(nam_hip_batch_set_stream_state(mBatch.get(), stream, blob.data(), (int64_t)blob.size()));
+    if (mBank) // (kept for the next SetMaxBufferSize, which builds a new batch)
+      mMembers.at((size_t)stream) = nam_hip_batch_get_stream_model(mBatch.get(), stream);
+  }
   void process_batch(const float* in, float* out, const int num_frames)
   {
     detail::check(nam_hip_batch_process_f32(mBatch.get(), in, out, num_frames));

@@ -290,6 +290,45 @@ NAM_HIP_API int nam_hip_batch_get_stream_model(const nam_hip_batch* batch, int s
  * (NAM/lstm.cpp has no SetMaxBufferSize override); this call mirrors that: LSTM batches only prewarm. */
 NAM_HIP_API int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm);
 
+/* ---- stream slots: restart one stream of a live batch, save and restore it ----
+ * A batch is N slots that players come to and leave. These four calls are blocking, take host memory and belong to the
+ * non-real-time side, like Reset. Like nam_hip_batch_set_slimmable_size each one first quiesces the batch: a running session's
+ * launch ends and hands the state back, tickets in flight complete and stay available to wait, a remembered caller stream is
+ * waited for. None of them changes the state or the output of a stream it does not name.
+ *
+ * nam_hip_batch_restart_streams: the listed streams (stream_ids == NULL: all; duplicates are allowed) take, bit for bit, the
+ * state a NEWLY CREATED batch of the same model or bank and max_frames (any stream count) holds after
+ * nam_hip_batch_reset(batch, prewarm). A WaveNet stream: zeroed history, then the prewarm (or the cached prewarmed image). An
+ * LSTM stream: its h0 / c0 from the weight stream (a bank: its member's) FIRST, then the prewarm — unlike nam_hip_batch_reset,
+ * which mirrors the reference and leaves h / c alone, so that a recycled slot does not start from the previous player's
+ * recurrent state. A Linear stream: its own columns of the batch's history ring become zero (the ring position and every other
+ * stream's columns stay). A slimmable stream keeps its width, a bank stream its member. An id out of range is
+ * NAM_HIP_ERR_INVALID_ARGUMENT and changes nothing. */
+NAM_HIP_API int nam_hip_batch_restart_streams(nam_hip_batch* batch, const int* stream_ids, int n_ids, int prewarm);
+/* One stream's state as an opaque, self-describing blob: get on one batch, set on the same or on another one (another stream
+ * count, another GPU, another process with the same library version): a rewind, a checkpoint, a move. From the next call on the
+ * destination stream produces exactly the bits the source stream would have produced (under the same kernel: kernels of
+ * different launch classes differ by ~1e-7 by design).
+ * The blob records a magic and format version, the architecture, a 64-bit fingerprint of the model (config text and weights),
+ * for a bank the member index and that member's fingerprint, for a slimmable model the width, for a WaveNet the layout its
+ * state is in (the op program's rings / the zero-padded A1 rings / nam_wn_reg_kernel's histories / freshly zeroed), the payload
+ * length and what it depends on, and a checksum of the payload. Payload: the stream's state row (WaveNet: write positions and
+ * rings; LSTM: h / c per layer), or for a Linear stream its columns of the history ring, oldest frame first — independent of
+ * the source batch's ring position.
+ * nam_hip_batch_stream_state_size: the bytes get writes for `stream` now (it depends on the stream's width), or an error code.
+ * nam_hip_batch_get_stream_state: writes the blob to buf and its size to *out_size (out_size may be NULL). A capacity that is
+ * too small is NAM_HIP_ERR_INVALID_ARGUMENT with the needed size in *out_size; nothing is written to buf.
+ * nam_hip_batch_set_stream_state: validates everything before it touches the batch, then moves the stream to the blob's width
+ * (as nam_hip_batch_set_slimmable_size moves it, without the reset), binds it to the blob's member (nam_hip_batch_get_stream_model
+ * reports it from then on) and writes the state (a Linear stream's rows rotated to the destination's ring position). Refused with
+ * NAM_HIP_ERR_INVALID_ARGUMENT, a message that names the field, and nothing changed: a blob of another model or whose member is
+ * another model than the bank's; another payload geometry (a Linear batch of another max_frames class); a truncated or
+ * corrupted blob; a blob whose WaveNet layout differs from what the destination's streams of that width hold ("reset first":
+ * a freshly zeroed blob fits anywhere, and freshly zeroed streams take the blob's layout). */
+NAM_HIP_API int64_t nam_hip_batch_stream_state_size(const nam_hip_batch* batch, int stream);
+NAM_HIP_API int nam_hip_batch_get_stream_state(nam_hip_batch* batch, int stream, void* buf, int64_t capacity, int64_t* out_size);
+NAM_HIP_API int nam_hip_batch_set_stream_state(nam_hip_batch* batch, int stream, const void* buf, int64_t size);
+
 /* SlimmableModel::SetSlimmableSize(val) for a subset of the streams (NAM/slimmable.h:23,
  * NAM/wavenet/slimmable.cpp:420-431,527-530): the listed streams switch to the sub-model of width
  * ratio_to_channels(ratio) and start from a freshly reset (and, if the batch was last reset with

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "nam_hip_batch_kernel_name_for", "nam_hip_version_support", "nam_hip_device_count",
     "nam_hip_bank_create", "nam_hip_bank_free", "nam_hip_bank_n_models", "nam_hip_batch_create_bank",
     "nam_hip_batch_set_stream_model", "nam_hip_batch_get_stream_model",
+    "nam_hip_batch_restart_streams", "nam_hip_batch_stream_state_size", "nam_hip_batch_get_stream_state", "nam_hip_batch_set_stream_state",
 ]
 
 
@@ -168,6 +169,11 @@ def load_library():
     L.nam_hip_batch_create_bank.argtypes = [vp, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     L.nam_hip_batch_set_stream_model.argtypes = [vp, ctypes.POINTER(ci), ci, ci]
     L.nam_hip_batch_get_stream_model.argtypes = [vp, ci]
+    L.nam_hip_batch_restart_streams.argtypes = [vp, ctypes.POINTER(ci), ci, ci]
+    L.nam_hip_batch_stream_state_size.argtypes = [vp, ci]
+    L.nam_hip_batch_stream_state_size.restype = ctypes.c_int64
+    L.nam_hip_batch_get_stream_state.argtypes = [vp, ci, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.nam_hip_batch_set_stream_state.argtypes = [vp, ci, ctypes.c_char_p, ctypes.c_int64]
     _lib = L
     return L
 
@@ -380,6 +386,32 @@ class Batch:
     def stream_model(self, stream: int) -> int:
         """The bank member ``stream`` runs (0 for a one-model batch)."""
         return _check(self._L.nam_hip_batch_get_stream_model(self._h, int(stream)))
+
+    def restart_streams(self, stream_ids: Optional[Sequence[int]] = None, prewarm: bool = True):
+        """The listed stream slots (None: all) start over as a new player's: bit for bit the state of a newly created batch after
+        ``Reset(prewarm)`` — an LSTM stream gets its h0 / c0 back first, which ``Reset`` leaves alone. Every other stream, a
+        slimmable stream's width and a bank stream's member are untouched (nam_hip_batch_restart_streams)."""
+        if stream_ids is None:
+            _check(self._L.nam_hip_batch_restart_streams(self._h, None, 0, 1 if prewarm else 0))
+        else:
+            arr = (ctypes.c_int * max(len(stream_ids), 1))(*[int(s) for s in stream_ids])
+            _check(self._L.nam_hip_batch_restart_streams(self._h, arr, len(stream_ids), 1 if prewarm else 0))
+
+    def get_stream_state(self, stream: int) -> bytes:
+        """One stream's state as an opaque, self-describing blob (nam_hip_batch_get_stream_state) for ``set_stream_state`` on this
+        or another batch of the same model: a rewind, a checkpoint, a move."""
+        n = _check(self._L.nam_hip_batch_stream_state_size(self._h, int(stream)))
+        buf = ctypes.create_string_buffer(n)
+        size = ctypes.c_int64(0)
+        _check(self._L.nam_hip_batch_get_stream_state(self._h, int(stream), buf, n, ctypes.byref(size)))
+        return buf.raw[:size.value]
+
+    def set_stream_state(self, stream: int, blob: bytes):
+        """Restore a blob of ``get_stream_state`` into ``stream``: it takes the blob's width and bank member and continues exactly
+        as the source stream would have. A blob that does not fit (another model, another geometry, truncated or corrupted,
+        another state layout) raises NamHipError(ERR_INVALID_ARGUMENT) naming the field, and nothing changes."""
+        blob = bytes(blob)
+        _check(self._L.nam_hip_batch_set_stream_state(self._h, int(stream), blob, len(blob)))
 
     def set_kernel(self, kernel: int):
         _check(self._L.nam_hip_batch_set_kernel(self._h, int(kernel)))

@@ -333,21 +333,8 @@ int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, i
 int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, int member)
 {
   std::vector<int> ids;
-  if (!stream_ids)
-  {
-    ids.resize(b->n_streams);
-    for (int i = 0; i < b->n_streams; i++)
-      ids[i] = i;
-  }
-  else
-    for (int i = 0; i < n_ids; i++)
-    {
-      if (stream_ids[i] < 0 || stream_ids[i] >= b->n_streams)
-        return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_model: stream id out of range");
-      ids.push_back(stream_ids[i]);
-    }
-  std::sort(ids.begin(), ids.end());
-  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  if (const int rc = collect_stream_ids(b, stream_ids, n_ids, "nam_hip_batch_set_stream_model", ids))
+    return rc;
   std::vector<int> moved;
   for (int s : ids)
     if (b->stream_member[s] != member)
@@ -417,6 +404,9 @@ int nam_hip_bank_create(const nam_hip_model* const* models, int n_models, nam_hi
     }
     else if (per_member == BANK_MEMBER_SCALARS)
       data->scal.resize((size_t)n_models * 2);
+    for (int i = 0; i < n_models; i++) // (stream state blobs name a member by what it computes: stream_state.h)
+      data->member_fp.push_back(model_fingerprint(*member_spec(*models[i])));
+    data->fingerprint = sstate::fnv1a64(data->member_fp.data(), data->member_fp.size() * sizeof(uint64_t));
     for (int i = 0; i < n_models; i++)
     {
       const Plan& p = member_plan(*models[i]);

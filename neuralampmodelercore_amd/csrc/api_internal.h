@@ -7,6 +7,7 @@
 //   api_bank.cpp      model banks: the families' rules (kBankFamily), which models may share a batch, the bank's device image,
 //                     per-stream member binding
 //   launch_policy.h   nam_wn_reg_kernel's launch shape, workgroups per CU and stream bound: integers in, integers out (no HIP)
+//   stream_state.h    one stream's state as a blob: header, encode, validate, the Linear ring's row arithmetic (no HIP)
 // No exception leaves these files (guarded); errors are codes + nam_hip_last_error.
 #pragma once
 #include "../../include/nam_hip.h"
@@ -30,6 +31,7 @@
 #include "launch_policy.h"
 #include "model_spec.h"
 #include "plan.h"
+#include "stream_state.h"
 #include "wr_jit.h"
 
 using namespace namhip;
@@ -127,6 +129,9 @@ struct nam_hip_bank_data
   std::vector<float> scal; // [n_members][2]: head_scale, act_p0 (A1Args::bank_scal)
   int n_init = 0; // floats of a member's initial state (LSTMPlan::init_state: h0 / c0 from ITS weight stream)
   std::vector<float> init; // [n_members][n_init]
+  // what a stream state blob names its model by (stream_state.h): every member's fingerprint, and the bank's (theirs, in order)
+  std::vector<uint64_t> member_fp; // [n_members]
+  uint64_t fingerprint = 0;
 };
 struct nam_hip_bank
 {
@@ -458,6 +463,20 @@ int reset_streams(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, bool
 // fresh state for the streams `moved` (ascending, not empty) that have just joined `g`: their ids to the device, optionally their
 // members' initial states (an LSTM bank), Reset (+ prewarm as the batch was last reset), and the batch's stream drained
 int reset_moved_streams(nam_hip_batch* b, WidthGroup& g, const std::vector<int>& moved, bool fill_initial_states);
+// a control call's stream list as ascending unique ids (stream_ids == nullptr: every stream); an id out of range fails as `who`
+int collect_stream_ids(const nam_hip_batch* b, const int* stream_ids, int n_ids, const char* who, std::vector<int>& ids);
+// the streams `moved` (ascending) leave their width groups for group `w`: membership, the group's state allocation, every group's
+// device map. Their state in `w` is whatever lies there: the caller resets or writes it. The batch is quiesced.
+int move_streams_to_width(nam_hip_batch* b, const std::vector<int>& moved, int w);
+// Stream slots (include/nam_hip.h: nam_hip_batch_restart_streams, _get / _set_stream_state), behind the entry points' argument
+// checks. Each quiesces the batch first and leaves its stream drained.
+// `ids`: ascending, unique, in range. The state of a newly created batch after nam_hip_batch_reset(prewarm) for these streams.
+int restart_streams(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm);
+int64_t stream_state_bytes(const nam_hip_batch* b, int stream);
+int get_stream_state(nam_hip_batch* b, int stream, void* buf); // (buf: stream_state_bytes(b, stream) bytes)
+int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size);
+// 64 bits that name a model: architecture, config text, fast_tanh and weights (a container: its submodels'; a nested condition_dsp's too)
+uint64_t model_fingerprint(const ModelSpec& s);
 // api_session.cpp
 StateFamily persist_family(const nam_hip_batch* b, const WidthGroup& g);
 int persist_kind(const nam_hip_batch* b);

@@ -1,5 +1,5 @@
 // api_launch.cpp — model handles -> plans -> device blobs; which kernel a launch of a width group runs and its arguments;
-// Reset / prewarm (NAM/dsp.cpp:67-140). See api_internal.h.
+// Reset / prewarm (NAM/dsp.cpp:67-140); stream slots (restart one stream, its state out of and into a batch). See api_internal.h.
 #include "api_internal.h"
 
 namespace namhip
@@ -727,6 +727,232 @@ int reset_moved_streams(nam_hip_batch* b, WidthGroup& g, const std::vector<int>&
   if (rc != NAM_HIP_OK)
     return rc;
   NAM_HIP_CHECK(e);
+  return NAM_HIP_OK;
+}
+
+int collect_stream_ids(const nam_hip_batch* b, const int* stream_ids, int n_ids, const char* who, std::vector<int>& ids)
+{
+  ids.clear();
+  if (!stream_ids)
+  {
+    ids.resize((size_t)b->n_streams);
+    for (int i = 0; i < b->n_streams; i++)
+      ids[(size_t)i] = i;
+    return NAM_HIP_OK;
+  }
+  for (int i = 0; i < n_ids; i++)
+  {
+    if (stream_ids[i] < 0 || stream_ids[i] >= b->n_streams)
+      return fail(NAM_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": stream id out of range");
+    ids.push_back(stream_ids[i]);
+  }
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  return NAM_HIP_OK;
+}
+
+int move_streams_to_width(nam_hip_batch* b, const std::vector<int>& moved, int w)
+{
+  for (int s : moved)
+  {
+    auto& old = b->groups[(size_t)b->stream_width[(size_t)s]].streams;
+    old.erase(std::remove(old.begin(), old.end(), s), old.end());
+    b->stream_width[(size_t)s] = w;
+    b->groups[(size_t)w].streams.push_back(s);
+  }
+  std::sort(b->groups[(size_t)w].streams.begin(), b->groups[(size_t)w].streams.end());
+  int rc = ensure_state(b, b->groups[(size_t)w]);
+  for (size_t i = 0; rc == NAM_HIP_OK && i < b->groups.size(); i++)
+    rc = refresh_map(b, b->groups[i]);
+  return rc;
+}
+
+// ---- stream slots (include/nam_hip.h: nam_hip_batch_restart_streams, _get / _set_stream_state) ----
+
+uint64_t model_fingerprint(const ModelSpec& s)
+{
+  uint64_t h = sstate::fnv1a64(s.architecture_name.data(), s.architecture_name.size());
+  h = sstate::fnv1a64(s.config_text.data(), s.config_text.size(), h);
+  const int32_t flags[2] = {s.arch, s.fast_tanh ? 1 : 0};
+  h = sstate::fnv1a64(flags, sizeof(flags), h);
+  if (const std::vector<float>* w = s.weights())
+    h = sstate::fnv1a64(w->data(), w->size() * sizeof(float), h);
+  auto nested = [&](const ModelSpec& sub) {
+    const uint64_t f = model_fingerprint(sub);
+    h = sstate::fnv1a64(&f, sizeof(f), h);
+  };
+  if (s.arch == ARCH_WAVENET && s.wavenet.condition_dsp)
+    nested(*s.wavenet.condition_dsp);
+  for (const auto& sub : s.submodels)
+    nested(*sub);
+  return h;
+}
+
+// The state of a newly created batch after nam_hip_batch_reset(prewarm), for the streams `ids` (ascending, unique, in range)
+int restart_streams(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
+{
+  NAM_HIP_CHECK(quiesce(b));
+  for (size_t w = 0; w < b->groups.size(); w++)
+  {
+    WidthGroup& g = b->groups[w];
+    std::vector<int> sub; // the listed streams of this group (a slimmable stream keeps its width)
+    for (int s : ids)
+      if (b->stream_width[(size_t)s] == (int)w)
+        sub.push_back(s);
+    if (sub.empty())
+      continue;
+    const Plan& p = *g.plan;
+    if (p.arch == ARCH_LINEAR) // the stream's own columns of the shared ring; the position and every other column stay
+    {
+      const int cps = p.linear.cols_per_stream;
+      for (int s : sub)
+        NAM_HIP_CHECK(launch_linear_stream_cols(g.d_lin_hist.get(), g.lin_hist_frames, g.lin_cols_pad, g.lin_pos, s * cps, cps, nullptr,
+                                                LINEAR_COLS_ZERO, b->stream.get()));
+      NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
+      continue;
+    }
+    const bool all = sub.size() == g.streams.size();
+    DeviceBuf<int> d_sub;
+    if (!all)
+      NAM_HIP_CHECK(upload(d_sub, sub.data(), sub.size()));
+    const int* const d_map = all ? g.d_map.get() : d_sub.get();
+    int rc = NAM_HIP_OK;
+    // an LSTM's Reset clears nothing (nam_hip_batch_reset mirrors the reference): a new player's slot gets h0 / c0 first, as a
+    // newly created batch's streams do (ensure_state)
+    if (p.arch == ARCH_LSTM && g.d_bank_member)
+      rc = bank_fill_initial_state(b, g, d_map, (int)sub.size());
+    else if (p.arch == ARCH_LSTM)
+    {
+      const hipError_t e = launch_fill_state(g.d_state.get(), g.state_stride, d_map, (int)sub.size(), g.d_init.get(), (int)p.lstm.init_state.size(),
+                                             p.state_floats, b->stream.get());
+      if (e != hipSuccess)
+        rc = fail(NAM_HIP_ERR_DEVICE, std::string("launch_fill_state: ") + hipGetErrorString(e));
+    }
+    if (rc == NAM_HIP_OK)
+      rc = reset_streams(b, g, d_map, (int)sub.size(), prewarm, sub.front());
+    const hipError_t e = hipStreamSynchronize(b->stream.get()); // (before d_sub goes: the launches read it)
+    if (rc != NAM_HIP_OK)
+      return rc;
+    NAM_HIP_CHECK(e);
+  }
+  return NAM_HIP_OK;
+}
+
+// what the plan of width `w` keeps per stream and what its group holds now (stream_state.h)
+static sstate::Geometry stream_geometry(const nam_hip_batch* b, int w)
+{
+  const WidthGroup& g = b->groups[(size_t)w];
+  const Plan& p = *g.plan;
+  sstate::Geometry q;
+  q.arch = p.arch;
+  if (p.arch == ARCH_LINEAR)
+  {
+    q.lin_hist_frames = g.lin_hist_frames;
+    q.lin_channels = p.linear.cols_per_stream;
+    return q;
+  }
+  q.state_floats = p.state_floats;
+  if (p.arch == ARCH_WAVENET)
+  {
+    q.state_family = (int32_t)g.state_family;
+    q.layout0 = p.wr.ok ? p.wr.hist_floats : 0;
+    q.layout1 = p.wr.ok ? p.wr.n_layers : 0;
+  }
+  else
+  {
+    q.layout0 = p.lstm.hidden;
+    q.layout1 = p.lstm.n_layers;
+  }
+  return q;
+}
+static_assert(sstate::kFamilyFresh == (int)STATE_FRESH && (int)STATE_WN_REG == 2, "stream_state.h validates StateFamily's range");
+static_assert(ARCH_LINEAR == 4, "stream_state.h: Geometry::payload_bytes");
+
+int64_t stream_state_bytes(const nam_hip_batch* b, int stream)
+{
+  return sstate::blob_bytes(stream_geometry(b, b->stream_width[(size_t)stream]));
+}
+
+int get_stream_state(nam_hip_batch* b, int stream, void* buf)
+{
+  NAM_HIP_CHECK(quiesce(b));
+  const int w = b->stream_width[(size_t)stream];
+  WidthGroup& g = b->groups[(size_t)w];
+  const sstate::Geometry q = stream_geometry(b, w);
+  const size_t bytes = (size_t)q.payload_bytes();
+  std::vector<float> payload(bytes / sizeof(float));
+  if (q.arch == ARCH_LINEAR)
+  {
+    DeviceBuf<float> rows; // the stream's columns, oldest frame first
+    NAM_HIP_CHECK(hipMalloc(rows.out(), bytes));
+    hipError_t e = launch_linear_stream_cols(g.d_lin_hist.get(), g.lin_hist_frames, g.lin_cols_pad, g.lin_pos, stream * q.lin_channels,
+                                             q.lin_channels, rows.get(), LINEAR_COLS_GATHER, b->stream.get());
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(payload.data(), rows.get(), bytes, hipMemcpyDeviceToHost, b->stream.get());
+    const hipError_t es = hipStreamSynchronize(b->stream.get()); // (before `rows` goes)
+    NAM_HIP_CHECK(e);
+    NAM_HIP_CHECK(es);
+  }
+  else
+  {
+    NAM_HIP_CHECK(hipMemcpyAsync(payload.data(), g.d_state.get() + (size_t)stream * g.state_stride, bytes, hipMemcpyDeviceToHost, b->stream.get()));
+    NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
+  }
+  const int member = b->bank ? b->stream_member[(size_t)stream] : -1;
+  sstate::encode(buf, b->bank ? b->bank->fingerprint : model_fingerprint(*b->model->spec), member,
+                 b->bank ? b->bank->member_fp[(size_t)member] : 0, w, q, payload.data());
+  return NAM_HIP_OK;
+}
+
+int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size)
+{
+  NAM_HIP_CHECK(quiesce(b));
+  // 1. everything the blob says against the batch, before anything changes
+  std::vector<sstate::Geometry> widths;
+  for (size_t w = 0; w < b->groups.size(); w++)
+    widths.push_back(stream_geometry(b, (int)w));
+  sstate::Expect ex;
+  ex.model_fp = b->bank ? b->bank->fingerprint : model_fingerprint(*b->model->spec);
+  ex.member_fp = b->bank ? b->bank->member_fp.data() : nullptr;
+  ex.n_members = b->bank ? b->bank->n_members : 0;
+  ex.widths = widths.data();
+  ex.n_widths = (int32_t)widths.size();
+  sstate::Header h;
+  const std::string why = sstate::validate(buf, size, ex, h);
+  if (!why.empty())
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_state: " + why);
+  const float* const payload = reinterpret_cast<const float*>(static_cast<const char*>(buf) + sizeof(sstate::Header));
+  // 2. the stream joins the blob's width group, as nam_hip_batch_set_slimmable_size moves it — without the reset
+  if (b->stream_width[(size_t)stream] != h.width)
+  {
+    const int rc = move_streams_to_width(b, {stream}, h.width);
+    if (rc != NAM_HIP_OK)
+      return rc;
+  }
+  WidthGroup& g = b->groups[(size_t)h.width];
+  // 3. ... and is bound to the blob's member
+  if (b->bank && b->stream_member[(size_t)stream] != h.member)
+  {
+    b->stream_member[(size_t)stream] = h.member;
+    NAM_HIP_CHECK(hipMemcpy(g.d_bank_member.get(), b->stream_member.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
+  }
+  // 4. the state
+  const size_t bytes = (size_t)h.payload_bytes;
+  if (h.arch == ARCH_LINEAR)
+  {
+    DeviceBuf<float> rows; // oldest frame first: rotated to this batch's ring position by the kernel
+    NAM_HIP_CHECK(upload(rows, payload, bytes / sizeof(float)));
+    const hipError_t e = launch_linear_stream_cols(g.d_lin_hist.get(), g.lin_hist_frames, g.lin_cols_pad, g.lin_pos, stream * h.lin_channels,
+                                                   h.lin_channels, rows.get(), LINEAR_COLS_SCATTER, b->stream.get());
+    const hipError_t es = hipStreamSynchronize(b->stream.get()); // (before `rows` goes)
+    NAM_HIP_CHECK(e);
+    NAM_HIP_CHECK(es);
+    return NAM_HIP_OK;
+  }
+  NAM_HIP_CHECK(hipMemcpyAsync(g.d_state.get() + (size_t)stream * g.state_stride, payload, bytes, hipMemcpyHostToDevice, b->stream.get()));
+  NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
+  if (h.arch == ARCH_WAVENET && g.state_family == STATE_FRESH) // (the other streams of the group are zeros: any layout's)
+    g.state_family = (StateFamily)h.state_family;
   return NAM_HIP_OK;
 }
 

@@ -1,8 +1,9 @@
 // kernel_lstm.hip — the LSTM kernels (lanes = streams; 16 streams per wavefront on the matrix cores) and the
-// per-stream state fill.
+// per-stream state fill (with it: one stream's columns of a Linear batch's history ring).
 #include "device_common.h"
 #include "il_common.h"
 #include "persist_wave.h"
+#include "stream_state.h"
 
 namespace namhip
 {
@@ -1037,6 +1038,22 @@ __global__ void nam_fill_state_bank_kernel(float* state, long state_stride, cons
     st[i] = i < n_init ? mine[i] : 0.0f;
 }
 
+// A Linear batch keeps no per-stream rows: one stream's state is its columns of the batch's history ring (kernels.h:
+// launch_linear_stream_cols). One thread per (canonical row j, column c): ring row = ring_row(pos, j) (stream_state.h).
+__global__ __launch_bounds__(256) void nam_linear_stream_cols_kernel(float* hist, int hist_frames, int cols_pad, int pos, int col0, int n_cols,
+                                                                     float* rows, int op)
+{
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)hist_frames * n_cols)
+    return;
+  const int j = (int)(i / n_cols), c = (int)(i - (long)j * n_cols);
+  float* const cell = hist + (size_t)sstate::ring_row(pos, j, hist_frames) * cols_pad + col0 + c;
+  if (op == LINEAR_COLS_GATHER)
+    rows[i] = *cell;
+  else
+    *cell = op == LINEAR_COLS_SCATTER ? rows[i] : 0.0f;
+}
+
 int lstm_lds_bytes(const LSTMArgs& a)
 {
   const long floats = (long)(a.in_ch + a.out_ch) * kBlock * 65 + 2l * a.n_layers * a.hidden * kBlock + 4l * a.hidden * kBlock;
@@ -1186,6 +1203,19 @@ hipError_t launch_fill_state_bank(float* state, long state_stride, const int* st
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(nam_fill_state_bank_kernel, dim3(n_streams), dim3(256), 0, stream, state, state_stride, stream_map,
                      n_streams, init, member_of, n_init, state_floats);
+  return hipGetLastError();
+}
+
+hipError_t launch_linear_stream_cols(float* hist, int hist_frames, int cols_pad, int pos, int col0, int n_cols, float* rows, LinearColsOp op,
+                                     hipStream_t stream)
+{
+  // (the bounds the kernel's addresses rely on: the columns inside a row, the position inside the ring)
+  if (!hist || hist_frames <= 0 || cols_pad <= 0 || pos < 0 || pos >= hist_frames || col0 < 0 || n_cols <= 0 || col0 + n_cols > cols_pad
+      || (op != LINEAR_COLS_ZERO && !rows) || (long)hist_frames * n_cols > (1l << 30))
+    return hipErrorInvalidValue;
+  const long cells = (long)hist_frames * n_cols;
+  hipLaunchKernelGGL(nam_linear_stream_cols_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, hist, hist_frames, cols_pad,
+                     pos, col0, n_cols, rows, (int)op);
   return hipGetLastError();
 }
 

@@ -353,5 +353,16 @@ hipError_t launch_fill_state(float* state, long state_stride, const int* stream_
 // the bank form: `init` = [member][n_init], stream s takes row member_of[s] (indexed by STREAM, like LSTMArgs::bank_member)
 hipError_t launch_fill_state_bank(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
                                   const int* member_of, int n_init, int state_floats, hipStream_t stream);
+// One stream's columns [col0, col0 + n_cols) of a Linear batch's history ring `hist` = [hist_frames][cols_pad] at position `pos`
+// (the row the next frame goes to: the oldest). `rows` = [hist_frames][n_cols] in device memory, oldest frame first
+// (stream_state.h: ring_row); unused by LINEAR_COLS_ZERO. No other column is read or written.
+enum LinearColsOp : int
+{
+  LINEAR_COLS_ZERO = 0, // the columns become zero
+  LINEAR_COLS_GATHER = 1, // ring -> rows
+  LINEAR_COLS_SCATTER = 2 // rows -> ring
+};
+hipError_t launch_linear_stream_cols(float* hist, int hist_frames, int cols_pad, int pos, int col0, int n_cols, float* rows, LinearColsOp op,
+                                     hipStream_t stream);
 
 } // namespace namhip

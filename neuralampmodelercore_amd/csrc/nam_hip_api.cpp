@@ -462,6 +462,54 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
   return NAM_HIP_OK;
 }
 
+int nam_hip_batch_restart_streams(nam_hip_batch* batch, const int* stream_ids, int n_ids, int prewarm)
+{
+  if (!batch || n_ids < 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_restart_streams: bad argument");
+  return guarded([&]() -> int {
+    std::vector<int> ids;
+    if (const int rc = collect_stream_ids(batch, stream_ids, n_ids, "nam_hip_batch_restart_streams", ids))
+      return rc;
+    NAM_HIP_CHECK(hipSetDevice(batch->device));
+    return restart_streams(batch, ids, prewarm != 0);
+  });
+}
+
+int64_t nam_hip_batch_stream_state_size(const nam_hip_batch* batch, int stream)
+{
+  if (!batch || stream < 0 || stream >= batch->n_streams)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_stream_state_size: bad argument");
+  return stream_state_bytes(batch, stream);
+}
+
+int nam_hip_batch_get_stream_state(nam_hip_batch* batch, int stream, void* buf, int64_t capacity, int64_t* out_size)
+{
+  if (out_size)
+    *out_size = 0;
+  if (!batch || stream < 0 || stream >= batch->n_streams || capacity < 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_get_stream_state: bad argument");
+  const int64_t need = stream_state_bytes(batch, stream);
+  if (out_size)
+    *out_size = need;
+  if (!buf || capacity < need)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_get_stream_state: capacity " + std::to_string(capacity) + ", the stream's state takes "
+                                                + std::to_string(need) + " bytes");
+  return guarded([&]() -> int {
+    NAM_HIP_CHECK(hipSetDevice(batch->device));
+    return get_stream_state(batch, stream, buf);
+  });
+}
+
+int nam_hip_batch_set_stream_state(nam_hip_batch* batch, int stream, const void* buf, int64_t size)
+{
+  if (!batch || stream < 0 || stream >= batch->n_streams || !buf || size < 0)
+    return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_stream_state: bad argument");
+  return guarded([&]() -> int {
+    NAM_HIP_CHECK(hipSetDevice(batch->device));
+    return set_stream_state(batch, stream, buf, size);
+  });
+}
+
 int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids, int n_ids, double ratio)
 {
   if (!batch)
@@ -474,23 +522,8 @@ int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids
   if (w < 0)
     return fail(NAM_HIP_ERR_MODEL, "nam_hip_batch_set_slimmable_size: no plan for this ratio");
   std::vector<int> ids;
-  if (!stream_ids)
-  {
-    ids.resize(batch->n_streams);
-    for (int i = 0; i < batch->n_streams; i++)
-      ids[i] = i;
-  }
-  else
-  {
-    for (int i = 0; i < n_ids; i++)
-    {
-      if (stream_ids[i] < 0 || stream_ids[i] >= batch->n_streams)
-        return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_set_slimmable_size: stream id out of range");
-      ids.push_back(stream_ids[i]);
-    }
-  }
-  std::sort(ids.begin(), ids.end());
-  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  if (const int rc = collect_stream_ids(batch, stream_ids, n_ids, "nam_hip_batch_set_slimmable_size", ids))
+    return rc;
   std::vector<int> moved;
   for (int s : ids)
     if (batch->stream_width[s] != w) // same width: no-op (slimmable.cpp:459-464)
@@ -498,23 +531,8 @@ int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids
   if (moved.empty())
     return NAM_HIP_OK;
   NAM_HIP_CHECK(quiesce(batch));
-  for (int s : moved)
-  {
-    auto& old = batch->groups[batch->stream_width[s]].streams;
-    old.erase(std::remove(old.begin(), old.end(), s), old.end());
-    batch->stream_width[s] = w;
-    batch->groups[w].streams.push_back(s);
-  }
-  std::sort(batch->groups[w].streams.begin(), batch->groups[w].streams.end());
-  int rc = ensure_state(batch, batch->groups[w]);
-  if (rc != NAM_HIP_OK)
+  if (const int rc = move_streams_to_width(batch, moved, w))
     return rc;
-  for (auto& g : batch->groups)
-  {
-    rc = refresh_map(batch, g);
-    if (rc != NAM_HIP_OK)
-      return rc;
-  }
   // fresh sub-model state for the streams that moved: Reset (+ prewarm) as in slimmable.cpp:433-447
   return reset_moved_streams(batch, batch->groups[w], moved, false);
 }
