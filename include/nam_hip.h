@@ -78,8 +78,25 @@ extern "C" {
  *   submit / wait, synchronize, n_streams, kernel_name*. nam_hip_batch_set_persistent returns 0 (a model without recurrence has
  *   nothing to keep resident; calls launch as usual); nam_hip_batch_set_kernel accepts NAM_HIP_KERNEL_AUTO, anything else is
  *   NAM_HIP_ERR_UNSUPPORTED; set_slimmable_size returns what it returns for any non-slimmable model.
- *   NAM_HIP_ERR_UNSUPPORTED too: a Linear model as a member of a bank (nam_hip_bank_create), as a submodel of a SlimmableContainer,
- *   or as a WaveNet's condition_dsp. */
+ *   NAM_HIP_ERR_UNSUPPORTED too: a Linear model as a member of a bank (nam_hip_bank_create), as a submodel of a SlimmableContainer
+ *   that also holds submodels of another architecture ("SlimmableContainer: submodel i is a Linear model ...", naming the first),
+ *   or as a WaveNet's condition_dsp.
+ * A SlimmableContainer whose submodels are ALL Linear, each 1-in / 1-out (one impulse response at several lengths; a submodel with
+ *   more channels fails with the container's mono message), loads: architecture NAM_HIP_ARCH_CONTAINER, is_slimmable 1,
+ *   prewarm_samples 0, nam_hip_model_slimmable_breakpoints = the max_values but the last. Its batch keeps ONE input ring for all
+ *   streams, as long as the longest submodel needs (state_bytes_per_stream: one column of it), and every stream runs the submodel
+ *   nam_hip_batch_set_slimmable_size chose for it (ModelSpec::container_index, container.cpp:85-97; a new batch: the last one) —
+ *   per-stream impulse responses in one launch: nam_linear_pairs_kernel (what kernel_name* report) between the append kernel and a
+ *   reduce kernel, three launches per piece however many sizes are in use.
+ *   Contract: a stream on submodel w produces, BIT FOR BIT, what a one-model Linear batch of w produces for the same input (same
+ *   K-splits, taps oldest first as one chain of fused multiply-adds, partial sums in split order, the bias last), for finite input,
+ *   counted from the stream's last reset or size change — at any stream count and whatever the other streams run.
+ *   set_slimmable_size: a stream that changes submodel starts from a freshly reset one (its column of the ring becomes zero); a
+ *   stream already on that submodel, the ring position and every stream not named are untouched. nam_hip_batch_reset zeroes the
+ *   ring and keeps the sizes; restart_streams zeroes the streams' columns and keeps their sizes. A stream state blob records the
+ *   container and the stream's submodel (its width); the payload is the stream's column, oldest frame first; set_stream_state moves
+ *   the stream to the blob's submodel without the reset. Everything a Linear batch supports works, with the same answers from
+ *   set_persistent (0) and set_kernel (NAM_HIP_KERNEL_AUTO only). As a bank member the container stays refused. */
 
 /* kernel selection for nam_hip_batch_set_kernel */
 #define NAM_HIP_KERNEL_AUTO 0

@@ -7,6 +7,7 @@
 //   api_bank.cpp      model banks: the families' rules (kBankFamily), which models may share a batch, the bank's device image,
 //                     per-stream member binding
 //   launch_policy.h   nam_wn_reg_kernel's launch shape, workgroups per CU and stream bound: integers in, integers out (no HIP)
+//   linear_worklist.h the (column tile, submodel) work list of an all-Linear container's batch: assignment in, tables and extents out (no HIP)
 //   stream_state.h    one stream's state as a blob: header, encode, validate, the Linear ring's row arithmetic (no HIP)
 // No exception leaves these files (guarded); errors are codes + nam_hip_last_error.
 #pragma once
@@ -191,6 +192,26 @@ struct WidthGroup
   int lin_hist_frames = 0, lin_cols_pad = 0, lin_part_frames = 0, lin_piece = 0, lin_pos = 0;
 };
 
+// A batch of a SlimmableContainer whose submodels are all Linear: the input history does not depend on the impulse
+// response, so the batch keeps ONE ring [hist_frames][cols_pad] (column = stream) for all its streams, whichever submodel each is
+// on, and a launch piece runs a work list of (column tile, submodel) pairs (linear_worklist.h). The batch's width groups carry the
+// submodels' plans and the streams' membership only: no blob, no ring, no state of their own. The tables and `part` are sized at
+// creation for the worst assignment; the work list is rebuilt and uploaded by the control calls that change an assignment
+// (nam_hip_batch_set_slimmable_size, nam_hip_batch_set_stream_state), never by a process call.
+struct LinearContainer
+{
+  bool on = false;
+  std::vector<LinearSub> subs; // [submodel]
+  LinearWorkCaps caps;
+  LinearWorkList work; // as the device tables hold it
+  DeviceBuf<float> d_blob; // the submodels' padded taps behind one another
+  DeviceBuf<float> d_hist, d_part; // [hist_frames][cols_pad]; [caps.max_part_slabs][part_frames][32]
+  DeviceBuf<LinearPair> d_pairs; // [caps.max_pairs]
+  DeviceBuf<int32_t> d_col_pair; // [caps.cols_pad]
+  int hist_frames = 0, part_frames = 0, piece = 0;
+  int pos = 0; // the ring row the next frame goes to (host state, as WidthGroup::lin_pos)
+};
+
 // Persistent block mode (nam_hip_batch_set_persistent): one resident launch of nam_a1_p2_kernel per session, fed one
 // command per 64-frame buffer through a device-memory ring (kernel_a1_p2.hip, PERSIST).
 constexpr unsigned kPRing = 1024; // commands in flight at most (power of two)
@@ -320,6 +341,7 @@ struct nam_hip_batch
   std::vector<float> pipe_cvt; // the _f64 forms of submit / wait: one buffer of float32 on the way in / out
   int kernel = NAM_HIP_KERNEL_AUTO;
   std::vector<WidthGroup> groups;
+  LinearContainer lin; // (lin.on: an all-Linear container's batch)
   std::vector<int> stream_width;
   bool was_reset = false;
   bool reset_with_prewarm = true; // thread_local gPrewarmOnResetDefault = true (NAM/dsp.cpp:20)
@@ -468,6 +490,16 @@ int collect_stream_ids(const nam_hip_batch* b, const int* stream_ids, int n_ids,
 // the streams `moved` (ascending) leave their width groups for group `w`: membership, the group's state allocation, every group's
 // device map. Their state in `w` is whatever lies there: the caller resets or writes it. The batch is quiesced.
 int move_streams_to_width(nam_hip_batch* b, const std::vector<int>& moved, int w);
+// An all-Linear container's batch (LinearContainer). lin_container_model: the model is one. _create: the ring, the tables and the
+// first work list, every stream on the last submodel. _launch: a launch of any length, cut into pieces. _move: the streams `moved`
+// (ascending) go to submodel `w` — membership, optionally their columns zeroed over the whole ring, the work list rebuilt and
+// uploaded; the batch is quiesced, and its stream is drained on return.
+bool lin_container_model(const nam_hip_model& m);
+int lin_container_create(nam_hip_batch* b);
+int lin_container_launch(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s);
+int lin_container_move(nam_hip_batch* b, const std::vector<int>& moved, int w, bool zero_columns);
+// frames of history one stream of such a batch keeps at this max_frames
+int lin_container_hist_frames(const nam_hip_model& m, int max_frames);
 // Stream slots (include/nam_hip.h: nam_hip_batch_restart_streams, _get / _set_stream_state), behind the entry points' argument
 // checks. Each quiesces the batch first and leaves its stream drained.
 // `ids`: ascending, unique, in range. The state of a newly created batch after nam_hip_batch_reset(prewarm) for these streams.

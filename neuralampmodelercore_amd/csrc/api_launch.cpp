@@ -616,6 +616,125 @@ static int launch_linear_group(nam_hip_batch* b, WidthGroup& g, const int* d_map
   return NAM_HIP_OK;
 }
 
+// ---- an all-Linear container's batch (api_internal.h: LinearContainer) ----
+
+bool lin_container_model(const nam_hip_model& m)
+{
+  return m.spec->arch == ARCH_CONTAINER && !m.plans.empty() && m.plans[0].arch == ARCH_LINEAR; // (the loader admits all or none)
+}
+
+int lin_container_hist_frames(const nam_hip_model& m, int max_frames)
+{
+  int taps = 0;
+  for (const Plan& p : m.plans)
+    taps = std::max(taps, p.linear.n_splits * p.linear.split_taps);
+  return taps + m.plans[0].linear.piece_frames(max_frames); // (the piece depends on max_frames alone)
+}
+
+// The work list of the streams' current assignment (b->stream_width), checked against what creation allocated, to the device.
+// Control calls only: allocates host memory and copies synchronously.
+static int lin_container_upload(nam_hip_batch* b)
+{
+  LinearContainer& lc = b->lin;
+  if (!build_linear_worklist(b->stream_width.data(), b->n_streams, lc.subs.data(), (int)lc.subs.size(), lc.work)
+      || (int64_t)lc.work.pairs.size() > lc.caps.max_pairs || lc.work.part_slabs > lc.caps.max_part_slabs || lc.work.grid_splits > lc.caps.max_splits
+      || (int)lc.work.col_pair.size() != lc.caps.cols_pad)
+    return fail(NAM_HIP_ERR_MODEL, "Linear container: the work list exceeds what the batch allocated");
+  NAM_HIP_CHECK(hipMemcpy(lc.d_pairs.get(), lc.work.pairs.data(), lc.work.pairs.size() * sizeof(LinearPair), hipMemcpyHostToDevice));
+  NAM_HIP_CHECK(hipMemcpy(lc.d_col_pair.get(), lc.work.col_pair.data(), lc.work.col_pair.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return NAM_HIP_OK;
+}
+
+int lin_container_create(nam_hip_batch* b)
+{
+  const nam_hip_model& m = *b->model;
+  LinearContainer& lc = b->lin;
+  if (b->n_streams > (1 << 24))
+    return fail(NAM_HIP_ERR_UNSUPPORTED, "Linear: more than 16,777,216 columns (streams x channels) in one batch");
+  std::vector<float> blob;
+  for (const Plan& p : m.plans)
+  {
+    LinearSub s;
+    s.n_splits = p.linear.n_splits;
+    s.split_taps = p.linear.split_taps;
+    s.taps_off = (int32_t)blob.size() + p.linear.taps_off;
+    s.bias = p.linear.bias;
+    lc.subs.push_back(s);
+    blob.insert(blob.end(), p.blob.begin(), p.blob.end());
+  }
+  lc.caps = linear_work_caps(b->n_streams, lc.subs.data(), (int)lc.subs.size());
+  if (lc.caps.max_part_slabs > INT32_MAX)
+    return fail(NAM_HIP_ERR_UNSUPPORTED, "Linear container: too many streams x K-splits for one batch");
+  lc.piece = m.plans[0].linear.piece_frames(b->max_frames);
+  lc.part_frames = (lc.piece + kBlock - 1) / kBlock * kBlock;
+  lc.hist_frames = lin_container_hist_frames(m, b->max_frames);
+  lc.pos = 0;
+  NAM_HIP_CHECK(upload(lc.d_blob, blob.data(), blob.size()));
+  const size_t hist_bytes = (size_t)lc.hist_frames * lc.caps.cols_pad * sizeof(float);
+  NAM_HIP_CHECK(hipMalloc(lc.d_hist.out(), hist_bytes));
+  NAM_HIP_CHECK(hipMalloc(lc.d_part.out(), (size_t)linear_part_floats(lc.caps.max_part_slabs, lc.part_frames) * sizeof(float)));
+  NAM_HIP_CHECK(hipMalloc(lc.d_pairs.out(), (size_t)lc.caps.max_pairs * sizeof(LinearPair)));
+  NAM_HIP_CHECK(hipMalloc(lc.d_col_pair.out(), (size_t)lc.caps.cols_pad * sizeof(int32_t)));
+  NAM_HIP_CHECK(hipMemsetAsync(lc.d_hist.get(), 0, hist_bytes, b->stream.get())); // history starts at zero (Buffer, dsp.cpp:203-230)
+  lc.on = true;
+  return lin_container_upload(b);
+}
+
+// As launch_linear_group: pieces of at most lc.piece frames, each append + pairs + reduce on `s`; the ring position advances per piece.
+int lin_container_launch(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long io_stride, hipStream_t s)
+{
+  LinearContainer& lc = b->lin;
+  LinearPairsArgs p;
+  LinearArgs& a = p.a;
+  a.blob = lc.d_blob.get();
+  a.hist = lc.d_hist.get();
+  a.part = lc.d_part.get();
+  a.io_stride = io_stride;
+  a.n_streams = a.n_cols = b->n_streams;
+  a.in_ch = a.out_ch = a.cols_per_stream = 1;
+  a.cols_pad = lc.caps.cols_pad;
+  a.hist_frames = lc.hist_frames;
+  a.part_frames = lc.part_frames;
+  a.n_splits = lc.work.grid_splits;
+  a.split_taps = lc.caps.max_split_taps;
+  a.taps_off = 0;
+  a.bias = 0.0f;
+  p.pairs = lc.d_pairs.get();
+  p.col_pair = lc.d_col_pair.get();
+  p.n_pairs = (int)lc.work.pairs.size();
+  p.hist_taps = lc.caps.max_hist_taps;
+  for (int at = 0; at < n_frames; at += lc.piece)
+  {
+    a.n_frames = std::min(lc.piece, n_frames - at);
+    a.in = d_in ? d_in + at : nullptr;
+    a.out = d_out ? d_out + at : nullptr;
+    a.pos = lc.pos;
+    NAM_HIP_CHECK(launch_linear_pairs(p, s));
+    lc.pos = (lc.pos + a.n_frames) % lc.hist_frames;
+  }
+  return NAM_HIP_OK;
+}
+
+int lin_container_move(nam_hip_batch* b, const std::vector<int>& moved, int w, bool zero_columns)
+{
+  LinearContainer& lc = b->lin;
+  for (int s : moved)
+  {
+    auto& old = b->groups[(size_t)b->stream_width[(size_t)s]].streams;
+    old.erase(std::remove(old.begin(), old.end(), s), old.end());
+    b->stream_width[(size_t)s] = w;
+    b->groups[(size_t)w].streams.push_back(s);
+  }
+  std::sort(b->groups[(size_t)w].streams.begin(), b->groups[(size_t)w].streams.end());
+  // a freshly reset submodel (container.cpp:85-97 + Reset): the stream's column is zero over the whole ring; the position and every
+  // other column stay
+  for (size_t i = 0; zero_columns && i < moved.size(); i++)
+    NAM_HIP_CHECK(launch_linear_stream_cols(lc.d_hist.get(), lc.hist_frames, lc.caps.cols_pad, lc.pos, moved[i], 1, nullptr, LINEAR_COLS_ZERO,
+                                            b->stream.get()));
+  NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
+  return lin_container_upload(b);
+}
+
 // Launch one group's kernel over `n` streams given by `d_map` (nullptr = streams 0..n-1).
 int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out,
                  int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx)
@@ -792,6 +911,14 @@ uint64_t model_fingerprint(const ModelSpec& s)
 int restart_streams(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
 {
   NAM_HIP_CHECK(quiesce(b));
+  if (b->lin.on) // the streams' columns of the one ring; sizes, the position and every other column stay
+  {
+    for (int s : ids)
+      NAM_HIP_CHECK(launch_linear_stream_cols(b->lin.d_hist.get(), b->lin.hist_frames, b->lin.caps.cols_pad, b->lin.pos, s, 1, nullptr,
+                                              LINEAR_COLS_ZERO, b->stream.get()));
+    NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
+    return NAM_HIP_OK;
+  }
   for (size_t w = 0; w < b->groups.size(); w++)
   {
     WidthGroup& g = b->groups[w];
@@ -838,6 +965,19 @@ int restart_streams(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
   return NAM_HIP_OK;
 }
 
+// the history ring a Linear stream's columns live in: the group's own, or the one ring of an all-Linear container's batch
+struct LinRing
+{
+  float* hist;
+  int frames, cols_pad, pos;
+};
+static LinRing lin_ring(const nam_hip_batch* b, const WidthGroup& g)
+{
+  if (b->lin.on)
+    return LinRing{b->lin.d_hist.get(), b->lin.hist_frames, b->lin.caps.cols_pad, b->lin.pos};
+  return LinRing{g.d_lin_hist.get(), g.lin_hist_frames, g.lin_cols_pad, g.lin_pos};
+}
+
 // what the plan of width `w` keeps per stream and what its group holds now (stream_state.h)
 static sstate::Geometry stream_geometry(const nam_hip_batch* b, int w)
 {
@@ -847,7 +987,7 @@ static sstate::Geometry stream_geometry(const nam_hip_batch* b, int w)
   q.arch = p.arch;
   if (p.arch == ARCH_LINEAR)
   {
-    q.lin_hist_frames = g.lin_hist_frames;
+    q.lin_hist_frames = lin_ring(b, g).frames;
     q.lin_channels = p.linear.cols_per_stream;
     return q;
   }
@@ -885,8 +1025,9 @@ int get_stream_state(nam_hip_batch* b, int stream, void* buf)
   {
     DeviceBuf<float> rows; // the stream's columns, oldest frame first
     NAM_HIP_CHECK(hipMalloc(rows.out(), bytes));
-    hipError_t e = launch_linear_stream_cols(g.d_lin_hist.get(), g.lin_hist_frames, g.lin_cols_pad, g.lin_pos, stream * q.lin_channels,
-                                             q.lin_channels, rows.get(), LINEAR_COLS_GATHER, b->stream.get());
+    const LinRing r = lin_ring(b, g);
+    hipError_t e = launch_linear_stream_cols(r.hist, r.frames, r.cols_pad, r.pos, stream * q.lin_channels, q.lin_channels, rows.get(),
+                                             LINEAR_COLS_GATHER, b->stream.get());
     if (e == hipSuccess)
       e = hipMemcpyAsync(payload.data(), rows.get(), bytes, hipMemcpyDeviceToHost, b->stream.get());
     const hipError_t es = hipStreamSynchronize(b->stream.get()); // (before `rows` goes)
@@ -925,7 +1066,7 @@ int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size
   // 2. the stream joins the blob's width group, as nam_hip_batch_set_slimmable_size moves it — without the reset
   if (b->stream_width[(size_t)stream] != h.width)
   {
-    const int rc = move_streams_to_width(b, {stream}, h.width);
+    const int rc = b->lin.on ? lin_container_move(b, {stream}, h.width, false) : move_streams_to_width(b, {stream}, h.width);
     if (rc != NAM_HIP_OK)
       return rc;
   }
@@ -942,8 +1083,9 @@ int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size
   {
     DeviceBuf<float> rows; // oldest frame first: rotated to this batch's ring position by the kernel
     NAM_HIP_CHECK(upload(rows, payload, bytes / sizeof(float)));
-    const hipError_t e = launch_linear_stream_cols(g.d_lin_hist.get(), g.lin_hist_frames, g.lin_cols_pad, g.lin_pos, stream * h.lin_channels,
-                                                   h.lin_channels, rows.get(), LINEAR_COLS_SCATTER, b->stream.get());
+    const LinRing r = lin_ring(b, g);
+    const hipError_t e = launch_linear_stream_cols(r.hist, r.frames, r.cols_pad, r.pos, stream * h.lin_channels, h.lin_channels, rows.get(),
+                                                   LINEAR_COLS_SCATTER, b->stream.get());
     const hipError_t es = hipStreamSynchronize(b->stream.get()); // (before `rows` goes)
     NAM_HIP_CHECK(e);
     NAM_HIP_CHECK(es);

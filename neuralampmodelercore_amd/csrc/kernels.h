@@ -5,6 +5,7 @@
 #include <hip/hip_ext.h>
 #include <type_traits>
 
+#include "linear_worklist.h"
 #include "plan.h"
 
 namespace namhip
@@ -281,6 +282,22 @@ struct LinearArgs
 };
 // append + nam_linear_kernel + nam_linear_reduce_kernel (+ zeros for output channels >= cols_per_stream), enqueued on `stream`
 hipError_t launch_linear(const LinearArgs& a, hipStream_t stream);
+
+// A SlimmableContainer of Linear models (linear_worklist.h): every stream one column (1-in / 1-out) of the same ring, each on its own
+// submodel. One PIECE of a launch, three kernels: nam_linear_append_kernel as above, nam_linear_pairs_kernel over the work list,
+// nam_linear_pairs_reduce_kernel (every column sums its own pair's splits and adds that submodel's bias).
+struct LinearPairsArgs
+{
+  // blob: the submodels' padded taps behind one another (LinearPair::taps_off points into it); part: [slab][part_frames][32];
+  // n_splits: the grid's split extent (LinearWorkList::grid_splits); split_taps: the largest of the container (the dynamic LDS);
+  // in_ch = out_ch = cols_per_stream = 1; taps_off and bias are the pairs'
+  LinearArgs a;
+  const LinearPair* pairs; // [n_pairs]
+  const int32_t* col_pair; // [cols_pad]
+  int n_pairs;
+  int hist_taps; // the largest n_splits x split_taps of a submodel: the ring keeps that many frames + the piece
+};
+hipError_t launch_linear_pairs(const LinearPairsArgs& p, hipStream_t stream);
 
 // nam_wn_reg_kernel (plan.h: WrPlan). One launch serves up to kWrMaxGroups WIDTH GROUPS — streams of a slimmable model
 // (or container) that currently run different sub-models: workgroups [first, next group's first) belong to group g, each

@@ -190,6 +190,9 @@ int64_t nam_hip_model_get_string(const nam_hip_model* model, int field, char* bu
                   + (p.wr.ok ? std::string(" wn_reg=1") : " wn_reg=0 (" + p.wr.why + ")")
                   + (p.wr.jit_failed.empty() ? std::string() : " wn_reg_jit=failed (" + p.wr.jit_failed + ")");
       }
+      if (lin_container_model(*model)) // (the plans above are the submodels' own: as one-model batches run them)
+        text += " | container: kernel=nam_linear_pairs_kernel, one ring for every stream, ring_frames="
+                + std::to_string(lin_container_hist_frames(*model, 0));
       break;
     default: return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_model_get_string: unknown field");
   }
@@ -273,6 +276,8 @@ int nam_hip_model_get_info(const nam_hip_model* model, nam_hip_model_info* info)
                         | ((p.a1.valid && p.a1.il_ok && p.a1.p2_ok) ? 4 | 8 : 0)
                         | (p.wr.ok ? 16 : 0) | (p.wr.jit_failed.empty() ? 0 : 32);
   info->state_bytes_per_stream = (int64_t)p.state_floats * (int64_t)sizeof(float);
+  if (lin_container_model(*model)) // one column of the batch's one ring, as long as the longest submodel needs (max_frames <= kLinearPieceCap)
+    info->state_bytes_per_stream = (int64_t)lin_container_hist_frames(*model, 0) * (int64_t)sizeof(float);
   std::strncpy(info->version, s.version.c_str(), sizeof(info->version) - 1);
   return NAM_HIP_OK;
 }
@@ -336,11 +341,12 @@ static int create_batch(const nam_hip_model* model, std::shared_ptr<const nam_hi
   // nam_hip_batch_destroy: its owners release whatever was already allocated (stream, blobs, state, staging)
   const int rc = [&]() -> int {
     NAM_HIP_CHECK(hipStreamCreateWithFlags(b->stream.out(), hipStreamNonBlocking));
+    const bool lin_container = !b->bank && lin_container_model(*model); // (its groups: plans and membership only)
     b->groups.resize(model->plans.size());
     for (size_t i = 0; i < model->plans.size(); i++)
     {
       b->groups[i].plan = &model->plans[i];
-      const int r = b->bank ? upload_bank_group(b, b->groups[i]) : upload_group(b, b->groups[i]);
+      const int r = lin_container ? NAM_HIP_OK : b->bank ? upload_bank_group(b, b->groups[i]) : upload_group(b, b->groups[i]);
       if (r != NAM_HIP_OK)
         return r;
     }
@@ -349,7 +355,7 @@ static int create_batch(const nam_hip_model* model, std::shared_ptr<const nam_hi
     g.streams.resize(n_streams);
     for (int i = 0; i < n_streams; i++)
       g.streams[i] = i;
-    const int r = ensure_state(b, g);
+    const int r = lin_container ? lin_container_create(b) : ensure_state(b, g);
     if (r != NAM_HIP_OK)
       return r;
     const size_t in_floats = (size_t)n_streams * model->spec->in_channels() * max_frames;
@@ -444,9 +450,15 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
   NAM_HIP_CHECK(quiesce(batch)); // launches still running on a caller-supplied stream must not race with the zeroing
   batch->was_reset = true;
   batch->reset_with_prewarm = prewarm != 0;
+  if (batch->lin.on) // zero history, as a Linear batch's; the streams keep their submodels
+  {
+    NAM_HIP_CHECK(hipMemsetAsync(batch->lin.d_hist.get(), 0, (size_t)batch->lin.hist_frames * batch->lin.caps.cols_pad * sizeof(float),
+                                 batch->stream.get()));
+    batch->lin.pos = 0;
+  }
   for (auto& g : batch->groups)
   {
-    if (g.streams.empty())
+    if (g.streams.empty() || batch->lin.on)
       continue;
     const int rc = reset_streams(batch, g, g.d_map.get(), (int)g.streams.size(), prewarm != 0, g.streams.front());
     if (rc != NAM_HIP_OK)
@@ -531,6 +543,8 @@ int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids
   if (moved.empty())
     return NAM_HIP_OK;
   NAM_HIP_CHECK(quiesce(batch));
+  if (batch->lin.on) // the moved streams' columns of the one ring become zero: a freshly reset submodel
+    return lin_container_move(batch, moved, w, true);
   if (const int rc = move_streams_to_width(batch, moved, w))
     return rc;
   // fresh sub-model state for the streams that moved: Reset (+ prewarm) as in slimmable.cpp:433-447
@@ -571,6 +585,8 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
     if (gs.n > 1)
       return n_frames > 0 ? launch_wr_all(batch, gs, d_in, d_out, n_frames, (long)frame_stride, s, LaunchContext()) : NAM_HIP_OK;
   }
+  if (batch->lin.on) // one launch for every stream, whichever submodel each is on
+    return lin_container_launch(batch, d_in, d_out, n_frames, (long)frame_stride, s);
   for (auto& g : batch->groups)
   {
     if (g.streams.empty())
@@ -837,10 +853,11 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
     if (rc != NAM_HIP_OK)
       return rc;
   }
-  if (batch->model->spec->arch == ARCH_LINEAR) // one device engine (include/nam_hip.h): nothing to choose
+  if (batch->model->spec->arch == ARCH_LINEAR || batch->lin.on) // one device engine (include/nam_hip.h): nothing to choose
   {
     if (kernel != NAM_HIP_KERNEL_AUTO)
-      return fail(NAM_HIP_ERR_UNSUPPORTED, "nam_hip_batch_set_kernel: a Linear batch runs nam_linear_kernel only (NAM_HIP_KERNEL_AUTO)");
+      return fail(NAM_HIP_ERR_UNSUPPORTED, batch->lin.on ? "nam_hip_batch_set_kernel: a container of Linear models runs nam_linear_pairs_kernel only (NAM_HIP_KERNEL_AUTO)"
+                                                         : "nam_hip_batch_set_kernel: a Linear batch runs nam_linear_kernel only (NAM_HIP_KERNEL_AUTO)");
     batch->kernel = kernel;
     return NAM_HIP_OK;
   }
@@ -923,8 +940,10 @@ int nam_hip_batch_debug_timeline(nam_hip_batch* batch, int n_frames, long long* 
   {
     LaunchContext ctx;
     ctx.dbg = dbg.get();
+    if (batch->lin.on)
+      rc = lin_container_launch(batch, nullptr, nullptr, n_frames, 0, batch->stream.get());
     for (auto& g : batch->groups)
-      if (!g.streams.empty() && rc == NAM_HIP_OK)
+      if (!g.streams.empty() && rc == NAM_HIP_OK && !batch->lin.on)
         rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), nullptr, nullptr, n_frames, 0, batch->stream.get(), ctx);
     e = hipStreamSynchronize(batch->stream.get()); // (before `dbg` goes: the launches write it)
     if (e == hipSuccess)
@@ -945,6 +964,8 @@ const char* nam_hip_batch_kernel_name_for(const nam_hip_batch* batch, int n_fram
 {
   if (!batch)
     return "";
+  if (batch->lin.on) // the work list's kernel, whatever the assignment
+    return "nam_linear_pairs_kernel";
   // the group with the most streams (a uniform batch has exactly one populated group)
   const WidthGroup* best = &batch->groups[batch->model->full_width];
   for (const auto& g : batch->groups)

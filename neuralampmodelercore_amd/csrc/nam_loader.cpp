@@ -828,8 +828,13 @@ static std::shared_ptr<ModelSpec> build_model(const Value& root, const LoadOptio
         throw std::runtime_error("ContainerModel: submodels must be sorted by ascending max_value");
     if (m->sub_max_value.back() < 1.0)
       throw std::runtime_error("ContainerModel: last submodel max_value must be >= 1.0");
-    for (size_t i = 0; i < m->submodels.size(); i++)
-      if (m->submodels[i]->arch == ARCH_LINEAR) // (one shared impulse response per batch: nam_linear_kernel knows no width groups)
+    // Linear submodels: all of them or none. An all-Linear container is one batch with one input ring and an impulse response per
+    // stream (nam_linear_pairs_kernel); the other architectures' width groups keep per-stream state rows, which a Linear model has none of
+    bool all_linear = true;
+    for (const auto& sm : m->submodels)
+      all_linear = all_linear && sm->arch == ARCH_LINEAR;
+    for (size_t i = 0; !all_linear && i < m->submodels.size(); i++)
+      if (m->submodels[i]->arch == ARCH_LINEAR)
         throw UnsupportedError("SlimmableContainer: submodel " + std::to_string(i)
                                + " is a Linear model, which the device path runs only as a batch's one model");
     for (const auto& sm : m->submodels)
