@@ -383,16 +383,21 @@ NAM_HIP_API int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* cons
 
 /* Persistent block mode (opt-in; nam_a1_q_kernel / nam_a1_p4_kernel, nam_kq_kernel, nam_wn_reg_kernel — mixed slimmable widths included — and
  * the small LSTM kernels): instead of one kernel launch per nam_hip_batch_process_device call, a SESSION launch consumes
- * every call of a multiple of 64 frames (up to 2,048; n_frames / 64 commands) — a command is a 64-bit word in a
+ * every call of up to 2,048 frames — of ANY length on nam_wn_reg_kernel and the LSTM kernels (n_frames / 64 whole commands and
+ * one partial command of 1 .. 63 frames: 32- and 48-frame hosts, 120 / 240 / 480-frame network packets stay on the resident
+ * launch), of a multiple of 64 frames on nam_a1_q_kernel / nam_a1_p4_kernel / nam_kq_kernel (n_frames / 64 commands; their
+ * pipelines hand fixed sub-blocks from stage to stage) — a command is a 64-bit word in a
  * device-memory ring, stored by the host itself when the call's stream is idle, else by hipStreamWriteValue64 on that
  * stream, so it is ordered behind whatever produced the input there — for as long as the next command is already there
  * when a buffer is finished, and leaves as soon as the ring is empty (a device-wide synchronize never waits for a
  * session; the next call starts the launch again). What a launch per buffer pays on top of the computation (dispatch,
  * cold prologue, state in and out: 4-12 us) is paid once per burst.
  * Consecutive calls must address the same resident window (d_in / d_out of the first call plus a common frame offset,
- * same frame_stride; device memory or host-mapped memory); anything else — another window, a ragged length, Reset,
- * SetSlimmableSize, set_kernel, a render, destroy — ends the session first (the launch writes the streams' state back),
- * transparently. The blocking *_f32 / *_f64 entry points stay inside the session (host-mapped staging).
+ * same frame_stride, offsets of any alignment; device memory or host-mapped memory); anything else — another window, Reset,
+ * SetSlimmableSize, set_kernel, a render, destroy, and on the three pipeline kernels a length that is no multiple of 64 (it runs
+ * as a plain launch; the next whole buffer starts a session again) — ends the session first (the launch writes the streams'
+ * state back), transparently. A session that has carried partial commands is renumbered (one flush and session start) every 2^25
+ * commands — 9.3 hours of 48-frame calls at 48 kHz — instead of every 2^30 (csrc/session_command.h). The blocking *_f32 / *_f64 entry points stay inside the session (host-mapped staging).
  * Outputs are NOT ordered on the caller's stream: call nam_hip_batch_flush (or nam_hip_batch_synchronize, or use the
  * blocking *_f32 / *_f64 entry points, which do it) before consuming them.
  * Eligible: one width group on nam_a1_q_kernel / nam_a1_p4_kernel / nam_kq_kernel up to 8 streams per CU (beyond one per CU the workgroups
@@ -416,7 +421,9 @@ NAM_HIP_API int nam_hip_batch_flush(nam_hip_batch* batch, void* hip_stream);
  * there and copies it to `out` ([n_streams][out_channels][the submit's n_frames]; NULL: completed and discarded). Up to
  * NAM_HIP_PIPE_SLOTS tickets may be in flight (the next submit fails with NAM_HIP_ERR_INVALID_ARGUMENT until the oldest
  * has been waited for); buffers are rendered in submit order, a ticket is waited for once, in any order.
- * In persistent mode (nam_hip_batch_set_persistent) buffers of a multiple of 64 frames are commands of the session, the
+ * In persistent mode (nam_hip_batch_set_persistent) buffers are commands of the session — of any length on nam_wn_reg_kernel and
+ * the LSTM kernels, of a multiple of 64 frames on the pipeline kernels (another length there is rendered at once by plain
+ * launches and handed out by the wait) —, the
  * input written through the PCIe window, the output stored to host memory by the resident launch itself — nam_a1_q_kernel
  * and nam_kq_kernel publish every command, so a wait returns while the launch runs on with the buffers behind it; other
  * kernels' tickets complete when the launch has drained its ring. (The pipeline of nam_a1_q_kernel holds five to six

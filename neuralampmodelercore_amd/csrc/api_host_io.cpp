@@ -51,7 +51,10 @@ bool host_windows(nam_hip_batch* b, int slots, HostWindows& w, bool prealloc)
 
 bool host_mapped_applies(nam_hip_batch* b, int n_frames)
 {
-  if (!b->ps.enabled || n_frames % kBlock != 0 || n_frames > kPersistMaxFrames || !persist_eligible(b))
+  if (!b->ps.enabled || n_frames > kPersistMaxFrames)
+    return false;
+  const int kind = persist_kind(b);
+  if (kind == PERSIST_NONE || (n_frames % kBlock != 0 && !persist_any_length(kind))) // (a ragged length: only kernels that take a count per command)
     return false;
   for (auto& g0 : b->groups)
     if (!g0.streams.empty() && g0.plan->arch == ARCH_WAVENET && g0.state_family >= 0 && g0.state_family != persist_family(b, g0))
@@ -61,7 +64,7 @@ bool host_mapped_applies(nam_hip_batch* b, int n_frames)
 
 
 // Returns 0 when the buffer went through the session, 1 when the mode does not apply (not enabled / not eligible /
-// n_frames not a multiple of 64), < 0 on failure.
+// n_frames not a multiple of 64 on a session kernel that needs one: persist_any_length), < 0 on failure.
 int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_f64, float* out_f32, double* out_f64, int n_frames)
 {
   if (!host_mapped_applies(b, n_frames) || !host_windows(b, 1, b->win))
@@ -81,7 +84,7 @@ int process_host_mapped(nam_hip_batch* b, const float* in_f32, const double* in_
   }
   push_out_host_stores();
   CallHints hints; // what this call tells the launches started on its behalf, and no launch after it
-  hints.one_buffer_call = n_frames == kBlock; // (one command, then the caller waits: the stages of a pipeline would only queue up)
+  hints.one_buffer_call = n_frames <= kBlock; // (one command, then the caller waits: the stages of a pipeline would only queue up)
   hints.short_blocking_call = n_frames <= 4 * kBlock;
   const SessionCaller caller(b->stream.get(), hints);
   // nam::DSP::process back to back (NAM/dsp.h:97; tools/benchmodel.cpp:129-132: a loop of blocking calls): when the previous
@@ -175,7 +178,7 @@ int pipe_submit(nam_hip_batch* b, const float* in, int n_frames, PipeSlot& sl, i
     sl.how = 1;
     return NAM_HIP_OK;
   }
-  // a session batch with a ragged length (or without host-mapped memory): rendered now, handed out by the wait
+  // a session batch of a pipeline kernel with a ragged length (or one without host-mapped memory): rendered now, handed out by the wait
   sl.held.resize(rows_out * n_frames);
   const int rc = nam_hip_batch_process_f32(b, in, sl.held.data(), n_frames);
   if (rc != NAM_HIP_OK)

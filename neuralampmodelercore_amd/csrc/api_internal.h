@@ -32,6 +32,7 @@
 #include "launch_policy.h"
 #include "model_spec.h"
 #include "plan.h"
+#include "session_command.h"
 #include "stream_state.h"
 #include "wr_jit.h"
 
@@ -384,7 +385,15 @@ enum PersistKind : int
 
 // (kPersistTurns, how many turns a session's workgroups may take on the chip: launch_policy.h)
 constexpr int kGraceUs = 40; // how long a fresh launch looks for the doorbell it was started for
-constexpr int kPersistMaxFrames = 2048; // buffers up to this long go through the session as n_frames / 64 commands
+constexpr int kPersistMaxFrames = 2048; // buffers up to this long go through the session as ceil(n_frames / 64) commands
+static_assert(session::kCmdFrames == kBlock, "a whole session command is one device block");
+// Session kernels that take a frame count with every command (PersistWave hands it out: persist_wave.h), so a call of ANY length up to
+// kPersistMaxFrames stays in the session. The pipeline kernels (PERSIST_A1_P2, PERSIST_KQ) hand fixed sub-blocks from stage to stage:
+// their sessions take multiples of 64 frames only, any other length ends the session and runs a plain launch.
+constexpr bool persist_any_length(int kind)
+{
+  return kind == PERSIST_WN_REG || kind == PERSIST_LSTM_ROW || kind == PERSIST_LSTM_WIDE;
+}
 
 // The non-empty groups of a batch when ALL of them run nam_wn_reg_kernel (then one launch serves the whole batch, and a
 // persistent session can too); n = 0 otherwise. (A fixed array: this runs inside process calls, which allocate nothing.)
@@ -518,7 +527,7 @@ int persist_stop(nam_hip_batch* b, CallHints hints);
 int persist_prepare(nam_hip_batch* b);
 int persist_start(nam_hip_batch* b, const float* d_in, float* d_out, long stride);
 int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long stride, const SessionCaller& caller);
-int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, const SessionCaller& caller);
+int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, const SessionCaller& caller, int n = kBlock);
 void persist_free(nam_hip_batch* b);
 // api_launch.cpp
 int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out);

@@ -454,15 +454,22 @@ int persist_start(nam_hip_batch* b, const float* d_in, float* d_out, long stride
   return NAM_HIP_OK;
 }
 
-// One 64-frame buffer for every stream of the batch through the session. Returns 1 when this call cannot be expressed
-// as a command of a session (the caller then launches as usual).
+// One buffer for every stream of the batch through the session. Returns 1 when this call cannot be expressed as commands of a
+// session (the caller then launches as usual).
 // A buffer of any multiple of 64 frames (what hosts send: NAM/dsp.h:97 takes any num_frames <= maxBufferSize; plugins run
 // 64 ... 1,024) is that many commands, submitted back to back: the session renders them without a kernel boundary in between.
+// Any other length (32- or 48-frame low-latency hosts, 120 / 240 / 480-frame network packets) is its whole commands and one
+// partial command behind them (session_command.h) when the session's kernel takes a frame count per command
+// (persist_any_length: nam_wn_reg_kernel and the two LSTM kernels); for the pipeline kernels it stays outside the session.
 int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_frames, long stride, const SessionCaller& caller)
 {
   // (longer calls — an offline render of a whole file — are one resident launch of their own: same kernel, no commands)
-  if (n_frames <= 0 || n_frames % kBlock != 0 || n_frames > kPersistMaxFrames)
+  if (n_frames <= 0 || n_frames > kPersistMaxFrames)
     return 1;
+  const bool partial = session::has_partial(n_frames);
+  if (partial && !persist_any_length(persist_kind(b)))
+    return 1;
+  const int n_cmds = session::command_count(n_frames);
   {
     // A buffer is never split across sessions: whether this one still fits the session — its sequence numbers below the
     // rebase mark, its LAST command inside the 2 GB window the kernels address — is decided once, here, not command by
@@ -471,9 +478,10 @@ int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_fram
     PersistSession& ps = b->ps;
     if (ps.active)
     {
-      const long off_last = (d_in + (n_frames - kBlock)) - ps.in_base;
-      const bool past_mark = ps.seq + (unsigned)(n_frames / kBlock) >= ps.rebase_at;
-      if (past_mark || off_last > 0x1fff0000l)
+      const long off_last = (d_in + session::command_offset(n_cmds - 1)) - ps.in_base;
+      // (a call with a partial command is held to the shorter tag of that encoding: session_command.h, kPartialRebaseAt)
+      const bool past_mark = !session::call_fits(ps.seq, n_frames, ps.rebase_at);
+      if (past_mark || off_last > session::kWindowMaxOff)
       {
         // (the session that starts with this buffer renumbers from 0 even if the count itself has not reached the mark yet:
         // otherwise a buffer of several commands would reach it in mid-buffer and be split after all)
@@ -483,17 +491,21 @@ int persist_submit(nam_hip_batch* b, const float* d_in, float* d_out, int n_fram
           return rc;
       }
     }
+    else if (partial && !session::call_fits(ps.seq, n_frames, ps.rebase_at))
+      ps.rebase_pending = true; // (the numbering runs on across sessions: the one this call starts renumbers from 0)
   }
-  for (int f = 0; f < n_frames; f += kBlock)
+  for (int i = 0; i < n_cmds; i++)
   {
-    const int rc = persist_submit_block(b, d_in + f, d_out + f, stride, caller);
+    const int f = session::command_offset(i);
+    const int rc = persist_submit_block(b, d_in + f, d_out + f, stride, caller, session::command_frames(n_frames, i));
     if (rc != NAM_HIP_OK)
       return rc < 0 ? rc : (f == 0 ? rc : fail(NAM_HIP_ERR_DEVICE, "persistent session: a buffer was split across sessions"));
   }
   return NAM_HIP_OK;
 }
 
-int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, const SessionCaller& caller)
+// `n`: the command's frames, 1 .. 64 (fewer than 64: only for a session kernel of persist_any_length — persist_submit decides)
+int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long stride, const SessionCaller& caller, int n)
 {
   PersistSession& ps = b->ps;
   if (ps.active)
@@ -564,7 +576,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
     if (idle)
       ps.outstanding = false;
   }
-  const unsigned long long cmd = ((unsigned long long)(ps.seq + 1) << 32) | (unsigned long long)(unsigned)(d_in - ps.in_base);
+  const unsigned long long cmd = session::encode(ps.seq + 1, (unsigned)(d_in - ps.in_base), n); // (64 frames: `(seq + 1) << 32 | offset`, as ever)
   const unsigned slot = ps.seq & (kPRing - 1);
   // Nothing in flight on the caller's stream: nothing to order the command behind, the host stores it itself (no
   // device-side write operation, which costs the host ~4 us and the device a small kernel per buffer).

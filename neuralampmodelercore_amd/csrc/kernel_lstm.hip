@@ -641,7 +641,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BANK ? 8 : 1
   const bool pers = a.ps.ring != nullptr;
   PersistWave pw;
   unsigned cmd_off = 0;
-  if (pers && !pw.begin(a.ps, (int)blockIdx.x, cmd_off))
+  int cmd_n = kBlock; // frames of the session command in hand, 1 .. 64 (session_command.h)
+  if (pers && !pw.begin(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
   {
     pw.leave(a.ps, (int)blockIdx.x); // nothing to do
     return;
@@ -660,7 +661,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BANK ? 8 : 1
 
   for (int f0 = pers ? (int)cmd_off : 0;;)
   {
-    const int nvalid = pers ? kBlock : min(kBlock, a.n_frames - f0);
+    const int nvalid = pers ? cmd_n : min(kBlock, a.n_frames - f0);
     if (pers)
       pw.look_ahead(a.ps);
     // lane q of the row: frames q, q + 16, q + 32, q + 48 of the row's stream (16 lanes = 64 contiguous bytes)
@@ -681,7 +682,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BANK ? 8 : 1
     auto step = [&](auto t_tag, auto whole_tag) {
       constexpr int T = decltype(t_tag)::value;
       if constexpr (!decltype(whole_tag)::value)
-        if (T >= nvalid) // (wavefront-uniform; a whole block — every block but a launch's ragged last one — runs the steps without the test)
+        if (T >= nvalid) // (wavefront-uniform; a whole block — every block but a launch's ragged last one or a session's partial command — runs the steps without the test)
           return;
 #pragma unroll
       for (int l = 0; l < NL; l++)
@@ -758,7 +759,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BANK ? 8 : 1
       }
     if (pers)
     {
-      if (!pw.next(a.ps, (int)blockIdx.x, cmd_off))
+      if (!pw.next(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
         break; // ring empty: leave
       f0 = (int)cmd_off;
     }
@@ -884,7 +885,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   const bool pers = a.ps.ring != nullptr;
   PersistWave pw;
   unsigned cmd_off = 0;
-  if (pers && !pw.begin(a.ps, (int)blockIdx.x, cmd_off))
+  int cmd_n = kBlock; // frames of the session command in hand, 1 .. 64 (session_command.h)
+  if (pers && !pw.begin(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
   {
     pw.leave(a.ps, (int)blockIdx.x); // nothing to do
     return;
@@ -907,7 +909,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
 
   for (int f0 = pers ? (int)cmd_off : 0;;)
   {
-    const int nvalid = pers ? kBlock : min(kBlock, a.n_frames - f0);
+    const int nvalid = pers ? cmd_n : min(kBlock, a.n_frames - f0);
     if (pers)
       pw.look_ahead(a.ps);
     float xv[NI]; // lane = frame
@@ -992,7 +994,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     }
     if (pers)
     {
-      if (!pw.next(a.ps, (int)blockIdx.x, cmd_off))
+      if (!pw.next(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
         break; // ring empty: leave
       f0 = (int)cmd_off;
     }

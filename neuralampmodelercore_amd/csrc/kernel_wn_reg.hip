@@ -1115,6 +1115,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
   const bool pers = a.ps.ring != nullptr;
   PersistWave pw;
   unsigned cmd_off = 0;
+  int cmd_n = kBlock; // frames of the session command in hand, 1 .. 64 (session_command.h)
   float* const st = G.state + (long)stream * G.state_stride;
   int* const sti = reinterpret_cast<int*>(st);
   float* const st_ring = st + kWrPosInts;
@@ -1126,7 +1127,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
   unsigned done = 0; // NST > 1, last wave: commands finished
   if constexpr (NST == 1)
   {
-    if (pers && !pw.begin(a.ps, (int)blockIdx.x, cmd_off))
+    if (pers && !pw.begin(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
     {
       pw.leave(a.ps, (int)blockIdx.x); // nothing to do
       return;
@@ -1137,7 +1138,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
     // wave 0 looks for the launch's first command; its answer is the workgroup's
     if (S == 0)
     {
-      const bool ready = !pers || pw.begin(a.ps, (int)blockIdx.x, cmd_off);
+      const bool ready = !pers || pw.begin(a.ps, (int)blockIdx.x, cmd_off, cmd_n);
       if (lane < NST - 1) // (the queues' counters)
       {
         int* const qw = reinterpret_cast<int*>(lds + queue0_b + (unsigned)lane * (unsigned)kWrQueueBytes + kQRegsB);
@@ -1365,7 +1366,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
     WrRegs r;
     if (NST == 1 || S == 0)
     {
-      n = pers ? kBlock : min(kBlock, a.n_frames - f0);
+      n = pers ? cmd_n : min(kBlock, a.n_frames - f0); // (a session's partial block may stand anywhere in the stream: everything below moves on by n)
       if (pers)
         pw.look_ahead(a.ps);
       if (pf_off == f0)
@@ -1415,8 +1416,10 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
               int nf = -1, nn = kBlock;
               if (pers)
               {
-                if ((unsigned)(pw.spec >> 32) == pw.seq + 2u)
-                  nf = (int)(unsigned)pw.spec;
+                unsigned po;
+                int pn;
+                if (pw.peek(po, pn))
+                  nf = (int)po, nn = pn;
               }
               else if (f0 + kBlock < a.n_frames)
               {
@@ -1501,8 +1504,10 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
         int nf = -1, nn = kBlock;
         if (pers)
         {
-          if ((unsigned)(pw.spec >> 32) == pw.seq + 2u)
-            nf = (int)(unsigned)pw.spec;
+          unsigned po;
+          int pn;
+          if (pw.peek(po, pn))
+            nf = (int)po, nn = pn;
         }
         else if (f0 + kBlock < a.n_frames)
         {
@@ -1628,7 +1633,7 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
     bool more;
     if (pers)
     {
-      more = pw.next(a.ps, (int)blockIdx.x, cmd_off); // false: ring empty, leave
+      more = pw.next(a.ps, (int)blockIdx.x, cmd_off, cmd_n); // false: ring empty, leave
       f0 = (int)cmd_off;
     }
     else
