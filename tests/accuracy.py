@@ -69,13 +69,14 @@ def inputs(amplitude):
     return x
 
 
-def run_oracle(model, fast_tanh, x, real, ratio=None):
-    """`model`: a fixture's name or a parsed .nam document. Every stream from Reset(prewarm=True), 64-frame calls."""
+def run_oracle(model, fast_tanh, x, real, ratio=None, luts=None):
+    """`model`: a fixture's name or a parsed .nam document. Every stream (x[s]: [frames] or [in_channels, frames]) from
+    Reset(prewarm=True), 64-frame calls. `luts`: lookup-table activations, as get_dsp takes them."""
     j = nam_oracle.validate_nam_file(model_path(model)) if isinstance(model, str) else model
     dt = np.float64 if real == "f64" else np.float32
     out = []
     for s in range(x.shape[0]):
-        m = nam_oracle.load_nam_json(j, fast_tanh=fast_tanh, real=real)
+        m = nam_oracle.load_nam_json(j, fast_tanh=nam_oracle.LoadMode(fast_tanh, luts) if luts else fast_tanh, real=real)
         if ratio is not None:
             m.SetSlimmableSize(ratio)
         m.Reset(SR, BLOCK, prewarm=True)

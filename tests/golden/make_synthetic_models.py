@@ -81,10 +81,11 @@ def build(name, arrays, seed):
     return len(weights)
 
 
-def build_general(name, in_channels, arrays, post_head, seed, gain=0.9):
+def build_general(name, in_channels, arrays, post_head, seed, gain=0.9, path=None):
     """Plain (ungated, no FiLM) WaveNet with an optional post-stack head and any channel counts.
     arrays: (channels, dilations, activation, head_size, head_bias); post_head: dict or None
-    (model.cpp:21-103: repeat activation -> Conv1D(kernel_sizes[i]) with bias, `channels` wide inside)."""
+    (model.cpp:21-103: repeat activation -> Conv1D(kernel_sizes[i]) with bias, `channels` wide inside).
+    path: where to write it instead of the fixtures' directory."""
     rng = np.random.default_rng(seed)
     layers, weights = [], []
 
@@ -121,7 +122,7 @@ def build_general(name, in_channels, arrays, post_head, seed, gain=0.9):
         config["in_channels"] = in_channels
     model = dict(version="0.5.4", architecture="WaveNet", config=config,
                  metadata=dict(name=name, note="synthetic test fixture (seeded random weights)"), weights=weights, sample_rate=48000)
-    with open(os.path.join(HERE, "models", name + ".nam"), "w") as f:
+    with open(path or os.path.join(HERE, "models", name + ".nam"), "w") as f:
         json.dump(model, f)
     return len(weights)
 
@@ -400,9 +401,38 @@ def add_post_head(m, rng):
     return m
 
 
-def write_featured(path, seed, wr_shapes=False, post_head=False):
+def weight_documents(d):
+    """Every (sub)document of .nam document `d` that carries a non-empty "weights" list, outermost first: the model itself,
+    a nested condition_dsp, the submodels of a container."""
+    found = []
+    if isinstance(d, dict):
+        if isinstance(d.get("weights"), list) and d["weights"]:
+            found.append(d)
+        for v in d.values():
+            found += weight_documents(v)
+    elif isinstance(d, list):
+        for v in d:
+            found += weight_documents(v)
+    return found
+
+
+def apply_gain(m, gain):
+    """Every weight of every "weights" list of `m` (nested condition_dsp and post-stack head included) times `gain`, rounded
+    to float32 — except the trailing head_scale of each WaveNet list: that one is compiled into nam_wn_reg_kernel's per-model
+    code object (plan_wr.cpp: WrShapeSet::header_text prints each op's scale), every other weight is data. gain 1: untouched."""
+    if gain == 1:
+        return m
+    for d in weight_documents(m):
+        keep = 1 if d.get("architecture") == "WaveNet" else 0
+        w = d["weights"]
+        d["weights"] = [float(np.float32(np.float32(v) * np.float32(gain))) for v in w[:len(w) - keep]] + w[len(w) - keep:]
+    return m
+
+
+def write_featured(path, seed, wr_shapes=False, post_head=False, gain=1.0):
     """Seeded feature-rich model -> `path`; returns the model dict. post_head: with a random post-stack head (drawn from
-    a generator of its own: the arrays of a seed are the same with and without it)."""
+    a generator of its own: the arrays of a seed are the same with and without it). gain: see apply_gain (the gains that
+    make these models react to their weights are tests/golden/featured_live.json, written by tests/model_teeth.py)."""
     rng = np.random.default_rng(seed)
     while True:
         try:
@@ -412,6 +442,7 @@ def write_featured(path, seed, wr_shapes=False, post_head=False):
             continue
     if post_head:
         add_post_head(m, np.random.default_rng(seed + 50_000))
+    apply_gain(m, gain)
     with open(path, "w") as f:
         json.dump(m, f)
     return m

@@ -13,6 +13,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests", "golden
 import neuralampmodelercore_amd as nam
 import make_synthetic_models as msm
 import bank_wr_models
+import model_teeth
 
 
 def _load(job):
@@ -47,6 +48,15 @@ def main():
             p = os.path.join(tmp, f"featured_{seed}.nam")
             msm.write_featured(p, 7000 + seed, wr_shapes=bool(seed % 2), post_head=seed >= 40)
             jobs.append((p, seed % 3 == 0))
+        # tests/test_gpu_accuracy_breadth.py: the same models times their live gains run on the code objects above (the gain
+        # leaves the header's text alone: tests/test_model_teeth.py), but also in the OTHER tanh mode where they have a Tanh,
+        # Sigmoid or SiLU; and one generated fixture
+        for row in model_teeth.live_rows():
+            p = os.path.join(tmp, f"live_{row['seed']}.nam")
+            if model_teeth.has_smooth_activation(model_teeth.featured(row["seed"], row["gain"], p)):
+                jobs.append((p, not model_teeth.fast_tanh_of(row["seed"])))
+        p = model_teeth.write_fixture(model_teeth.POSTHEAD_LIVE, os.path.join(tmp, model_teeth.POSTHEAD_LIVE + ".nam"))
+        jobs += [(p, False), (p, True)]
         # tests/test_bank_wr_abi.py, tests/test_gpu_bank_wr.py: the bank members they write (the same files: the cache key is the
         # generated header's text — shapes, offsets, head scales —, not the path)
         written = bank_wr_models.write_all(tmp)
