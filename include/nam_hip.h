@@ -390,7 +390,11 @@ NAM_HIP_API int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* cons
  * device-memory ring, stored by the host itself when the call's stream is idle, else by hipStreamWriteValue64 on that
  * stream, so it is ordered behind whatever produced the input there — for as long as the next command is already there
  * when a buffer is finished, and leaves as soon as the ring is empty (a device-wide synchronize never waits for a
- * session; the next call starts the launch again). What a launch per buffer pays on top of the computation (dispatch,
+ * session; the next call starts the launch again). A launch that serves HOST buffers — tickets, or blocking *_f32 / *_f64 calls
+ * that come back to back (the previous one returned less than 50 us ago) — stores one completion word per command instead, so the
+ * call waits for its own buffer only, and lingers for the next one for a bounded time (200 us: NAM_HIP_TICKET_LINGER_US,
+ * NAM_HIP_BLOCKING_LINGER_US; 0 = never; a device-wide synchronize then waits for the linger at most): on every session kernel,
+ * the pipeline kernels and nam_wn_reg_kernel / the LSTM kernels alike. What a launch per buffer pays on top of the computation (dispatch,
  * cold prologue, state in and out: 4-12 us) is paid once per burst.
  * Consecutive calls must address the same resident window (d_in / d_out of the first call plus a common frame offset,
  * same frame_stride, offsets of any alignment; device memory or host-mapped memory); anything else — another window, Reset,
@@ -424,14 +428,16 @@ NAM_HIP_API int nam_hip_batch_flush(nam_hip_batch* batch, void* hip_stream);
  * In persistent mode (nam_hip_batch_set_persistent) buffers are commands of the session — of any length on nam_wn_reg_kernel and
  * the LSTM kernels, of a multiple of 64 frames on the pipeline kernels (another length there is rendered at once by plain
  * launches and handed out by the wait) —, the
- * input written through the PCIe window, the output stored to host memory by the resident launch itself — nam_a1_q_kernel
- * and nam_kq_kernel publish every command, so a wait returns while the launch runs on with the buffers behind it; other
- * kernels' tickets complete when the launch has drained its ring. (The pipeline of nam_a1_q_kernel holds five to six
+ * input written through the PCIe window, the output stored to host memory by the resident launch itself — every session
+ * kernel (nam_a1_q_kernel, nam_kq_kernel, nam_wn_reg_kernel in all its forms, nam_lstm_row_kernel, nam_lstm_wide_kernel)
+ * publishes every command, so a wait returns when the ticket's own last command is through, while the launch runs on with the
+ * buffers behind it. (The pipeline of nam_a1_q_kernel holds five to six
  * 64-frame buffers at a time: keep at least eight in flight at that size, four at 256 frames.) Outside persistent mode: pinned staging, copies and the
  * launch enqueued on the batch's stream, an event behind them. Control calls (Reset, SetSlimmableSize, set_kernel,
  * synchronize) complete the tickets in flight first; their outputs stay available to wait. A ticket session's launch
- * looks for the next buffer for 200 us before it leaves (NAM_HIP_TICKET_LINGER_US; it holds its CUs meanwhile). The blocking process calls
- * may be mixed in (tickets in flight complete first). */
+ * looks for the next buffer for 200 us before it leaves (NAM_HIP_TICKET_LINGER_US; it holds its CUs meanwhile) when all its
+ * workgroups are on the chip at once; a batch of more streams than that runs its session in turns, publishes every command all
+ * the same and leaves whenever the ring is empty. The blocking process calls may be mixed in (tickets in flight complete first). */
 #define NAM_HIP_PIPE_SLOTS 16
 NAM_HIP_API int nam_hip_batch_submit_f32(nam_hip_batch* batch, const float* in, int n_frames, int64_t* out_ticket);
 NAM_HIP_API int nam_hip_batch_wait_f32(nam_hip_batch* batch, int64_t ticket, float* out);

@@ -273,6 +273,7 @@ struct PersistSession
   double t_poll = 0, t_out = 0, t_in = 0, t_cmd = 0, t_poll_max = 0, t_out_max = 0, t_in_max = 0, t_cmd_max = 0; // us (NAM_HIP_SESSION_STATS)
   MappedBuf<long long> why; // (NAM_HIP_SESSION_STATS) per workgroup: reason << 56 | grace loop << 48 | all-through count << 24 | own count
   unsigned long long n_waits = 0, n_polls = 0; // ticket waits, looks at the buffer's completion word
+  unsigned long long n_publishing = 0, n_lingering = 0; // launches that publish every command; those of them that linger for the next one
   unsigned epoch = 0; // counts session starts (a ticket of an earlier session is complete: sessions end flushed)
   // Burst lengths (commands between two whole flushes) of this session, newest first; ~0u = not seen yet. A host that flushes after
   // every buffer or two (a device-resident real-time chain: process_device + flush per 64 .. 256 frames) waits for the FIRST buffer of
@@ -284,7 +285,8 @@ struct PersistSession
   bool short_bursts() const { return bursts[0] <= 4u && bursts[1] <= 4u && bursts[2] <= 4u; }
   bool one_buffer_bursts() const { return bursts[0] == 1u && bursts[1] == 1u && bursts[2] == 1u; } // (nam_wn_reg_kernel: one wave per stream then)
   EventOwner retired; // the completion signal of the session's latest launch (kernels.h: LaunchStream), recorded by the dispatch itself
-  bool cmd_done_published = false; // the running launch stores p_cmd_done behind every command's results (A1Args::p_out_host == 2); p_prog stays ring bookkeeping every 16 commands
+  bool cmd_done_published = false; // the running launch stores p_cmd_done behind every command's results (A1Args::p_out_host == 2; PersistArgs::cmd_done); p_prog stays ring bookkeeping every 16 commands
+  bool all_resident = false; // every workgroup of the latest launch is on the chip at once (persist_launch; session_lingers): it need not take turns
 };
 
 // One buffer in flight between nam_hip_batch_submit_f32 and nam_hip_batch_wait_f32
@@ -486,6 +488,7 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
 WrGroupList wr_groups(nam_hip_batch* b);
 int launch_wr_all(nam_hip_batch* b, const WrGroupList& gs, const float* d_in, float* d_out, int n_frames, long io_stride,
                   hipStream_t s, const LaunchContext& ctx);
+bool wr_session_all_resident(nam_hip_batch* b, const WrGroupList& gs, const LaunchContext& ctx);
 int kernel_for_launch(const nam_hip_batch* b, const WidthGroup& g, int n_frames);
 int launch_group(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n, const float* d_in, float* d_out,
                  int n_frames, long io_stride, hipStream_t s, const LaunchContext& ctx);
@@ -570,9 +573,11 @@ inline int session_linger_ticks(const nam_hip_batch* b)
 // Whether the session's running launch lingers for the next command instead of leaving when the ring is empty (A1Args::p_linger):
 // it publishes every command, the host can store its "leave" word itself, and every workgroup is on the chip at once (more
 // workgroups than CUs take turns: the ones on the chip must leave when the ring is empty). The host and the resident kernel must agree.
+// PersistSession::all_resident is persist_launch's answer for the launch it started: one workgroup per CU for the pipeline kernels,
+// launch_policy.h: launch_all_resident for nam_wn_reg_kernel (the wavefront form actually launched) and the two LSTM kernels.
 inline bool session_lingers(const nam_hip_batch* b)
 {
-  return b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.n_wg <= b->n_cus;
+  return b->ps.cmd_done_published && b->ps.host_store_ok && b->ps.all_resident;
 }
 
 inline double stat_now_us()

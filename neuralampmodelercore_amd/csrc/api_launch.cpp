@@ -179,6 +179,15 @@ PersistArgs persist_args(const nam_hip_batch* b, const LaunchContext& ctx)
   pa.seq0 = b->ps.seq0;
   pa.cmd0 = b->ps.cmd0;
   pa.grace = b->ps.grace;
+  if (b->ps.cmd_done_published)
+  {
+    // the launch publishes every command (persist_launch decided), and lingers when the session does — beyond a microsecond,
+    // as A1Args::p_linger counts (NAM_HIP_TICKET_LINGER_US = 0 or 1: the launch leaves as promptly as any other)
+    const int ticks = session_lingers(b) ? session_linger_ticks(b) : 0;
+    pa.linger = ticks > 100 ? ticks : 0;
+    pa.cmd_count = b->ps.d_cmd_count.get();
+    pa.cmd_done = b->ps.cmd_done.dev();
+  }
   return pa;
 }
 
@@ -203,6 +212,49 @@ static void session_args(const nam_hip_batch* b, const LaunchContext& ctx, A1Arg
   a.p_cmd_done = b->ps.cmd_done.dev();
 }
 
+// What launch_policy.h: wr_launch_shape is asked about a launch of nam_wn_reg_kernel over these groups (launch_wr; persist_launch
+// asks the same question ahead of a session's launch: wr_session_all_resident)
+static WrShapeQuery wr_shape_query(const nam_hip_batch* b, WidthGroup* const* groups, const int* counts, int n_groups, int n_frames,
+                                   const LaunchContext& ctx, int dense_forms)
+{
+  WrShapeQuery q;
+  q.can_split = q.can_split4 = true;
+  for (int k = 0; k < n_groups; k++)
+  {
+    const WrPlan& w = groups[k]->plan->wr;
+    q.can_split = q.can_split && w.split_op[3] >= 1 && w.split_op[3] < (int)w.ops.size();
+    q.can_split4 = q.can_split4 && w.split_op[0] >= 1 && w.split_op[0] < w.split_op[1] && w.split_op[1] < w.split_op[2]
+                   && w.split_op[2] < (int)w.ops.size();
+    q.total += counts[k];
+    q.lds_bytes = std::max(q.lds_bytes, w.lds_bytes);
+  }
+  // (a session whose caller flushes after EVERY buffer is a series of one-buffer calls: nothing for a pipeline to overlap)
+  const bool session = ctx.session_kind != PERSIST_NONE;
+  const bool one_buffer_bursts = session && !b->pipe_session && b->ps.one_buffer_bursts();
+  q.cus = b->n_cus;
+  q.max_stages = b->wr_max_stages;
+  q.dense_forms = dense_forms;
+  q.multi_buffer = !b->no_pipe && !ctx.hints.one_buffer_call && !one_buffer_bursts && (session || n_frames > kBlock);
+  return q;
+}
+
+// Will the session launch that launch_wr_all(b, gs, .., ctx) starts hold every workgroup on the chip at once, in the wavefront form
+// it is started in (launch_policy.h: wr_all_resident)? The same query, the same answer: the host and the launch agree on lingering.
+bool wr_session_all_resident(nam_hip_batch* b, const WrGroupList& gs, const LaunchContext& ctx)
+{
+  if (gs.n <= 0)
+    return false;
+  int counts[kWrMaxGroups];
+  for (int k = 0; k < gs.n; k++)
+    counts[k] = (int)gs.g[k]->streams.size();
+  const std::string& module = gs.g[0]->plan->wr.jit_module;
+  const WrJitFunctions jit = module.empty() ? WrJitFunctions() : wr_jit_functions(module, b->device);
+  if (jit.rc != NAM_HIP_OK)
+    return false; // (the launch itself reports it)
+  const WrShapeQuery q = wr_shape_query(b, gs.g, counts, gs.n, kBlock, ctx, jit.dense_forms());
+  return wr_all_resident(q, wr_launch_shape(q));
+}
+
 // nam_wn_reg_kernel over up to kWrMaxGroups width groups in ONE launch (kernels.h: WrArgs): group k's `counts[k]` streams
 // (`maps[k]`: position -> stream index, nullptr = identity) become consecutive workgroups.
 int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* maps, const int* counts, int n_groups,
@@ -211,8 +263,8 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
   // 1. the arguments, from the groups
   WrArgs a;
   std::memset(&a, 0, sizeof(a));
-  int total = 0, lds_bytes = 0;
-  bool layers = false, runs = false, rt_layers = false, can_split = true, can_split4 = true;
+  int total = 0;
+  bool layers = false, runs = false, rt_layers = false;
   for (int k = 0; k < n_groups; k++)
   {
     WidthGroup& g = *groups[k];
@@ -241,11 +293,7 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
     for (int q = 0; q < 3; q++)
       G.split_op[q] = w.split_op[q];
     G.prog = w.program;
-    can_split = can_split && w.split_op[3] >= 1 && w.split_op[3] < (int)w.ops.size();
-    can_split4 = can_split4 && w.split_op[0] >= 1 && w.split_op[0] < w.split_op[1] && w.split_op[1] < w.split_op[2]
-                 && w.split_op[2] < (int)w.ops.size();
     total += counts[k];
-    lds_bytes = std::max(lds_bytes, w.lds_bytes);
   }
   a.n_groups = n_groups;
   a.in = d_in;
@@ -267,18 +315,7 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
     return jit.rc;
   // 2. how many wavefronts per stream, and which build of them (launch_policy.h): more than one only when the launch holds more
   // than one buffer
-  // (a session whose caller flushes after EVERY buffer is a series of one-buffer calls: nothing for a pipeline to overlap)
-  const bool session = ctx.session_kind != PERSIST_NONE;
-  const bool one_buffer_bursts = session && !b->pipe_session && b->ps.one_buffer_bursts();
-  WrShapeQuery q;
-  q.total = total;
-  q.lds_bytes = lds_bytes;
-  q.cus = b->n_cus;
-  q.max_stages = b->wr_max_stages;
-  q.can_split = can_split;
-  q.can_split4 = can_split4;
-  q.dense_forms = jit.dense_forms();
-  q.multi_buffer = !b->no_pipe && !ctx.hints.one_buffer_call && !one_buffer_bursts && (session || n_frames > kBlock);
+  const WrShapeQuery q = wr_shape_query(b, groups, counts, n_groups, n_frames, ctx, jit.dense_forms());
   const WrLaunchShape shape = wr_launch_shape(q);
   const int stages = shape.stages;
   if (q.multi_buffer)
@@ -290,7 +327,7 @@ int launch_wr(nam_hip_batch* b, WidthGroup* const* groups, const int* const* map
     b->wr_last_dense = shape.dense;
   }
   // 3. the launch, as `stages` wavefronts per stream
-  lds_bytes = shape.lds_bytes;
+  const int lds_bytes = shape.lds_bytes;
   if (stages == 2) // (the kernels read a two-wave launch's cut from [1]: WrGroup::split_op)
     for (int k = 0; k < n_groups; k++)
       a.g[k].split_op[1] = groups[k]->plan->wr.split_op[3];

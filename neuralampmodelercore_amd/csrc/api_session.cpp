@@ -91,27 +91,36 @@ static int persist_launch(nam_hip_batch* b, CallHints hints, int grace_us, long 
   for (int w = 0; w < ps.n_wg; w++)
     __atomic_and_fetch(&ps.words.host()[ps.done_off + w], 0x7fffffffu, __ATOMIC_RELAXED);
   ps.outstanding = true;
-  // ticketed host buffers: nam_a1_q_kernel / nam_kq_kernel store the per-buffer completion word (p_cmd_done) behind every
-  // command's results (their p_prog, like every kernel's, is ring bookkeeping every 16 commands — never a completion signal;
-  // the other kernels' tickets complete when the launch has left)
+  // (a session of the interleaved-frame family runs that family: family_for_launch; `retired`: the launch's own completion signal, what persist_wait waits on)
+  const LaunchContext ctx{ps.kind, hints, ps.retired.get()};
+  // ticketed host buffers: the session kernels store the per-buffer completion word (A1Args::p_cmd_done; PersistArgs::cmd_done:
+  // nam_wn_reg_kernel and the two LSTM kernels) behind every command's results (their p_prog is ring bookkeeping every 16
+  // commands — never a completion signal); a session on a device window publishes nothing and completes when the launch has left
   {
     // ... and, round 6, a BLOCKING host caller that hands one buffer in after the other (nam_hip_batch::blocking_linger):
     // nam_a1_p4_kernel — what the official topology's short blocking calls run — publishes the word too, so the call waits
     // for its own command and the next call finds the launch still there (no launch, no prologue, no retirement per call)
-    ps.cmd_done_published = (b->pipe_session || b->blocking_linger) && ps.out_is_host && !b->no_pipe
-                        && (ps.kind == PERSIST_A1_P2 || ps.kind == PERSIST_KQ); // (pipe_session: never the short-burst rule)
+    // (NAM_HIP_MAX_STAGES=1 rules out the PIPELINE kernels' publishing forms; the one-wavefront kernels publish in every form)
+    ps.cmd_done_published = (b->pipe_session || b->blocking_linger) && ps.out_is_host
+                        && (persist_any_length(ps.kind) || (!b->no_pipe && (ps.kind == PERSIST_A1_P2 || ps.kind == PERSIST_KQ))); // (pipe_session: never the short-burst rule)
+    // every workgroup on the chip at once? One per CU for the pipeline kernels; several for the others (launch_policy.h), for
+    // nam_wn_reg_kernel in the wavefront form this very launch takes. A launch that runs in turns publishes but never lingers.
+    ps.all_resident = ps.kind == PERSIST_WN_REG     ? wr_session_all_resident(b, wr_groups(b), ctx)
+                      : ps.kind == PERSIST_LSTM_ROW  ? launch_all_resident(ps.n_wg, kLstmRowResidentPerCu, b->n_cus)
+                      : ps.kind == PERSIST_LSTM_WIDE ? launch_all_resident(ps.n_wg, kLstmWideResidentPerCu, b->n_cus)
+                                                     : ps.n_wg <= b->n_cus;
     // ... and linger: a workgroup that finds itself up to date when a launch starts (another one's backlog was the reason for
     // the launch) must not leave at once — the commands to come would find it gone, and the rest of the launch would have to
     // linger and leave before the next launch could pick it up again
+    ps.n_publishing += ps.cmd_done_published ? 1 : 0;
     if (session_lingers(b))
     {
+      ps.n_lingering += session_linger_ticks(b) > 100 ? 1 : 0; // (as the kernels count: beyond a microsecond)
       ps.grace = std::max(ps.grace, session_linger_ticks(b));
       // "a workgroup of this launch has left" (il_common.h: session_leaving; p_cmd_count[mask + 2] = [kPRing + 1]): none yet
       NAM_HIP_CHECK(hipMemsetAsync(ps.d_cmd_count.get() + kPRing + 1, 0, sizeof(unsigned), ps.kstream.get()));
     }
   }
-  // (a session of the interleaved-frame family runs that family: family_for_launch; `retired`: the launch's own completion signal, what persist_wait waits on)
-  const LaunchContext ctx{ps.kind, hints, ps.retired.get()};
   return ps.kind == PERSIST_WN_REG
            ? launch_wr_all(b, wr_groups(b), ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get(), ctx)
            : launch_group(b, g, nullptr, b->n_streams, ps.in_base, ps.out_base, kBlock, ps.stride, ps.kstream.get(), ctx);

@@ -759,6 +759,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BANK ? 8 : 1
       }
     if (pers)
     {
+      PersistWave::complete(a.ps, pw.seq); // (once per workgroup: every stream of the wavefront has stored the command's output)
       if (!pw.next(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
         break; // ring empty: leave
       f0 = (int)cmd_off;
@@ -994,6 +995,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     }
     if (pers)
     {
+      PersistWave::complete(a.ps, pw.seq); // (once per workgroup: every stream of the wavefront has stored the command's output)
       if (!pw.next(a.ps, (int)blockIdx.x, cmd_off, cmd_n))
         break; // ring empty: leave
       f0 = (int)cmd_off;

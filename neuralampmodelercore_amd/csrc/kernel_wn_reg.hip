@@ -1626,6 +1626,8 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
       kbuf++;
       if (S > 0)
       {
+        if (pers && S == NST - 1) // (a program ends in WR_OUTPUT: this wave stored the command's output)
+          PersistWave::complete(a.ps, done);
         done++; // (the next buffer comes out of the queue)
         continue;
       }
@@ -1633,6 +1635,8 @@ __device__ __forceinline__ void wn_reg_body(const WrArgs& a)
     bool more;
     if (pers)
     {
+      if constexpr (NST == 1)
+        PersistWave::complete(a.ps, pw.seq); // (the one wave: its output stores are behind it)
       more = pw.next(a.ps, (int)blockIdx.x, cmd_off, cmd_n); // false: ring empty, leave
       f0 = (int)cmd_off;
     }

@@ -89,6 +89,13 @@ struct PersistArgs
   long long seq0 = -1; // >= 0: every workgroup has consumed exactly this many commands (cons is not read) ...
   unsigned long long cmd0 = 0; // ... and this is the next command (the ring is not read for it)
   int grace = 0; // ticks (100 MHz) a fresh launch looks for its first command before it leaves again
+  // Per-command completion, as A1Args::p_cmd_count / p_cmd_done / p_linger (persist_wave.h: complete, wait_command).
+  // cmd_done == nullptr: the launch does not publish — none of the three is read, and the kernels run what they always ran.
+  int linger = 0; // ticks (100 MHz) a workgroup that finds the ring empty looks for the next command before it leaves; 0 = it leaves at once
+  unsigned* cmd_count = nullptr; // device memory: [c & ring_mask] workgroups through command c (zero between uses); [ring_mask + 1] the highest
+                                 // command every workgroup is through; [ring_mask + 2] workgroups of this launch that have left (the host clears it per launch)
+  unsigned* cmd_done = nullptr; // host-mapped: [c & ring_mask] = c + 1, stored by the last workgroup through command c behind everybody's results
+  // (the host's "leave" word of a lingering launch is ring[ring_mask + 1]; the launch's workgroup count is its grid)
 };
 
 // I/O convention for every kernel: planar float32 in HBM,

@@ -31,6 +31,20 @@ inline int wr_stream_bound(int lds_bytes, int cus)
   return kPersistTurns * wr_workgroups_per_cu(lds_bytes, 1, 1) * std::max(cus, 1);
 }
 
+// Are all `n_wg` workgroups of a launch on the chip at once, when a CU holds `per_cu` of them? What a session's launch needs to
+// LINGER (persist_wave.h: wait_command): a workgroup that waits for a slot on a CU consumes nothing while the resident ones wait
+// for it, so a launch that runs in turns must leave when its ring is empty. The pipeline kernels' sessions have one workgroup per
+// CU (api_internal.h: session_lingers); the one-wavefront-per-workgroup kernels have several, hence this instead of n_wg <= cus.
+inline bool launch_all_resident(int n_wg, int per_cu, int cus)
+{
+  return n_wg >= 1 && per_cu >= 1 && (long)n_wg <= (long)per_cu * std::max(cus, 1);
+}
+// Workgroups (one wavefront each) of nam_lstm_row_kernel / nam_lstm_wide_kernel a CU holds at once WHATEVER registers the
+// instantiation was allocated: one per SIMD (a wavefront may hold a SIMD's whole register file; their LDS, under 12 KB, never
+// binds). persist_kind admits more streams than that (the row kernel: eight workgroups per CU); those sessions run in turns.
+constexpr int kLstmRowResidentPerCu = 4;
+constexpr int kLstmWideResidentPerCu = 4;
+
 struct WrShapeQuery
 {
   int total = 0; // workgroups (streams) of the launch
@@ -105,6 +119,12 @@ inline WrLaunchShape wr_launch_shape(const WrShapeQuery& q)
   }
   out.lds_bytes += (out.stages - 1) * kWrQueueBytes;
   return out;
+}
+
+// ... and whether the launch of that shape holds all its workgroups on the chip at once (wr_duration's `turns` == 1 for the form chosen)
+inline bool wr_all_resident(const WrShapeQuery& q, const WrLaunchShape& shape)
+{
+  return launch_all_resident(q.total, wr_workgroups_per_cu(shape.lds_bytes, shape.stages, shape.dense ? 2 : 1), q.cus);
 }
 
 } // namespace api

@@ -431,6 +431,8 @@ void nam_hip_batch_destroy(nam_hip_batch* batch)
   if (stats_on() && batch->ps.n_starts)
     std::fprintf(stderr, "nam_hip session: %llu starts, %llu launches (%llu from a wait / flush), %llu commands stored by the host, %llu through the stream\n",
                  batch->ps.n_starts, batch->ps.n_launches, batch->ps.n_flush_relaunches, batch->ps.n_host_doorbells, batch->ps.n_stream_doorbells);
+  if (stats_on() && batch->ps.n_starts)
+    std::fprintf(stderr, "nam_hip session launches: %llu publish every command, %llu of them linger\n", batch->ps.n_publishing, batch->ps.n_lingering);
   if (stats_on() && batch->ps.n_waits)
   {
     std::fprintf(stderr, "nam_hip tickets: %llu waits, %.1f looks at the completion word each\n", batch->ps.n_waits, (double)batch->ps.n_polls / batch->ps.n_waits);

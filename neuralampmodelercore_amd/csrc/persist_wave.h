@@ -6,6 +6,14 @@
 // when a buffer is finished, and leaves as soon as the ring is empty (it never waits unboundedly: a device-wide
 // synchronize must not depend on a command arriving). A wavefront of its own needs no agreement step: every lane
 // reads the same ring word.
+//
+// A session whose results go to host memory for ticketed buffers or back-to-back blocking calls PUBLISHES every command
+// (PersistArgs::cmd_done != nullptr): the workgroup that has stored command c's output counts itself in, the last one through
+// stores c + 1 to the host's completion word of the command (complete()), so a wait returns while the launch runs on. Such a
+// launch may also LINGER (PersistArgs::linger > 0): a workgroup that finds the ring empty waits for the next command for a
+// bounded time under the rules of the pipeline kernels' sessions (wait_command() mirrors il_common.h: session_wait_command,
+// leaving() mirrors session_leaving) instead of leaving at once, so the next buffer finds the launch still there. A launch
+// that does not publish (device windows, hosts that flush) takes none of these paths: one wavefront-uniform test per command.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -52,7 +60,15 @@ struct PersistWave
     }
     seq = (unsigned)__builtin_amdgcn_readfirstlane((int)p.cons[wg]);
     unsigned long long v = ring_load(p, seq);
-    if (p.grace > 0 && !is_command(v, seq + 1))
+    if (p.linger > 0)
+    {
+      // a launch that lingers (the host set grace >= linger): a workgroup that finds itself up to date — another one's backlog
+      // was the reason for the launch — stays for the commands to come, under wait_command's rules
+      v = wait_command(p, seq + 1, v, (long long)p.grace);
+      if (!is_command(v, seq + 1))
+        leaving(p);
+    }
+    else if (p.grace > 0 && !is_command(v, seq + 1))
     {
       // started right behind a stream-ordered command store on another hardware queue: look for a bounded time
       const long long t_end = (long long)wall_clock64() + p.grace;
@@ -68,6 +84,46 @@ struct PersistWave
   }
   // while a buffer is being processed: request the next command (consumed by next())
   __device__ __forceinline__ void look_ahead(const PersistArgs& p) { spec = ring_load(p, seq + 1); }
+  // A lingering launch waits for command `tag` (ring slot of sequence number tag - 1; `v`: what the slot held at the last look)
+  // for `window` ticks of the 100 MHz clock. The twin of il_common.h: session_wait_command for one-wavefront workgroups, rule for
+  // rule: the host's "leave" word behind the ring (= the session's command count: nothing follows) ends the wait at once; when
+  // the window has passed the workgroup stays only while another workgroup is BEHIND it (cmd_count[mask + 1]: the highest command
+  // every workgroup is through) and no workgroup of this launch has left (cmd_count[mask + 2]); 20 ms at the very most, so a
+  // device-wide synchronize never depends on a command arriving. Every lane reads the same words: the branches are uniform.
+  static __device__ __forceinline__ unsigned long long wait_command(const PersistArgs& p, const unsigned tag, unsigned long long v, const long long window)
+  {
+    if (is_command(v, tag) || window <= 0)
+      return v;
+    const long long t0 = (long long)wall_clock64(), t_end = t0 + window, t_cap = t0 + 2000000ll;
+    for (;;)
+    {
+      __builtin_amdgcn_s_sleep(16);
+      v = ring_load(p, tag - 1u);
+      if (is_command(v, tag))
+        break;
+      const long long now = (long long)wall_clock64();
+      const unsigned gone = (unsigned)__builtin_amdgcn_readfirstlane(
+        (int)(unsigned)__hip_atomic_load(p.ring + p.ring_mask + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+      if (gone == tag - 1u)
+        break;
+      if (now >= t_end)
+      {
+        const unsigned all_done = (unsigned)__builtin_amdgcn_readfirstlane(
+          (int)__hip_atomic_load(p.cmd_count + p.ring_mask + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        const unsigned left = (unsigned)__builtin_amdgcn_readfirstlane(
+          (int)__hip_atomic_load(p.cmd_count + p.ring_mask + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (now >= t_cap || (int)(all_done - (tag - 1u)) >= 0 || left != 0u)
+          break;
+      }
+    }
+    return v;
+  }
+  // ... and a workgroup of a lingering launch that leaves says so (one lane; the twin of il_common.h: session_leaving)
+  static __device__ __forceinline__ void leaving(const PersistArgs& p)
+  {
+    if (p.linger > 0 && (threadIdx.x & 63u) == 0u)
+      __hip_atomic_fetch_add(p.cmd_count + p.ring_mask + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   // a buffer is finished: the next command, or false when the ring is empty (the caller then leaves)
   __device__ __forceinline__ bool next(const PersistArgs& p, int wg, unsigned& frame_off, int& n_frames)
   {
@@ -76,10 +132,44 @@ struct PersistWave
       __hip_atomic_store(p.prog + wg, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     unsigned long long v = spec;
     if (!is_command(v, seq + 1))
+    {
       v = ring_load(p, seq); // the early look missed: once more, now
+      if (p.linger > 0) // (wavefront-uniform) ... and, a launch that lingers, for a while
+      {
+        v = wait_command(p, seq + 1, v, (long long)p.linger);
+        if (!is_command(v, seq + 1))
+          leaving(p);
+      }
+    }
     frame_off = (unsigned)v;
     n_frames = session::frames_of_hi((unsigned)(v >> 32));
     return is_command(v, seq + 1);
+  }
+  // Command number `c` (counted from 0: the one taken with seq == c) is finished and this workgroup's output of it is stored:
+  // publish it when the launch does that (wavefront-uniform test; called by the wavefront that stored the output). Results
+  // visible to the host first (system-scope release fence), then one lane counts the workgroup in (agent scope); the workgroup
+  // that finds everybody else there — with ONE workgroup that is the first through — zeroes the counter for the slot's next use,
+  // stores c + 1 to the host's completion word and raises "the highest command everybody is through" (wait_command's second rule).
+  static __device__ __forceinline__ void complete(const PersistArgs& p, unsigned c)
+  {
+    if (p.cmd_done == nullptr)
+      return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    const unsigned slot = c & (unsigned)p.ring_mask;
+    unsigned before = 0u;
+    if ((threadIdx.x & 63u) == 0u)
+      before = __hip_atomic_fetch_add(p.cmd_count + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((unsigned)__builtin_amdgcn_readfirstlane((int)before) == gridDim.x - 1u)
+    {
+      // (the others' fences stand in front of their counts: this one orders their results, seen through the counter, in front of the word)
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "");
+      if ((threadIdx.x & 63u) == 0u)
+      {
+        __hip_atomic_store(p.cmd_count + slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p.cmd_done + slot, c + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_fetch_max(p.cmd_count + p.ring_mask + 1, c + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
   }
   // results visible, then the consumed-command count: device copy for this workgroup's next launch, host copy (with
   // the "left" bit) for the host

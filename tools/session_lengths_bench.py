@@ -7,7 +7,8 @@ walking one window, a flush and a device synchronize behind each region (bank_be
 min, max over --runs timings of --regions regions), xRT, and — from a second, untimed pass of ONE region per length with
 NAM_HIP_SESSION_STATS=1 — the session starts / launches / commands of that region. 64 frames is in the list: the whole-buffer path,
 whose run-to-run spread (us_min .. us_max) is the margin for "level" when two commits are compared. Then the blocking host call
-(process()) at 32, 48 and 64 frames, 200 calls back to back (--frames / --host-frames choose other lengths; "" = none).
+(process()) at 32, 48 and 64 frames, 200 calls back to back, and tickets (submit / wait, 16 in flight) at 64 and 256 frames, 200 per
+timing (--frames / --host-frames / --ticket-frames choose other lengths; "" = none).
 
 Run the same file on two checkouts to compare them; every (config, pass) is a process of its own (the statistics switch is read
 once per process), one JSON line per row.
@@ -37,6 +38,9 @@ SLIM_RATIOS = (0.0, 0.34, 0.67, 1.0)
 FRAMES = (32, 48, 64, 96, 120, 240, 480)
 HOST_FRAMES = (32, 48, 64)
 REGION = 20  # calls between flushes
+TICKET_FRAMES = (64, 256)
+TICKET_DEPTH = 16  # tickets in flight (NAM_HIP_PIPE_SLOTS)
+TICKET_REGION = 200  # tickets per timing
 MAX_FRAMES = 480
 
 
@@ -54,7 +58,7 @@ def make_batch(nam, model, cfg):
     return b
 
 
-def child(config, stats, runs, regions, frames_list, host_frames_list):
+def child(config, stats, runs, regions, frames_list, host_frames_list, ticket_frames_list):
     import torch
     import neuralampmodelercore_amd as nam
     cfg = CONFIGS[config]
@@ -116,6 +120,37 @@ def child(config, stats, runs, regions, frames_list, host_frames_list):
         b.close()
         print("row-end", file=sys.stderr, flush=True)
         print("row: " + json.dumps(row), flush=True)
+    for frames in ticket_frames_list:
+        b = make_batch(nam, model, cfg)
+        x = (0.2 * np.random.default_rng(2).standard_normal((n, ic, frames))).astype(np.float32)
+        out = np.empty((n, model.NumOutputChannels(), frames), dtype=np.float32)
+        row = dict(config=config, model=cfg["model"], streams=n, frames=frames, path=f"tickets, {TICKET_DEPTH} in flight", kernel=b.kernel_name())
+
+        def feed(n_tickets):
+            inflight = []
+            for _ in range(n_tickets):
+                if len(inflight) == TICKET_DEPTH:
+                    b.wait(inflight.pop(0), out)
+                inflight.append(b.submit(x))
+            while inflight:
+                b.wait(inflight.pop(0), out)
+
+        if stats:
+            feed(TICKET_REGION)
+            row["stats_region_calls"] = TICKET_REGION
+        else:
+            feed(TICKET_REGION)
+            per_call = []
+            for _ in range(runs):
+                t0 = time.perf_counter()
+                feed(TICKET_REGION)
+                per_call.append((time.perf_counter() - t0) * 1e6 / TICKET_REGION)
+            med = statistics.median(per_call)
+            row.update(us_per_call_median=round(med, 3), us_min=round(min(per_call), 3), us_max=round(max(per_call), 3),
+                       xrt=round(xrt(n, frames, med)), runs=runs)
+        b.close()
+        print("row-end", file=sys.stderr, flush=True)
+        print("row: " + json.dumps(row), flush=True)
 
 
 def main():
@@ -125,12 +160,13 @@ def main():
     ap.add_argument("--regions", type=int, default=10)
     ap.add_argument("--frames", default=",".join(map(str, FRAMES)), help="device-resident call lengths")
     ap.add_argument("--host-frames", default=",".join(map(str, HOST_FRAMES)), help="blocking host call lengths")
+    ap.add_argument("--ticket-frames", default=",".join(map(str, TICKET_FRAMES)), help="ticket lengths (submit / wait, 16 in flight)")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--stats", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         return child(args.child, args.stats, args.runs, args.regions, [int(f) for f in args.frames.split(",") if f],
-                     [int(f) for f in args.host_frames.split(",") if f])
+                     [int(f) for f in args.host_frames.split(",") if f], [int(f) for f in args.ticket_frames.split(",") if f])
     for config in [int(c) for c in args.configs.split(",")]:
         rows = {}
         for stats in (False, True):
@@ -138,7 +174,7 @@ def main():
             if stats:
                 env["NAM_HIP_SESSION_STATS"] = "1"
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(config), "--runs", str(args.runs), "--regions", str(args.regions),
-                                "--frames", args.frames, "--host-frames", args.host_frames]
+                                "--frames", args.frames, "--host-frames", args.host_frames, "--ticket-frames", args.ticket_frames]
                                + (["--stats"] if stats else []), env=env, capture_output=True, text=True, timeout=900)
             if r.returncode != 0:
                 sys.stderr.write(r.stdout + r.stderr)
