@@ -341,7 +341,12 @@ NAM_HIP_API int nam_hip_batch_restart_streams(nam_hip_batch* batch, const int* s
  * NAM_HIP_ERR_INVALID_ARGUMENT, a message that names the field, and nothing changed: a blob of another model or whose member is
  * another model than the bank's; another payload geometry (a Linear batch of another max_frames class); a truncated or
  * corrupted blob; a blob whose WaveNet layout differs from what the destination's streams of that width hold ("reset first":
- * a freshly zeroed blob fits anywhere, and freshly zeroed streams take the blob's layout). */
+ * a freshly zeroed blob fits anywhere, and freshly zeroed streams take the blob's layout).
+ * A2 containers at mixed sizes in persistent mode (nam_hip_batch_set_persistent): an A2-Lite stream's blob is ALWAYS in
+ * nam_wn_reg_kernel's layout, whichever way the stream currently lives — get copies a zero-padded stream's rings out into that
+ * layout (the padded channels are dropped), set copies them in (the padded channels become zero) —, so the blob format, its size
+ * and where it may go (an all-Lite batch, a mixed one, persistent or not) do not depend on the batch it came from.
+ * nam_hip_batch_restart_streams works on either kind of stream of such a batch. */
 NAM_HIP_API int64_t nam_hip_batch_stream_state_size(const nam_hip_batch* batch, int stream);
 NAM_HIP_API int nam_hip_batch_get_stream_state(nam_hip_batch* batch, int stream, void* buf, int64_t capacity, int64_t* out_size);
 NAM_HIP_API int nam_hip_batch_set_stream_state(nam_hip_batch* batch, int stream, const void* buf, int64_t size);
@@ -349,7 +354,10 @@ NAM_HIP_API int nam_hip_batch_set_stream_state(nam_hip_batch* batch, int stream,
 /* SlimmableModel::SetSlimmableSize(val) for a subset of the streams (NAM/slimmable.h:23,
  * NAM/wavenet/slimmable.cpp:420-431,527-530): the listed streams switch to the sub-model of width
  * ratio_to_channels(ratio) and start from a freshly reset (and, if the batch was last reset with
- * prewarm, prewarmed) state, as the reference's rebuilt model does. stream_ids == NULL selects all. */
+ * prewarm, prewarmed) state, as the reference's rebuilt model does. stream_ids == NULL selects all.
+ * Every stream the call does not name keeps its state — also where the call mixes or un-mixes an A2 container's batch in
+ * persistent mode and those streams change the kernel they run on (nam_hip_batch_set_persistent): their histories are copied
+ * into the other kernel's layout, float for float. */
 NAM_HIP_API int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids, int n_ids, double ratio);
 
 /* DSP::process(NAM_SAMPLE** input, NAM_SAMPLE** output, int num_frames) — NAM/dsp.h:97,
@@ -406,6 +414,17 @@ NAM_HIP_API int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* cons
  * blocking *_f32 / *_f64 entry points, which do it) before consuming them.
  * Eligible: one width group on nam_a1_q_kernel / nam_a1_p4_kernel / nam_kq_kernel up to 8 streams per CU (beyond one per CU the workgroups
  * take turns on the chip); every group on nam_wn_reg_kernel up to 8 x min(4, 160 KB / LDS image) streams per CU (in turns too); small LSTMs.
+ * A SlimmableContainer of the A2 family (A2.nam: A2-Lite and A2-Full, submodels that differ in channel count only) whose streams
+ * are at MIXED sizes is eligible as ONE group on nam_kq_kernel, up to 8 streams per CU: while the mode is on, the narrower streams
+ * run zero-padded copies of their submodel (exact: zero weights and biases on the padded rows) next to the Full ones — one
+ * resident launch, one command ring; tickets, the blocking calls' linger, per-command completion and flush as on an all-Full
+ * batch, a length that is no multiple of 64 frames as on an all-Full batch too (one plain launch of nam_kt_mfma_kernel over every
+ * stream). All-Lite batches keep nam_wn_reg_kernel, all-Full ones nam_kq_kernel. The control calls that mix or un-mix a batch
+ * (this one, nam_hip_batch_set_slimmable_size, nam_hip_batch_set_stream_state, nam_hip_batch_reset, nam_hip_batch_set_kernel) move
+ * the state of the narrow streams they do NOT name between the two kernels' layouts — a copy of the same histories at the same
+ * ring positions, so those streams go on undisturbed; no process call ever does. Outside the mode such a batch launches per size,
+ * as ever. nam_hip_batch_kernel_name* answer nam_kq_kernel / nam_kt_mfma_kernel for such a batch whatever the sizes' shares: every
+ * stream runs them.
  * Returns 1 if the batch will use the mode, 0 if it is not eligible (the calls then launch as usual).
  * Allocation: this call and nam_hip_batch_reset — the non-real-time side of the reference's contract (NAM/dsp.h:163) — allocate
  * everything a session needs (command ring, completion words, its stream and events, the host windows of the blocking entry points);

@@ -57,7 +57,7 @@ bool host_mapped_applies(nam_hip_batch* b, int n_frames)
   if (kind == PERSIST_NONE || (n_frames % kBlock != 0 && !persist_any_length(kind))) // (a ragged length: only kernels that take a count per command)
     return false;
   for (auto& g0 : b->groups)
-    if (!g0.streams.empty() && g0.plan->arch == ARCH_WAVENET && g0.state_family >= 0 && g0.state_family != persist_family(b, g0))
+    if (group_state_in_play(b, g0) && g0.plan->arch == ARCH_WAVENET && g0.state_family >= 0 && g0.state_family != persist_family(b, g0))
       return false; // (the copying path reports the layout clash)
   return true;
 }

@@ -8,6 +8,7 @@
 //                     per-stream member binding
 //   launch_policy.h   nam_wn_reg_kernel's launch shape, workgroups per CU and stream bound: integers in, integers out (no HIP)
 //   linear_worklist.h the (column tile, submodel) work list of an all-Linear container's batch: assignment in, tables and extents out (no HIP)
+//   a2_transcode.h    an A2 container's narrow submodel between nam_wn_reg_kernel's state and the largest submodel's rings: the table, its check (no HIP)
 //   stream_state.h    one stream's state as a blob: header, encode, validate, the Linear ring's row arithmetic (no HIP)
 // No exception leaves these files (guarded); errors are codes + nam_hip_last_error.
 #pragma once
@@ -88,6 +89,14 @@ struct nam_hip_model
   std::vector<std::vector<int>> width_channels;
   std::vector<Plan> plans;
   int full_width = 0; // index of the full-size plan
+  // A container whose largest submodel is the topology nam_kq_kernel is compiled for and whose other submodels differ from it in
+  // channel count only (A2.nam: A2-Lite next to A2-Full; api_launch.cpp: build_model): per narrower submodel a SECOND plan,
+  // zero-padded onto the largest one's layout (plan_a1.cpp: build_a2_padded_plan), and the table between the submodel's own
+  // nam_wn_reg_kernel state and the padded rings (a2_transcode.h). [submodel]; the largest one's entries stay empty. Both vectors
+  // are empty unless EVERY narrower submodel has its pair: a batch at mixed sizes then runs persistent mode as one session.
+  std::vector<Plan> padded;
+  std::vector<A2Transcode> transcode;
+  bool a2_mix() const { return !padded.empty(); }
 
   bool slimmable() const { return spec->arch == ARCH_CONTAINER || (spec->arch == ARCH_WAVENET && spec->wavenet.slimmable); }
   int width_for_ratio(double ratio) const
@@ -211,6 +220,25 @@ struct LinearContainer
   DeviceBuf<int32_t> d_col_pair; // [caps.cols_pad]
   int hist_frames = 0, part_frames = 0, piece = 0;
   int pos = 0; // the ring row the next frame goes to (host state, as WidthGroup::lin_pos)
+};
+
+// A batch of an A2 container (nam_hip_model::a2_mix) whose streams are at MIXED sizes, in persistent mode: the
+// narrow streams live zero-padded in the largest submodel's state rows (`resident`: group[full_width].d_state holds EVERY stream's
+// rings; the narrow groups keep their membership, their own rows are stale) and the whole batch is one launch of the largest
+// submodel's kernels through their bank path — member = the stream's submodel, member full_width = the largest submodel's own
+// blob. Entered and left by control calls only (api_launch.cpp: a2mix_enter / a2mix_leave move the narrow streams' state with
+// nam_a2_transcode_kernel); outside persistent mode the batch is never resident and launches per width group as ever.
+struct A2Mix
+{
+  bool resident = false;
+  DeviceBuf<float> d_blob; // [submodel][stride]: the padded plans' blobs, the largest submodel's own at [full_width]
+  DeviceBuf<float> d_scal; // [submodel][2]: head_scale, the activation's slope (A1Args::bank_scal)
+  DeviceBuf<int> d_member; // [stream] = nam_hip_batch::stream_width, refreshed whenever the batch becomes resident
+  long stride = 0;
+  std::vector<DeviceBuf<A2XcRing>> d_rings; // [submodel]: nam_hip_model::transcode[submodel].rings
+  unsigned long long n_transcodes = 0; // (NAM_HIP_SESSION_STATS) launches of nam_a2_transcode_kernel, streams they moved, and the
+  unsigned long long n_streams_moved = 0; // host's time in them, the wait for the batch's stream included
+  double t_transcode_us = 0;
 };
 
 // Persistent block mode (nam_hip_batch_set_persistent): one resident launch of nam_a1_p2_kernel per session, fed one
@@ -344,6 +372,7 @@ struct nam_hip_batch
   std::vector<float> pipe_cvt; // the _f64 forms of submit / wait: one buffer of float32 on the way in / out
   int kernel = NAM_HIP_KERNEL_AUTO;
   std::vector<WidthGroup> groups;
+  A2Mix mix; // (mix.resident: an A2 container's batch at mixed sizes in persistent mode)
   LinearContainer lin; // (lin.on: an all-Linear container's batch)
   std::vector<int> stream_width;
   bool was_reset = false;
@@ -521,6 +550,21 @@ int get_stream_state(nam_hip_batch* b, int stream, void* buf); // (buf: stream_s
 int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size);
 // 64 bits that name a model: architecture, config text, fast_tanh and weights (a container: its submodels'; a nested condition_dsp's too)
 uint64_t model_fingerprint(const ModelSpec& s);
+// An A2 container's batch at mixed sizes (A2Mix). _wanted: persistent mode is on, more than one size is in use, and a session of
+// nam_kq_kernel over the padded plans can hold the batch. _enter / _leave: the narrow streams' state into / out of the largest
+// submodel's rows (nam_a2_transcode_kernel; the batch is quiesced by them, its stream drained on return); no-ops when the batch is
+// already there. _sync: whichever of the two `_wanted` asks for — the last step of every control call that changes a size, the
+// mode, the kernel choice or a stream's state; such a call starts with _leave, so between the two the batch is what it is
+// outside persistent mode.
+bool a2mix_wanted(const nam_hip_batch* b);
+int a2mix_enter(nam_hip_batch* b);
+int a2mix_leave(nam_hip_batch* b);
+int a2mix_sync(nam_hip_batch* b);
+// whether a launch or a session of the batch touches the group's own state rows (a resident batch: the largest submodel's only)
+inline bool group_state_in_play(const nam_hip_batch* b, const WidthGroup& g)
+{
+  return !g.streams.empty() && (!b->mix.resident || &g == &b->groups[(size_t)b->model->full_width]);
+}
 // api_session.cpp
 StateFamily persist_family(const nam_hip_batch* b, const WidthGroup& g);
 int persist_kind(const nam_hip_batch* b);

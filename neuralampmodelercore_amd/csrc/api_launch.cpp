@@ -510,6 +510,18 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
   const bool il = fn == FN_A1_P2 || fn == FN_A1_P4 || fn == FN_A1_Q;
   if (g.d_bank_member && !((bank_rules(b).fns >> fn) & 1u))
     return fail(NAM_HIP_ERR_UNSUPPORTED, bank_rules(b).launch_refusal);
+  if (b->mix.resident)
+  {
+    // an A2 container at mixed sizes (A2Mix): every stream's rings are in this group's rows, its weights are its submodel's
+    // (padded) blob — the bank path of the two kernels that know it, whole blobs at base offset 0 like an A2 bank's
+    if (&g != &b->groups[(size_t)b->model->full_width] || (fn != FN_KQ && fn != FN_KT_MFMA))
+      return fail(NAM_HIP_ERR_UNSUPPORTED, "A2 container at mixed sizes in persistent mode: only nam_kq_kernel and nam_kt_mfma_kernel run it "
+                                           "(a launch beyond 2^28 frames would take nam_a1_kernel: split the launch)");
+    a.blob = b->mix.d_blob.get();
+    a.bank_member = b->mix.d_member.get();
+    a.bank_scal = b->mix.d_scal.get();
+    a.bank_stride = b->mix.stride;
+  }
   if (il)
   {
     const int act = uniform_act(p.a1);
@@ -923,6 +935,141 @@ int move_streams_to_width(nam_hip_batch* b, const std::vector<int>& moved, int w
   return rc;
 }
 
+// ---- an A2 container's batch at mixed sizes in persistent mode (api_internal.h: A2Mix) ----
+
+bool a2mix_wanted(const nam_hip_batch* b)
+{
+  const nam_hip_model& m = *b->model;
+  if (!b->ps.enabled || b->bank || !m.a2_mix() || b->no_pipe)
+    return false;
+  const WidthGroup& full = b->groups[(size_t)m.full_width];
+  // what persist_kind asks of a one-size batch on nam_kq_kernel (PERSIST_KQ), of the largest submodel's plan over EVERY stream
+  if (!(full.plan->a1.valid && kq_runs(b, *full.plan) && !full.plan->a1.ws_ok && b->n_streams <= kPersistTurns * std::max(b->n_cus, 1)
+        && pick_kernel(b, full) == NAM_HIP_KERNEL_A1_MFMA))
+    return false;
+  if (full.state_family != STATE_FRESH && full.state_family != state_family_of(*full.plan, NAM_HIP_KERNEL_A1_MFMA))
+    return false;
+  int sizes = 0;
+  for (size_t w = 0; w < b->groups.size(); w++)
+  {
+    const WidthGroup& g = b->groups[w];
+    if (g.streams.empty())
+      continue;
+    sizes++;
+    // a narrow stream comes from and goes back to nam_wn_reg_kernel's layout: what the group runs outside the session
+    if ((int)w != m.full_width && (!m.transcode[w].ok || !g.d_state || pick_kernel(b, g) != NAM_HIP_KERNEL_WN_REG
+                                   || (g.state_family != STATE_FRESH && g.state_family != STATE_WN_REG)))
+      return false;
+  }
+  return sizes > 1;
+}
+
+// the device side of A2Mix, once per batch (a control call: set_persistent, set_slimmable_size ... allocate, process calls never)
+static int a2mix_prepare(nam_hip_batch* b)
+{
+  A2Mix& mx = b->mix;
+  if (mx.d_blob)
+    return NAM_HIP_OK;
+  const nam_hip_model& m = *b->model;
+  const Plan& full = m.plans[(size_t)m.full_width];
+  const size_t n = m.plans.size();
+  const size_t stride = (full.blob.size() + 3) / 4 * 4; // (the kernels read 16-byte records)
+  std::vector<float> blobs(n * stride, 0.0f), scal(2 * n, 0.0f);
+  DeviceBuf<float> d_blob, d_scal;
+  DeviceBuf<int> d_member;
+  std::vector<DeviceBuf<A2XcRing>> d_rings(n);
+  for (size_t w = 0; w < n; w++)
+  {
+    const Plan& p = (int)w == m.full_width ? full : m.padded[w];
+    if (p.blob.size() != full.blob.size())
+      return fail(NAM_HIP_ERR_MODEL, "A2 container: a padded plan's blob does not have the largest submodel's size");
+    std::memcpy(blobs.data() + w * stride, p.blob.data(), p.blob.size() * sizeof(float));
+    scal[2 * w] = p.blob[(size_t)p.a1.head_scale_off];
+    scal[2 * w + 1] = p.a1.arr[0].act == ACT_RELU ? 0.0f : p.a1.arr[0].act_p0; // (as a bank's members: api_bank.cpp)
+    if ((int)w == m.full_width)
+      continue;
+    const A2Transcode& t = m.transcode[w];
+    // the table against the rows it will be run on (a2_transcode_check has walked it at load: build_model)
+    if (t.wr_state_floats > m.plans[w].state_floats || t.a2_state_floats > full.state_floats)
+      return fail(NAM_HIP_ERR_MODEL, "A2 container: the transcode table names floats outside the state rows");
+    NAM_HIP_CHECK(upload(d_rings[w], t.rings.data(), t.rings.size()));
+  }
+  NAM_HIP_CHECK(upload(d_blob, blobs.data(), blobs.size()));
+  NAM_HIP_CHECK(upload(d_scal, scal.data(), scal.size()));
+  NAM_HIP_CHECK(hipMalloc(d_member.out(), (size_t)b->n_streams * sizeof(int)));
+  mx.d_blob = std::move(d_blob); // (all or nothing)
+  mx.d_scal = std::move(d_scal);
+  mx.d_member = std::move(d_member);
+  mx.d_rings = std::move(d_rings);
+  mx.stride = (long)stride;
+  return NAM_HIP_OK;
+}
+
+// every narrow stream's state between its group's row and the largest submodel's, on the batch's stream (the batch is quiesced)
+static int a2mix_move_all(nam_hip_batch* b, bool to_padded)
+{
+  const nam_hip_model& m = *b->model;
+  WidthGroup& full = b->groups[(size_t)m.full_width];
+  const double t0 = stats_on() ? stat_now_us() : 0.0;
+  for (size_t w = 0; w < b->groups.size(); w++)
+  {
+    WidthGroup& g = b->groups[w];
+    if ((int)w == m.full_width || g.streams.empty())
+      continue;
+    // (a narrow group of a mixed batch never holds every stream: refresh_map has given it its stream list)
+    if (!g.d_map || !g.d_state || !full.d_state)
+      return fail(NAM_HIP_ERR_MODEL, "A2 container: a narrow group without a stream map or state");
+    NAM_HIP_CHECK(launch_a2_transcode(b->mix.d_rings[w].get(), (int)m.transcode[w].rings.size(), full.d_state.get(), full.state_stride, g.d_state.get(),
+                                      g.state_stride, g.d_map.get(), (int)g.streams.size(), to_padded, b->stream.get()));
+    b->mix.n_transcodes++;
+    b->mix.n_streams_moved += g.streams.size();
+  }
+  NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
+  if (stats_on())
+    b->mix.t_transcode_us += stat_now_us() - t0;
+  return NAM_HIP_OK;
+}
+
+int a2mix_enter(nam_hip_batch* b)
+{
+  if (b->mix.resident)
+    return NAM_HIP_OK;
+  NAM_HIP_CHECK(quiesce(b));
+  if (const int rc = a2mix_prepare(b))
+    return rc;
+  NAM_HIP_CHECK(hipMemcpy(b->mix.d_member.get(), b->stream_width.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
+  if (const int rc = a2mix_move_all(b, true))
+    return rc;
+  const nam_hip_model& m = *b->model;
+  for (size_t w = 0; w < b->groups.size(); w++)
+  {
+    WidthGroup& g = b->groups[w];
+    if (g.streams.empty())
+      continue;
+    // zeros are zeros in either layout; from here on the rows are what they were moved as
+    if (g.state_family == STATE_FRESH)
+      g.state_family = (int)w == m.full_width ? state_family_of(*g.plan, NAM_HIP_KERNEL_A1_MFMA) : STATE_WN_REG;
+  }
+  b->mix.resident = true;
+  return NAM_HIP_OK;
+}
+
+int a2mix_leave(nam_hip_batch* b)
+{
+  if (!b->mix.resident)
+    return NAM_HIP_OK;
+  NAM_HIP_CHECK(quiesce(b));
+  if (const int rc = a2mix_move_all(b, false))
+    return rc;
+  b->mix.resident = false;
+  return NAM_HIP_OK;
+}
+
+int a2mix_sync(nam_hip_batch* b)
+{
+  return a2mix_wanted(b) ? a2mix_enter(b) : a2mix_leave(b);
+}
+
 // ---- stream slots (include/nam_hip.h: nam_hip_batch_restart_streams, _get / _set_stream_state) ----
 
 uint64_t model_fingerprint(const ModelSpec& s)
@@ -945,9 +1092,19 @@ uint64_t model_fingerprint(const ModelSpec& s)
 }
 
 // The state of a newly created batch after nam_hip_batch_reset(prewarm), for the streams `ids` (ascending, unique, in range)
+static int restart_streams_in_groups(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm);
 int restart_streams(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
 {
   NAM_HIP_CHECK(quiesce(b));
+  // (an A2 container at mixed sizes: every stream back in its own group's rows, the restart as ever, the batch resident again)
+  if (const int rc = a2mix_leave(b))
+    return rc;
+  if (const int rc = restart_streams_in_groups(b, ids, prewarm))
+    return rc;
+  return a2mix_sync(b);
+}
+static int restart_streams_in_groups(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
+{
   if (b->lin.on) // the streams' columns of the one ring; sizes, the position and every other column stay
   {
     for (int s : ids)
@@ -1058,6 +1215,24 @@ int get_stream_state(nam_hip_batch* b, int stream, void* buf)
   const sstate::Geometry q = stream_geometry(b, w);
   const size_t bytes = (size_t)q.payload_bytes();
   std::vector<float> payload(bytes / sizeof(float));
+  if (b->mix.resident && w != b->model->full_width)
+  {
+    // the stream lives zero-padded in the largest submodel's rows (A2Mix): its blob is its own group's row, as ever — this one
+    // stream's rings are copied there first (the padded copy stays the live one; no other stream is touched)
+    DeviceBuf<int> d_one;
+    NAM_HIP_CHECK(upload(d_one, &stream, 1));
+    WidthGroup& full = b->groups[(size_t)b->model->full_width];
+    const double t0 = stats_on() ? stat_now_us() : 0.0;
+    const hipError_t e = launch_a2_transcode(b->mix.d_rings[(size_t)w].get(), (int)b->model->transcode[(size_t)w].rings.size(), full.d_state.get(),
+                                             full.state_stride, g.d_state.get(), g.state_stride, d_one.get(), 1, false, b->stream.get());
+    const hipError_t es = hipStreamSynchronize(b->stream.get()); // (before `d_one` goes)
+    NAM_HIP_CHECK(e);
+    NAM_HIP_CHECK(es);
+    b->mix.n_transcodes++;
+    b->mix.n_streams_moved++;
+    if (stats_on())
+      b->mix.t_transcode_us += stat_now_us() - t0;
+  }
   if (q.arch == ARCH_LINEAR)
   {
     DeviceBuf<float> rows; // the stream's columns, oldest frame first
@@ -1082,9 +1257,20 @@ int get_stream_state(nam_hip_batch* b, int stream, void* buf)
   return NAM_HIP_OK;
 }
 
+static int set_stream_state_in_groups(nam_hip_batch* b, int stream, const void* buf, int64_t size);
 int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size)
 {
   NAM_HIP_CHECK(quiesce(b));
+  // (an A2 container at mixed sizes: the blob is written into the stream's own group's row with every stream back in its own; what
+  // the batch is afterwards — the blob may have changed the stream's size — decides where the streams live from here on)
+  if (const int rc = a2mix_leave(b))
+    return rc;
+  const int rc = set_stream_state_in_groups(b, stream, buf, size);
+  const int rs = a2mix_sync(b); // (also behind a refusal: the batch goes back to where it was)
+  return rc != NAM_HIP_OK ? rc : rs;
+}
+static int set_stream_state_in_groups(nam_hip_batch* b, int stream, const void* buf, int64_t size)
+{
   // 1. everything the blob says against the batch, before anything changes
   std::vector<sstate::Geometry> widths;
   for (size_t w = 0; w < b->groups.size(); w++)
@@ -1220,6 +1406,35 @@ int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out)
                      again.wr.ok ? "the run-time-flag instantiations" : "another kernel");
         p = std::move(again);
       }
+    }
+  }
+  // a container on the A2 family (nam_hip_model::padded): every narrower submodel zero-padded onto the largest one's layout, and
+  // the table between its two residences, walked once here. All or nothing: one submodel without its pair and a batch at mixed
+  // sizes stays what it was, a launch per size and no session.
+  if (m->spec->arch == ARCH_CONTAINER && m->plans.size() > 1 && m->plans[(size_t)m->full_width].arch == ARCH_WAVENET)
+  {
+    const Plan& full = m->plans[(size_t)m->full_width];
+    std::vector<Plan> padded(m->plans.size());
+    std::vector<A2Transcode> transcode(m->plans.size());
+    bool all = full.a1.valid && full.a1.kt_ok && full.a1.kp_ok;
+    for (size_t w = 0; all && w < m->plans.size(); w++)
+    {
+      if ((int)w == m->full_width)
+        continue;
+      const ModelSpec& sm = *m->spec->submodels[w];
+      std::string why;
+      all = sm.arch == ARCH_WAVENET && m->plans[w].arch == ARCH_WAVENET && build_a2_padded_plan(sm.wavenet, full, padded[w], why);
+      if (all)
+      {
+        transcode[w] = build_a2_transcode(m->plans[w], padded[w]);
+        all = transcode[w].ok && a2_transcode_check(transcode[w]).empty() && transcode[w].wr_state_floats <= m->plans[w].state_floats
+              && transcode[w].a2_state_floats <= full.state_floats;
+      }
+    }
+    if (all)
+    {
+      m->padded = std::move(padded);
+      m->transcode = std::move(transcode);
     }
   }
   *out = m.release();

@@ -24,6 +24,10 @@ int persist_kind(const nam_hip_batch* b)
     return PERSIST_NONE;
   if (g.plan->arch == ARCH_LINEAR) // no recurrence, nothing to keep resident: a Linear batch launches per call (Linear, follow-up)
     return PERSIST_NONE;
+  // an A2 container at mixed sizes whose narrow streams live zero-padded next to the largest submodel's (A2Mix; a2mix_wanted has
+  // asked what PERSIST_KQ asks below, of every stream): one group, one launch of nam_kq_kernel, one command ring
+  if (b->mix.resident)
+    return PERSIST_KQ;
   const int cus = std::max(b->n_cus, 1);
   {
     // nam_wn_reg_kernel serves every width group with one launch: a mixed-width batch is one session. Its workgroups
@@ -625,7 +629,7 @@ int persist_submit_block(nam_hip_batch* b, const float* d_in, float* d_out, long
   ps.flushed_valid = false;
   ps.last_caller = caller.stream;
   for (auto& g : b->groups)
-    if (!g.streams.empty() && g.plan->arch == ARCH_WAVENET)
+    if (group_state_in_play(b, g) && g.plan->arch == ARCH_WAVENET)
       g.state_family = persist_family(b, g);
   return NAM_HIP_OK;
 }

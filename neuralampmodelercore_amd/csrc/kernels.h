@@ -5,6 +5,7 @@
 #include <hip/hip_ext.h>
 #include <type_traits>
 
+#include "a2_transcode.h"
 #include "linear_worklist.h"
 #include "plan.h"
 
@@ -377,6 +378,11 @@ hipError_t launch_fill_state(float* state, long state_stride, const int* stream_
 // the bank form: `init` = [member][n_init], stream s takes row member_of[s] (indexed by STREAM, like LSTMArgs::bank_member)
 hipError_t launch_fill_state_bank(float* state, long state_stride, const int* stream_map, int n_streams, const float* init,
                                   const int* member_of, int n_init, int state_floats, hipStream_t stream);
+// nam_a2_transcode_kernel (kernel_a2_transcode.hip): the streams `streams` (device memory; nullptr = 0 .. n_streams - 1) of a narrow A2
+// container submodel between nam_wn_reg_kernel's state rows (`wr_state`) and the padded rings of the largest submodel's layout
+// (`a2_state`), ring by ring of the device table `rings` (a2_transcode.h); a plain copy, zeros into the padded channels
+hipError_t launch_a2_transcode(const A2XcRing* rings, int n_rings, float* a2_state, long a2_stride, float* wr_state, long wr_stride,
+                               const int* streams, int n_streams, bool to_padded, hipStream_t stream);
 // One stream's columns [col0, col0 + n_cols) of a Linear batch's history ring `hist` = [hist_frames][cols_pad] at position `pos`
 // (the row the next frame goes to: the oldest). `rows` = [hist_frames][n_cols] in device memory, oldest frame first
 // (stream_state.h: ring_row); unused by LINEAR_COLS_ZERO. No other column is read or written.

@@ -433,6 +433,9 @@ void nam_hip_batch_destroy(nam_hip_batch* batch)
                  batch->ps.n_starts, batch->ps.n_launches, batch->ps.n_flush_relaunches, batch->ps.n_host_doorbells, batch->ps.n_stream_doorbells);
   if (stats_on() && batch->ps.n_starts)
     std::fprintf(stderr, "nam_hip session launches: %llu publish every command, %llu of them linger\n", batch->ps.n_publishing, batch->ps.n_lingering);
+  if (stats_on() && batch->mix.n_transcodes)
+    std::fprintf(stderr, "nam_hip A2 mixed sizes: %llu launches of nam_a2_transcode_kernel moved %llu stream states, %.1f us of control calls in all\n",
+                 batch->mix.n_transcodes, batch->mix.n_streams_moved, batch->mix.t_transcode_us);
   if (stats_on() && batch->ps.n_waits)
   {
     std::fprintf(stderr, "nam_hip tickets: %llu waits, %.1f looks at the completion word each\n", batch->ps.n_waits, (double)batch->ps.n_polls / batch->ps.n_waits);
@@ -450,6 +453,7 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_reset: null batch");
   NAM_HIP_CHECK(hipSetDevice(batch->device));
   NAM_HIP_CHECK(quiesce(batch)); // launches still running on a caller-supplied stream must not race with the zeroing
+  batch->mix.resident = false; // (an A2 container at mixed sizes: every stream of every group is reset in its own group's rows, as ever — nothing to move back)
   batch->was_reset = true;
   batch->reset_with_prewarm = prewarm != 0;
   if (batch->lin.on) // zero history, as a Linear batch's; the streams keep their submodels
@@ -467,6 +471,8 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
       return rc;
   }
   NAM_HIP_CHECK(hipStreamSynchronize(batch->stream.get()));
+  if (const int rc = a2mix_sync(batch)) // (... and its narrow streams' fresh state moves next to the largest submodel's again)
+    return rc;
   if (batch->ps.enabled && persist_eligible(batch)) // (a session's window-independent resources: see nam_hip_batch_set_persistent)
   {
     const int rc = persist_prepare(batch);
@@ -547,10 +553,21 @@ int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids
   NAM_HIP_CHECK(quiesce(batch));
   if (batch->lin.on) // the moved streams' columns of the one ring become zero: a freshly reset submodel
     return lin_container_move(batch, moved, w, true);
+  // an A2 container in persistent mode (A2Mix): a change that mixes or un-mixes the batch moves the OTHER streams' state between
+  // the two layouts — a copy, so they go on as if nothing had happened; the named streams get their fresh state in their new
+  // group's own rows first, as ever
+  if (const int rc = a2mix_leave(batch))
+    return rc;
   if (const int rc = move_streams_to_width(batch, moved, w))
     return rc;
   // fresh sub-model state for the streams that moved: Reset (+ prewarm) as in slimmable.cpp:433-447
-  return reset_moved_streams(batch, batch->groups[w], moved, false);
+  if (const int rc = reset_moved_streams(batch, batch->groups[w], moved, false))
+    return rc;
+  if (const int rc = a2mix_sync(batch))
+    return rc;
+  if (batch->mix.resident) // (a batch that has just become one session: its ring and words, outside the audio path)
+    return persist_prepare(batch);
+  return NAM_HIP_OK;
 }
 
 int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float* d_out, int n_frames,
@@ -568,7 +585,7 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
   {
     // fresh state has the layout any kernel family writes; anything else must already be the session kernel's
     for (auto& g0 : batch->groups)
-      if (!g0.streams.empty() && g0.plan->arch == ARCH_WAVENET && g0.state_family >= 0
+      if (group_state_in_play(batch, g0) && g0.plan->arch == ARCH_WAVENET && g0.state_family >= 0
           && g0.state_family != persist_family(batch, g0))
         return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "persistent mode: the state was written in another kernel family's layout; reset first");
     const int rc = persist_submit(batch, d_in, d_out, n_frames, (long)frame_stride, s);
@@ -589,6 +606,10 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
   }
   if (batch->lin.on) // one launch for every stream, whichever submodel each is on
     return lin_container_launch(batch, d_in, d_out, n_frames, (long)frame_stride, s);
+  if (batch->mix.resident) // an A2 container at mixed sizes, a call outside the session (a ragged length): every stream's rings are in
+                           // the largest submodel's rows — one launch of its kernels over all of them, as an all-Full batch falls back
+    return launch_group(batch, batch->groups[(size_t)batch->model->full_width], nullptr, batch->n_streams, d_in, d_out, n_frames, (long)frame_stride, s,
+                        LaunchContext());
   for (auto& g : batch->groups)
   {
     if (g.streams.empty())
@@ -813,6 +834,13 @@ int nam_hip_batch_set_persistent(nam_hip_batch* batch, int enable)
       return rc;
   }
   batch->ps.enabled = enable != 0; // (persist_eligible / persist_kind look at it)
+  // an A2 container at mixed sizes: on, its narrow streams move next to the largest submodel's (one session of nam_kq_kernel); off,
+  // they move back to their own groups' rows and the batch launches per size again
+  if (const int rc = a2mix_sync(batch))
+  {
+    batch->ps.enabled = false;
+    return rc;
+  }
   const bool eligible = batch->ps.enabled && persist_eligible(batch);
   if (eligible)
   {
@@ -854,6 +882,16 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
     const int rc = persist_stop(batch, CallHints());
     if (rc != NAM_HIP_OK)
       return rc;
+  }
+  if (batch->mix.resident)
+  {
+    // an A2 container at mixed sizes: the choice is made on the batch as it is outside persistent mode (every stream in its own
+    // group's rows), and whatever it turns out to be decides where the streams live afterwards
+    if (const int rc = a2mix_leave(batch))
+      return rc;
+    const int rc = nam_hip_batch_set_kernel(batch, kernel);
+    const int rs = a2mix_sync(batch);
+    return rc != NAM_HIP_OK ? rc : rs;
   }
   if (batch->model->spec->arch == ARCH_LINEAR || batch->lin.on) // one device engine (include/nam_hip.h): nothing to choose
   {
@@ -944,8 +982,11 @@ int nam_hip_batch_debug_timeline(nam_hip_batch* batch, int n_frames, long long* 
     ctx.dbg = dbg.get();
     if (batch->lin.on)
       rc = lin_container_launch(batch, nullptr, nullptr, n_frames, 0, batch->stream.get());
+    if (batch->mix.resident) // (as nam_hip_batch_process_device: one launch over every stream)
+      rc = launch_group(batch, batch->groups[(size_t)batch->model->full_width], nullptr, batch->n_streams, nullptr, nullptr, n_frames, 0,
+                        batch->stream.get(), ctx);
     for (auto& g : batch->groups)
-      if (!g.streams.empty() && rc == NAM_HIP_OK && !batch->lin.on)
+      if (!g.streams.empty() && rc == NAM_HIP_OK && !batch->lin.on && !batch->mix.resident)
         rc = launch_group(batch, g, g.d_map.get(), (int)g.streams.size(), nullptr, nullptr, n_frames, 0, batch->stream.get(), ctx);
     e = hipStreamSynchronize(batch->stream.get()); // (before `dbg` goes: the launches write it)
     if (e == hipSuccess)
@@ -970,8 +1011,9 @@ const char* nam_hip_batch_kernel_name_for(const nam_hip_batch* batch, int n_fram
     return "nam_linear_pairs_kernel";
   // the group with the most streams (a uniform batch has exactly one populated group)
   const WidthGroup* best = &batch->groups[batch->model->full_width];
+  // (an A2 container at mixed sizes in persistent mode is ONE group, the largest submodel's, whatever the sizes' shares: A2Mix)
   for (const auto& g : batch->groups)
-    if (g.streams.size() > best->streams.size())
+    if (g.streams.size() > best->streams.size() && !batch->mix.resident)
       best = &g;
   return group_kernel_name(batch, *best, n_frames > 0 ? n_frames : kBlock);
 }

@@ -1,6 +1,7 @@
 // plan_a1.cpp — the A1-family kernels' plans (nam_a1_kernel, nam_a1_mfma_kernel, nam_a1_p2 / p4 / q, nam_kt_mfma_kernel,
 // nam_kq_kernel): eligibility, job descriptors, lane-record tiles, LDS layouts, the plan-time channel padding. See plan_internal.h.
 #include "plan_internal.h"
+#include "a2_transcode.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -907,6 +908,92 @@ bool pad_channels_for_mfma(const WaveNetSpec& wn, WaveNetSpec& out)
   }
   out.weights.push_back(*(w++)); // head_scale
   return w == wn.weights.data() + wn.weights.size();
+}
+
+// A single-array plain WaveNet (any per-layer kernel sizes, a head rechannel with taps: the A2 topology) zero-padded to `Cp`
+// channels — what lets a narrow submodel of a container (A2-Lite, 3 channels) run on the kernels compiled for its largest
+// submodel (A2-Full, 8: nam_kq_kernel / nam_kt_mfma_kernel) next to that submodel's streams (build_a2_padded_plan). Unlike
+// Plan::a1_padded_layout's padding above this is a SECOND plan beside the submodel's own, which stays as it is.
+// The padding is exact: a padded row has zero rechannel, conv, mixin and 1x1 weights and zero biases, so its conv sum is 0, its
+// activation is f(0) = 0 (only activations with f(0) = 0 are admitted) and its residual stays 0; a padded column meets only
+// those zeros, so a real row's sums gain terms w * 0 = +0 and nothing else; the head rechannel's padded columns are zero too.
+static bool pad_wavenet_to_channels(const WaveNetSpec& wn, int Cp, WaveNetSpec& out, std::string& why)
+{
+  auto no = [&](const char* w) {
+    why = w;
+    return false;
+  };
+  if (wn.condition_dsp || wn.with_head || wn.in_channels != 1 || wn.slimmable || wn.arrays.size() != 1)
+    return no("not a plain single-array WaveNet with a mono input");
+  const LayerArraySpec& A = wn.arrays[0];
+  if (A.channels >= Cp || A.channels < 1)
+    return no("not narrower than the largest submodel");
+  if (A.bottleneck != A.channels || A.condition_size != 1 || A.input_size != 1 || A.groups_input != 1 || A.groups_input_mixin != 1
+      || !A.layer1x1_active || A.layer1x1_groups != 1 || A.head1x1_active || A.head_size != 1)
+    return no("a layer feature the padding does not cover (bottleneck, groups, head1x1, condition or head size)");
+  for (int g : A.gating_modes)
+    if (g != GATING_NONE)
+      return no("gated layers");
+  for (int k = 0; k < FILM_COUNT; k++)
+    if (A.film[k].active)
+      return no("FiLM");
+  for (const ActSpec& a : A.activations)
+    if (a.type != ACT_TANH && a.type != ACT_FASTTANH && a.type != ACT_RELU && a.type != ACT_LEAKYRELU)
+      return no("an activation that does not map 0 to 0");
+  out = wn;
+  out.weights.clear();
+  const float* w = wn.weights.data();
+  const float* const w_end = w + wn.weights.size();
+  bool short_stream = false;
+  LayerArraySpec& P = out.arrays[0];
+  const int C = A.channels;
+  P.channels = P.bottleneck = Cp;
+  // tensor [rows][cols][taps] of the stream, zero-padded to [rows_p][cols_p][taps]
+  auto tensor = [&](int rows, int cols, int taps, int rows_p, int cols_p) {
+    const size_t n = (size_t)rows * cols * taps;
+    if ((size_t)(w_end - w) < n)
+    {
+      short_stream = true;
+      return;
+    }
+    for (int r = 0; r < rows_p; r++)
+      for (int c = 0; c < cols_p; c++)
+        for (int k = 0; k < taps; k++)
+          out.weights.push_back(r < rows && c < cols ? w[((size_t)r * cols + c) * taps + k] : 0.0f);
+    w += n;
+  };
+  tensor(C, 1, 1, Cp, 1); // rechannel [C][in]
+  for (int l = 0; l < A.num_layers() && !short_stream; l++)
+  {
+    tensor(C, C, A.kernel_sizes[(size_t)l], Cp, Cp); // conv [co][ci][k]
+    tensor(C, 1, 1, Cp, 1); // conv bias
+    tensor(C, 1, 1, Cp, 1); // input mixin [C][1]
+    tensor(C, C, 1, Cp, Cp); // layer1x1 [co][ci]
+    tensor(C, 1, 1, Cp, 1); // its bias
+  }
+  tensor(1, C, A.head_kernel_size, 1, Cp); // head rechannel [H = 1][C][K_h]
+  if (A.head_bias)
+    tensor(1, 1, 1, 1, 1);
+  tensor(1, 1, 1, 1, 1); // head_scale
+  if (short_stream || w != w_end)
+    return no("the weight stream does not have the plain layout");
+  return true;
+}
+
+bool build_a2_padded_plan(const WaveNetSpec& narrow, const Plan& full, Plan& out, std::string& why)
+{
+  const A1Plan& f = full.a1;
+  if (full.arch != ARCH_WAVENET || !f.valid || !f.kt_ok || !f.kp_ok || f.n_arrays != 1)
+  {
+    why = "the largest submodel is not the topology nam_kq_kernel is compiled for";
+    return false;
+  }
+  WaveNetSpec padded;
+  if (!pad_wavenet_to_channels(narrow, f.arr[0].channels, padded, why))
+    return false;
+  out = build_wavenet_plan(padded); // (no shape set: nam_wn_reg_kernel runs the submodel's OWN plan, never this one)
+  why = a2_layout_difference(out, full);
+  return why.empty();
 }
 
 // Geometry of a (possibly downloaded, possibly corrupt) file before any 32-bit offset is derived from it: dilations and

@@ -103,7 +103,7 @@ int run_compiler(const std::vector<std::string>& argv, const std::string& log)
       return -1;
   return WIFEXITED(status) ? WEXITSTATUS(status) : -1;
 }
-const char* const kSources[] = {"kernel_wn_reg.hip", "device_common.h", "kernels.h", "plan.h", "model_spec.h", "persist_wave.h", "session_command.h"};
+const char* const kSources[] = {"kernel_wn_reg.hip", "device_common.h", "kernels.h", "a2_transcode.h", "linear_worklist.h", "plan.h", "model_spec.h", "persist_wave.h", "session_command.h"};
 } // namespace
 
 bool wr_jit_enabled()
