@@ -346,7 +346,11 @@ NAM_HIP_API int nam_hip_batch_restart_streams(nam_hip_batch* batch, const int* s
  * nam_wn_reg_kernel's layout, whichever way the stream currently lives — get copies a zero-padded stream's rings out into that
  * layout (the padded channels are dropped), set copies them in (the padded channels become zero) —, so the blob format, its size
  * and where it may go (an all-Lite batch, a mixed one, persistent or not) do not depend on the batch it came from.
- * nam_hip_batch_restart_streams works on either kind of stream of such a batch. */
+ * nam_hip_batch_restart_streams works on either kind of stream of such a batch.
+ * Containers of the official WaveNet topology's sizes (standard, lite, feather) at mixed sizes in persistent mode: a lite or
+ * feather stream's blob is its own submodel's zero-padded rings, the layout it has in either residence — get copies the stream's
+ * row out of the standard submodel's rows first, set writes it into the stream's own row and the row moves back in —, so here
+ * too the blob's format, size and acceptable destinations are the same whether the batch is resident or not. */
 NAM_HIP_API int64_t nam_hip_batch_stream_state_size(const nam_hip_batch* batch, int stream);
 NAM_HIP_API int nam_hip_batch_get_stream_state(nam_hip_batch* batch, int stream, void* buf, int64_t capacity, int64_t* out_size);
 NAM_HIP_API int nam_hip_batch_set_stream_state(nam_hip_batch* batch, int stream, const void* buf, int64_t size);
@@ -357,7 +361,8 @@ NAM_HIP_API int nam_hip_batch_set_stream_state(nam_hip_batch* batch, int stream,
  * prewarm, prewarmed) state, as the reference's rebuilt model does. stream_ids == NULL selects all.
  * Every stream the call does not name keeps its state — also where the call mixes or un-mixes an A2 container's batch in
  * persistent mode and those streams change the kernel they run on (nam_hip_batch_set_persistent): their histories are copied
- * into the other kernel's layout, float for float. */
+ * into the other kernel's layout, float for float. The same holds for a container of the official WaveNet topology's sizes
+ * (standard, lite, feather): there the rows of the streams the call does not name are copied whole, bit for bit. */
 NAM_HIP_API int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids, int n_ids, double ratio);
 
 /* DSP::process(NAM_SAMPLE** input, NAM_SAMPLE** output, int num_frames) — NAM/dsp.h:97,
@@ -425,6 +430,20 @@ NAM_HIP_API int nam_hip_batch_render_f32(nam_hip_batch* batch, const float* cons
  * ring positions, so those streams go on undisturbed; no process call ever does. Outside the mode such a batch launches per size,
  * as ever. nam_hip_batch_kernel_name* answer nam_kq_kernel / nam_kt_mfma_kernel for such a batch whatever the sizes' shares: every
  * stream runs them.
+ * The same rule for the official WaveNet topology (standard 16 / 8, lite 12 / 6, feather 8 / 4 channels): a SlimmableContainer
+ * qualifies when EVERY submodel plans onto the padded 16 / 8 layout with a nam_a1_q_kernel plan — each one a model a bank of the
+ * interleaved-frame family would take, all with one activation and one fast_tanh, none differing from the largest in a field
+ * nam_hip_bank_create compares (NAM_HIP_FIELD_DESCRIPTION says "a1_mixed_session=1", or "=0" and the first difference). Its
+ * streams at MIXED sizes are ONE group on the BANK forms of nam_a1_q_kernel / nam_a1_p4_kernel, up to 8 streams per CU, member =
+ * the stream's submodel: one resident launch, one command ring; tickets, linger, per-command completion, flush and the
+ * short-burst switch to nam_a1_p4_kernel as on an all-standard batch; a length that is no multiple of 64 frames ends the session
+ * and runs one plain launch over every stream (nam_a1_p2_kernel, as a bank batch of that family). While the mode is on every
+ * stream's rings live in the standard submodel's state rows: a lite or feather stream's own rows have that layout already, so the
+ * control calls listed above copy whole rows (nam_state_rows_copy_kernel), bit for bit, and only there. nam_hip_batch_set_kernel:
+ * NAM_HIP_KERNEL_AUTO and NAM_HIP_KERNEL_A1_IL keep such a batch in the mode, any other choice takes it out. A batch whose
+ * streams are all at one size runs what it always ran. Not covered: a nano tier (4 / 2 channels: outside nam_a1_q_kernel's plan
+ * family, it lives on nam_wn_reg_kernel; one such submodel and the container does not qualify), model banks of containers,
+ * slimmable WaveNets of the slice method, Linear models.
  * Returns 1 if the batch will use the mode, 0 if it is not eligible (the calls then launch as usual).
  * Allocation: this call and nam_hip_batch_reset — the non-real-time side of the reference's contract (NAM/dsp.h:163) — allocate
  * everything a session needs (command ring, completion words, its stream and events, the host windows of the blocking entry points);

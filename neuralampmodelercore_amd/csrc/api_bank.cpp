@@ -290,6 +290,39 @@ const BankFamilyRules kBankFamily[BANK_FAMILY_COUNT] = {
    1u << FN_WN_REG, "model bank (nam_wn_reg_kernel family): only nam_wn_reg_kernel runs it", BANK_BLOB_WR, BANK_MEMBER_NOTHING},
 };
 
+// A container's submodels as the members of one BANK_A1_IL bank, the largest as member 0 (nam_hip_model::mix_family: MIX_A1): each
+// is put to member_refusal and a1_il_difference as a model of its own — its spec, its plan — exactly as nam_hip_bank_create puts
+// the members it is given.
+std::string container_a1_difference(const nam_hip_model& m)
+{
+  if (m.spec->arch != ARCH_CONTAINER || m.plans.size() != m.spec->submodels.size())
+    return "not a SlimmableContainer with one plan per submodel";
+  std::vector<nam_hip_model> sub(m.plans.size());
+  for (size_t w = 0; w < sub.size(); w++)
+  {
+    sub[w].spec = m.spec->submodels[w];
+    sub[w].plans.push_back(m.plans[w]);
+    sub[w].width_channels.push_back({});
+  }
+  const size_t order_first = (size_t)m.full_width; // (member 0 first: a refusal of the largest submodel is the first reason)
+  for (size_t k = 0; k < sub.size(); k++)
+  {
+    const size_t w = k == 0 ? order_first : (k <= order_first ? k - 1 : k);
+    int fam = BANK_A1_IL;
+    const std::string why = member_refusal(sub[w], &fam);
+    if (!why.empty())
+      return "submodel " + std::to_string(w) + " is " + why;
+    FirstDifference diff;
+    if (fam != BANK_A1_IL)
+      diff.text = std::string("family (") + kBankFamily[fam].name + " vs " + kBankFamily[BANK_A1_IL].name + ")";
+    else if (w != order_first)
+      kFirstDifference[BANK_A1_IL](diff, sub[order_first], sub[w]);
+    if (!diff.text.empty())
+      return "submodel " + std::to_string(w) + " differs from the largest submodel in " + diff.text;
+  }
+  return "";
+}
+
 int bank_blob_base(const Plan& p, int family)
 {
   return kBankFamily[family].blob_source == BANK_BLOB_KERNEL_REGION ? p.a1.ws_tiles_off : 0;

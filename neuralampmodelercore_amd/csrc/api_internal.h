@@ -96,7 +96,13 @@ struct nam_hip_model
   // are empty unless EVERY narrower submodel has its pair: a batch at mixed sizes then runs persistent mode as one session.
   std::vector<Plan> padded;
   std::vector<A2Transcode> transcode;
-  bool a2_mix() const { return !padded.empty(); }
+  // Which mixed-size residency a batch of this container has in persistent mode (MixFamily below; MIX_NONE: none, a batch at mixed
+  // sizes is a launch per size). MIX_A2: the pair of vectors above is filled. MIX_A1: every submodel is a member of ONE bank of
+  // the BANK_A1_IL family (api_bank.cpp: container_a1_difference) — the official topology at (padded) 16 / 8 channels, one
+  // activation, one fast_tanh; nothing more is kept, the submodels' own plans are the members. `mix_note`: the sentence
+  // NAM_HIP_FIELD_DESCRIPTION says about it ("" for a model the question does not arise for).
+  int mix_family = -1;
+  std::string mix_note;
 
   bool slimmable() const { return spec->arch == ARCH_CONTAINER || (spec->arch == ARCH_WAVENET && spec->wavenet.slimmable); }
   int width_for_ratio(double ratio) const
@@ -222,23 +228,55 @@ struct LinearContainer
   int pos = 0; // the ring row the next frame goes to (host state, as WidthGroup::lin_pos)
 };
 
-// A batch of an A2 container (nam_hip_model::a2_mix) whose streams are at MIXED sizes, in persistent mode: the
-// narrow streams live zero-padded in the largest submodel's state rows (`resident`: group[full_width].d_state holds EVERY stream's
-// rings; the narrow groups keep their membership, their own rows are stale) and the whole batch is one launch of the largest
-// submodel's kernels through their bank path — member = the stream's submodel, member full_width = the largest submodel's own
-// blob. Entered and left by control calls only (api_launch.cpp: a2mix_enter / a2mix_leave move the narrow streams' state with
-// nam_a2_transcode_kernel); outside persistent mode the batch is never resident and launches per width group as ever.
-struct A2Mix
+// A batch of a container with a mixed-size residency (nam_hip_model::mix_family) whose streams are at MIXED sizes, in persistent
+// mode: the narrow streams live zero-padded in the largest submodel's state rows (`resident`:
+// group[full_width].d_state holds EVERY stream's rings; the narrow groups keep their membership, their own rows are stale) and the
+// whole batch is one launch of the largest submodel's kernels through their bank path — member = the stream's submodel, member
+// full_width = the largest submodel's own blob. Entered and left by control calls only (api_launch.cpp: mix_enter / mix_leave move
+// the narrow streams' state); outside persistent mode the batch is never resident and launches per width group as ever.
+// The two families differ in their row of kMixFamily and in nothing else:
+//  * MIX_A2 (A2.nam: A2-Lite next to A2-Full): nam_kq_kernel / nam_kt_mfma_kernel over the padded plans' WHOLE blobs; a narrow
+//    stream's own rows are nam_wn_reg_kernel's layout, so its state moves through a table (nam_a2_transcode_kernel).
+//  * MIX_A1 (the official WaveNet topology: standard 16 / 8, lite 12 / 6, feather 8 / 4): the interleaved-frame kernels over the
+//    submodels' own blobs from A1Plan::ws_tiles_off on, as a BANK_A1_IL bank batch; a narrow stream's own rows already ARE the
+//    padded layout (equal state geometry is part of the bank comparison), so its state moves as a plain row copy
+//    (nam_state_rows_copy_kernel).
+enum MixFamily : int
+{
+  MIX_NONE = -1,
+  MIX_A2 = 0,
+  MIX_A1 = 1,
+  MIX_FAMILY_COUNT
+};
+enum MixMove : int // how a narrow group's rows get into and out of the largest submodel's
+{
+  MIX_MOVE_TRANSCODE, // ring by ring of nam_hip_model::transcode[submodel] (a2_transcode.h)
+  MIX_MOVE_COPY // the whole row as it is
+};
+struct MixFamilyRules // kMixFamily[MixFamily] (api_launch.cpp); plain data, as BankFamilyRules
+{
+  const char* name; // as the statistics line and refusals print it
+  int persist; // the PersistKind of the one session: what the largest submodel's plan must be eligible for over EVERY stream
+  int kernel_class; // the kernel class (NAM_HIP_KERNEL_*) a resident batch's one group runs: the session's and the plain launches'
+  int narrow_class; // ... and the class whose state layout a narrow group must keep outside the session (what it runs there)
+  unsigned fns; // bit per KernelFn that may launch a resident batch
+  const char* launch_refusal; // launch_a1_family's answer to any other function
+  int blob_source; // BankBlobSource: what the device image keeps of a submodel's blob, and what the launch arguments are rebased on
+  MixMove move;
+  const char* mover; // the kernel that moves the rows, as the statistics line names it
+};
+extern const MixFamilyRules kMixFamily[MIX_FAMILY_COUNT];
+struct SizeMix
 {
   bool resident = false;
-  DeviceBuf<float> d_blob; // [submodel][stride]: the padded plans' blobs, the largest submodel's own at [full_width]
-  DeviceBuf<float> d_scal; // [submodel][2]: head_scale, the activation's slope (A1Args::bank_scal)
+  DeviceBuf<float> d_blob; // [submodel][stride]: what blob_source keeps of every submodel's (padded) plan, the largest one's own at [full_width]
+  DeviceBuf<float> d_scal; // [submodel][2]: head_scale, the activation's parameter (A1Args::bank_scal)
   DeviceBuf<int> d_member; // [stream] = nam_hip_batch::stream_width, refreshed whenever the batch becomes resident
   long stride = 0;
-  std::vector<DeviceBuf<A2XcRing>> d_rings; // [submodel]: nam_hip_model::transcode[submodel].rings
-  unsigned long long n_transcodes = 0; // (NAM_HIP_SESSION_STATS) launches of nam_a2_transcode_kernel, streams they moved, and the
+  std::vector<DeviceBuf<A2XcRing>> d_rings; // MIX_MOVE_TRANSCODE: [submodel] = nam_hip_model::transcode[submodel].rings
+  unsigned long long n_moves = 0; // (NAM_HIP_SESSION_STATS) launches of the family's mover, streams they moved, and the
   unsigned long long n_streams_moved = 0; // host's time in them, the wait for the batch's stream included
-  double t_transcode_us = 0;
+  double t_move_us = 0;
 };
 
 // Persistent block mode (nam_hip_batch_set_persistent): one resident launch of nam_a1_p2_kernel per session, fed one
@@ -372,7 +410,7 @@ struct nam_hip_batch
   std::vector<float> pipe_cvt; // the _f64 forms of submit / wait: one buffer of float32 on the way in / out
   int kernel = NAM_HIP_KERNEL_AUTO;
   std::vector<WidthGroup> groups;
-  A2Mix mix; // (mix.resident: an A2 container's batch at mixed sizes in persistent mode)
+  SizeMix mix; // (mix.resident: a container's batch at mixed sizes in persistent mode, one session)
   LinearContainer lin; // (lin.on: an all-Linear container's batch)
   std::vector<int> stream_width;
   bool was_reset = false;
@@ -550,16 +588,20 @@ int get_stream_state(nam_hip_batch* b, int stream, void* buf); // (buf: stream_s
 int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size);
 // 64 bits that name a model: architecture, config text, fast_tanh and weights (a container: its submodels'; a nested condition_dsp's too)
 uint64_t model_fingerprint(const ModelSpec& s);
-// An A2 container's batch at mixed sizes (A2Mix). _wanted: persistent mode is on, more than one size is in use, and a session of
-// nam_kq_kernel over the padded plans can hold the batch. _enter / _leave: the narrow streams' state into / out of the largest
-// submodel's rows (nam_a2_transcode_kernel; the batch is quiesced by them, its stream drained on return); no-ops when the batch is
+// A container's batch at mixed sizes (SizeMix). _wanted: persistent mode is on, more than one size is in use, and a session of the
+// family's kernels over the device image can hold the batch. _enter / _leave: the narrow streams' state into / out of the largest
+// submodel's rows (the family's mover; the batch is quiesced by them, its stream drained on return); no-ops when the batch is
 // already there. _sync: whichever of the two `_wanted` asks for — the last step of every control call that changes a size, the
 // mode, the kernel choice or a stream's state; such a call starts with _leave, so between the two the batch is what it is
 // outside persistent mode.
-bool a2mix_wanted(const nam_hip_batch* b);
-int a2mix_enter(nam_hip_batch* b);
-int a2mix_leave(nam_hip_batch* b);
-int a2mix_sync(nam_hip_batch* b);
+bool mix_wanted(const nam_hip_batch* b);
+int mix_enter(nam_hip_batch* b);
+int mix_leave(nam_hip_batch* b);
+int mix_sync(nam_hip_batch* b);
+inline const MixFamilyRules& mix_rules(const nam_hip_batch* b) // (b->model->mix_family is one: mix.resident says so)
+{
+  return kMixFamily[b->model->mix_family];
+}
 // whether a launch or a session of the batch touches the group's own state rows (a resident batch: the largest submodel's only)
 inline bool group_state_in_play(const nam_hip_batch* b, const WidthGroup& g)
 {
@@ -568,6 +610,9 @@ inline bool group_state_in_play(const nam_hip_batch* b, const WidthGroup& g)
 // api_session.cpp
 StateFamily persist_family(const nam_hip_batch* b, const WidthGroup& g);
 int persist_kind(const nam_hip_batch* b);
+// the session a WaveNet group's plan is eligible for if the group held every stream of the batch (persist_kind's rule; mix_wanted
+// asks it of the largest submodel)
+int wavenet_persist_kind(const nam_hip_batch* b, const WidthGroup& g);
 int persist_flush(nam_hip_batch* b, const SessionCaller& caller);
 int persist_wait(nam_hip_batch* b, const SessionCaller& caller, unsigned target, bool whole);
 int persist_stop(nam_hip_batch* b, CallHints hints);
@@ -582,6 +627,9 @@ int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out);
 int upload_bank_group(nam_hip_batch* b, WidthGroup& g);
 int bank_fill_initial_state(nam_hip_batch* b, WidthGroup& g, const int* d_map, int n);
 int bank_set_stream_model(nam_hip_batch* b, const int* stream_ids, int n_ids, int member);
+// Whether a container's submodels are members of ONE bank of the BANK_A1_IL family with the largest one as member 0 — member_refusal
+// and the family's comparison, the ones nam_hip_bank_create runs. "" = they are; else the first reason, naming the submodel.
+std::string container_a1_difference(const nam_hip_model& m);
 // api_host_io.cpp
 bool host_windows(nam_hip_batch* b, int slots, HostWindows& w, bool prealloc = false);
 bool host_mapped_applies(nam_hip_batch* b, int n_frames);

@@ -128,6 +128,10 @@ int pick_kernel(const nam_hip_batch* b, const WidthGroup& g)
   // it (the gate-row kernels), nobody asks here. (api_bank.cpp: kBankFamily)
   if (g.d_bank_member && bank_rules(b).kernel_class != NAM_HIP_KERNEL_AUTO)
     return bank_rules(b).kernel_class;
+  // ... and so does a container's batch at mixed sizes while it is one group on the bank path (SizeMix: mix_wanted has checked that
+  // the class is one the batch's kernel choice admits)
+  if (b->mix.resident && &g == &b->groups[(size_t)b->model->full_width])
+    return mix_rules(b).kernel_class;
   const bool a1 = g.plan->a1.valid && g.d_a1;
   const bool mfma = a1 && (g.plan->a1.ws_ok || g.plan->a1.kt_ok);
   const bool il = a1 && g.plan->a1.il_ok && g.plan->a1.p2_ok; // the interleaved-frame kernels: the official topologies (compile-time job tables)
@@ -493,6 +497,12 @@ static int uniform_act(const A1Plan& a1)
   return a1.arr[0].act;
 }
 
+// first float of a submodel's blob a mixed-size residency's device image keeps (mix_prepare cuts there, the launch rebases on it)
+static int mix_blob_base(const Plan& p, const MixFamilyRules& r)
+{
+  return r.blob_source == BANK_BLOB_KERNEL_REGION ? p.a1.ws_tiles_off : 0;
+}
+
 static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args& a, int n, hipStream_t stream, const LaunchContext& ctx)
 {
   const LaunchStream s(stream, ctx.retired); // (for the session-capable kernels; the others take the bare stream)
@@ -512,11 +522,10 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
     return fail(NAM_HIP_ERR_UNSUPPORTED, bank_rules(b).launch_refusal);
   if (b->mix.resident)
   {
-    // an A2 container at mixed sizes (A2Mix): every stream's rings are in this group's rows, its weights are its submodel's
-    // (padded) blob — the bank path of the two kernels that know it, whole blobs at base offset 0 like an A2 bank's
-    if (&g != &b->groups[(size_t)b->model->full_width] || (fn != FN_KQ && fn != FN_KT_MFMA))
-      return fail(NAM_HIP_ERR_UNSUPPORTED, "A2 container at mixed sizes in persistent mode: only nam_kq_kernel and nam_kt_mfma_kernel run it "
-                                           "(a launch beyond 2^28 frames would take nam_a1_kernel: split the launch)");
+    // a container at mixed sizes (SizeMix): every stream's rings are in this group's rows, its weights are its submodel's (padded)
+    // blob — the bank path of the family's kernels, which are the ones that know it
+    if (&g != &b->groups[(size_t)b->model->full_width] || !((mix_rules(b).fns >> fn) & 1u))
+      return fail(NAM_HIP_ERR_UNSUPPORTED, mix_rules(b).launch_refusal);
     a.blob = b->mix.d_blob.get();
     a.bank_member = b->mix.d_member.get();
     a.bank_scal = b->mix.d_scal.get();
@@ -526,7 +535,7 @@ static int launch_a1_family(nam_hip_batch* b, WidthGroup& g, KernelFn fn, A1Args
   {
     const int act = uniform_act(p.a1);
     // a bank's rows start at the kernels' region of the blob (api_bank.cpp): offsets from there
-    const int base = g.d_bank_member ? bank_blob_base(p, b->bank->family) : 0;
+    const int base = g.d_bank_member ? bank_blob_base(p, b->bank->family) : b->mix.resident ? mix_blob_base(p, mix_rules(b)) : 0;
     a.tiles_off = p.a1.ws_tiles_off - base;
     a.consts_off = p.a1.ws_consts_off - base;
     a.xt_off = p.a1.ws_xt_off - base;
@@ -935,19 +944,37 @@ int move_streams_to_width(nam_hip_batch* b, const std::vector<int>& moved, int w
   return rc;
 }
 
-// ---- an A2 container's batch at mixed sizes in persistent mode (api_internal.h: A2Mix) ----
+// ---- a container's batch at mixed sizes in persistent mode (api_internal.h: SizeMix) ----
 
-bool a2mix_wanted(const nam_hip_batch* b)
+// The two residencies' rules (api_internal.h: MixFamilyRules); the functions below ask this table and name no family
+const MixFamilyRules kMixFamily[MIX_FAMILY_COUNT] = {
+  {"A2", PERSIST_KQ, NAM_HIP_KERNEL_A1_MFMA, NAM_HIP_KERNEL_WN_REG, 1u << FN_KQ | 1u << FN_KT_MFMA,
+   "A2 container at mixed sizes in persistent mode: only nam_kq_kernel and nam_kt_mfma_kernel run it "
+   "(a launch beyond 2^28 frames would take nam_a1_kernel: split the launch)",
+   BANK_BLOB_WHOLE, MIX_MOVE_TRANSCODE, "nam_a2_transcode_kernel"},
+  {"A1", PERSIST_A1_P2, NAM_HIP_KERNEL_A1_IL, NAM_HIP_KERNEL_A1_IL, 1u << FN_A1_P2 | 1u << FN_A1_P4 | 1u << FN_A1_Q,
+   "A1 container at mixed sizes in persistent mode: only the interleaved-frame kernels (nam_a1_q_kernel, nam_a1_p4_kernel, "
+   "nam_a1_p2_kernel) run it",
+   BANK_BLOB_KERNEL_REGION, MIX_MOVE_COPY, "nam_state_rows_copy_kernel"},
+};
+
+// the plan whose blob is submodel w's member of the device image: the largest submodel's own, a padded second plan, or the submodel's own
+static const Plan& mix_member_plan(const nam_hip_model& m, size_t w)
+{
+  return ((int)w == m.full_width || m.padded.empty()) ? m.plans[w] : m.padded[w];
+}
+
+bool mix_wanted(const nam_hip_batch* b)
 {
   const nam_hip_model& m = *b->model;
-  if (!b->ps.enabled || b->bank || !m.a2_mix() || b->no_pipe)
+  if (!b->ps.enabled || b->bank || m.mix_family == MIX_NONE)
     return false;
+  const MixFamilyRules& r = kMixFamily[m.mix_family];
   const WidthGroup& full = b->groups[(size_t)m.full_width];
-  // what persist_kind asks of a one-size batch on nam_kq_kernel (PERSIST_KQ), of the largest submodel's plan over EVERY stream
-  if (!(full.plan->a1.valid && kq_runs(b, *full.plan) && !full.plan->a1.ws_ok && b->n_streams <= kPersistTurns * std::max(b->n_cus, 1)
-        && pick_kernel(b, full) == NAM_HIP_KERNEL_A1_MFMA))
+  // what persist_kind asks of a one-size batch on the family's session kernel, of the largest submodel's plan over EVERY stream
+  if (wavenet_persist_kind(b, full) != r.persist)
     return false;
-  if (full.state_family != STATE_FRESH && full.state_family != state_family_of(*full.plan, NAM_HIP_KERNEL_A1_MFMA))
+  if (full.state_family != STATE_FRESH && full.state_family != state_family_of(*full.plan, r.kernel_class))
     return false;
   int sizes = 0;
   for (size_t w = 0; w < b->groups.size(); w++)
@@ -956,37 +983,47 @@ bool a2mix_wanted(const nam_hip_batch* b)
     if (g.streams.empty())
       continue;
     sizes++;
-    // a narrow stream comes from and goes back to nam_wn_reg_kernel's layout: what the group runs outside the session
-    if ((int)w != m.full_width && (!m.transcode[w].ok || !g.d_state || pick_kernel(b, g) != NAM_HIP_KERNEL_WN_REG
-                                   || (g.state_family != STATE_FRESH && g.state_family != STATE_WN_REG)))
+    if ((int)w == m.full_width)
+      continue;
+    // a narrow stream comes from and goes back to the layout of what its group runs outside the session
+    const StateFamily own = state_family_of(*g.plan, r.narrow_class);
+    if (!g.d_state || state_family_of(*g.plan, pick_kernel(b, g)) != own || (g.state_family != STATE_FRESH && g.state_family != own))
+      return false;
+    if (r.move == MIX_MOVE_TRANSCODE && !m.transcode[w].ok)
+      return false;
+    if (r.move == MIX_MOVE_COPY && g.plan->state_floats != full.plan->state_floats)
       return false;
   }
   return sizes > 1;
 }
 
-// the device side of A2Mix, once per batch (a control call: set_persistent, set_slimmable_size ... allocate, process calls never)
-static int a2mix_prepare(nam_hip_batch* b)
+// the device side of SizeMix, once per batch (a control call: set_persistent, set_slimmable_size ... allocate, process calls never)
+static int mix_prepare(nam_hip_batch* b)
 {
-  A2Mix& mx = b->mix;
+  SizeMix& mx = b->mix;
   if (mx.d_blob)
     return NAM_HIP_OK;
   const nam_hip_model& m = *b->model;
+  const MixFamilyRules& r = mix_rules(b);
   const Plan& full = m.plans[(size_t)m.full_width];
   const size_t n = m.plans.size();
-  const size_t stride = (full.blob.size() + 3) / 4 * 4; // (the kernels read 16-byte records)
+  const size_t region = full.blob.size() - (size_t)mix_blob_base(full, r);
+  const size_t stride = (region + 3) / 4 * 4; // (the kernels read 16-byte records)
   std::vector<float> blobs(n * stride, 0.0f), scal(2 * n, 0.0f);
   DeviceBuf<float> d_blob, d_scal;
   DeviceBuf<int> d_member;
   std::vector<DeviceBuf<A2XcRing>> d_rings(n);
   for (size_t w = 0; w < n; w++)
   {
-    const Plan& p = (int)w == m.full_width ? full : m.padded[w];
-    if (p.blob.size() != full.blob.size())
-      return fail(NAM_HIP_ERR_MODEL, "A2 container: a padded plan's blob does not have the largest submodel's size");
-    std::memcpy(blobs.data() + w * stride, p.blob.data(), p.blob.size() * sizeof(float));
+    const Plan& p = mix_member_plan(m, w);
+    const int base = mix_blob_base(p, r);
+    if (base < 0 || (size_t)base > p.blob.size() || p.blob.size() - (size_t)base != region)
+      return fail(NAM_HIP_ERR_MODEL, "container at mixed sizes: a submodel's blob does not have the largest submodel's size");
+    std::memcpy(blobs.data() + w * stride, p.blob.data() + base, region * sizeof(float));
     scal[2 * w] = p.blob[(size_t)p.a1.head_scale_off];
-    scal[2 * w + 1] = p.a1.arr[0].act == ACT_RELU ? 0.0f : p.a1.arr[0].act_p0; // (as a bank's members: api_bank.cpp)
-    if ((int)w == m.full_width)
+    // (as a bank's members, api_bank.cpp: nam_kq_kernel runs ReLU as LeakyReLU with slope 0)
+    scal[2 * w + 1] = (r.persist == PERSIST_KQ && p.a1.arr[0].act == ACT_RELU) ? 0.0f : p.a1.arr[0].act_p0;
+    if ((int)w == m.full_width || r.move != MIX_MOVE_TRANSCODE)
       continue;
     const A2Transcode& t = m.transcode[w];
     // the table against the rows it will be run on (a2_transcode_check has walked it at load: build_model)
@@ -1005,11 +1042,37 @@ static int a2mix_prepare(nam_hip_batch* b)
   return NAM_HIP_OK;
 }
 
-// every narrow stream's state between its group's row and the largest submodel's, on the batch's stream (the batch is quiesced)
-static int a2mix_move_all(nam_hip_batch* b, bool to_padded)
+// the streams `d_streams` (device memory, n of them) of the narrow group `w` between its own rows and the largest submodel's, by the
+// family's mover, on the batch's stream
+static int mix_move(nam_hip_batch* b, size_t w, const int* d_streams, int n, bool to_resident)
 {
   const nam_hip_model& m = *b->model;
   WidthGroup& full = b->groups[(size_t)m.full_width];
+  WidthGroup& g = b->groups[w];
+  if (!d_streams || !g.d_state || !full.d_state)
+    return fail(NAM_HIP_ERR_MODEL, "container at mixed sizes: a narrow group without a stream list or state");
+  if (mix_rules(b).move == MIX_MOVE_TRANSCODE)
+    NAM_HIP_CHECK(launch_a2_transcode(b->mix.d_rings[w].get(), (int)m.transcode[w].rings.size(), full.d_state.get(), full.state_stride, g.d_state.get(),
+                                      g.state_stride, d_streams, n, to_resident, b->stream.get()));
+  else
+  {
+    // (mix_wanted: the two plans' rows have one size; a row is state_stride >= state_floats floats on either side)
+    if (g.plan->state_floats != full.plan->state_floats || g.state_stride < g.plan->state_floats || full.state_stride < full.plan->state_floats)
+      return fail(NAM_HIP_ERR_MODEL, "container at mixed sizes: a narrow group's state rows are not the largest submodel's size");
+    float* const own = g.d_state.get();
+    float* const res = full.d_state.get();
+    NAM_HIP_CHECK(launch_state_rows_copy(to_resident ? res : own, to_resident ? full.state_stride : g.state_stride, to_resident ? own : res,
+                                         to_resident ? g.state_stride : full.state_stride, d_streams, n, g.plan->state_floats, b->stream.get()));
+  }
+  b->mix.n_moves++;
+  b->mix.n_streams_moved += (unsigned long long)n;
+  return NAM_HIP_OK;
+}
+
+// every narrow stream's state between its group's row and the largest submodel's, on the batch's stream (the batch is quiesced)
+static int mix_move_all(nam_hip_batch* b, bool to_resident)
+{
+  const nam_hip_model& m = *b->model;
   const double t0 = stats_on() ? stat_now_us() : 0.0;
   for (size_t w = 0; w < b->groups.size(); w++)
   {
@@ -1017,30 +1080,27 @@ static int a2mix_move_all(nam_hip_batch* b, bool to_padded)
     if ((int)w == m.full_width || g.streams.empty())
       continue;
     // (a narrow group of a mixed batch never holds every stream: refresh_map has given it its stream list)
-    if (!g.d_map || !g.d_state || !full.d_state)
-      return fail(NAM_HIP_ERR_MODEL, "A2 container: a narrow group without a stream map or state");
-    NAM_HIP_CHECK(launch_a2_transcode(b->mix.d_rings[w].get(), (int)m.transcode[w].rings.size(), full.d_state.get(), full.state_stride, g.d_state.get(),
-                                      g.state_stride, g.d_map.get(), (int)g.streams.size(), to_padded, b->stream.get()));
-    b->mix.n_transcodes++;
-    b->mix.n_streams_moved += g.streams.size();
+    if (const int rc = mix_move(b, w, g.d_map.get(), (int)g.streams.size(), to_resident))
+      return rc;
   }
   NAM_HIP_CHECK(hipStreamSynchronize(b->stream.get()));
   if (stats_on())
-    b->mix.t_transcode_us += stat_now_us() - t0;
+    b->mix.t_move_us += stat_now_us() - t0;
   return NAM_HIP_OK;
 }
 
-int a2mix_enter(nam_hip_batch* b)
+int mix_enter(nam_hip_batch* b)
 {
   if (b->mix.resident)
     return NAM_HIP_OK;
   NAM_HIP_CHECK(quiesce(b));
-  if (const int rc = a2mix_prepare(b))
+  if (const int rc = mix_prepare(b))
     return rc;
   NAM_HIP_CHECK(hipMemcpy(b->mix.d_member.get(), b->stream_width.data(), (size_t)b->n_streams * sizeof(int), hipMemcpyHostToDevice));
-  if (const int rc = a2mix_move_all(b, true))
+  if (const int rc = mix_move_all(b, true))
     return rc;
   const nam_hip_model& m = *b->model;
+  const MixFamilyRules& r = mix_rules(b);
   for (size_t w = 0; w < b->groups.size(); w++)
   {
     WidthGroup& g = b->groups[w];
@@ -1048,26 +1108,26 @@ int a2mix_enter(nam_hip_batch* b)
       continue;
     // zeros are zeros in either layout; from here on the rows are what they were moved as
     if (g.state_family == STATE_FRESH)
-      g.state_family = (int)w == m.full_width ? state_family_of(*g.plan, NAM_HIP_KERNEL_A1_MFMA) : STATE_WN_REG;
+      g.state_family = state_family_of(*g.plan, (int)w == m.full_width ? r.kernel_class : r.narrow_class);
   }
   b->mix.resident = true;
   return NAM_HIP_OK;
 }
 
-int a2mix_leave(nam_hip_batch* b)
+int mix_leave(nam_hip_batch* b)
 {
   if (!b->mix.resident)
     return NAM_HIP_OK;
   NAM_HIP_CHECK(quiesce(b));
-  if (const int rc = a2mix_move_all(b, false))
+  if (const int rc = mix_move_all(b, false))
     return rc;
   b->mix.resident = false;
   return NAM_HIP_OK;
 }
 
-int a2mix_sync(nam_hip_batch* b)
+int mix_sync(nam_hip_batch* b)
 {
-  return a2mix_wanted(b) ? a2mix_enter(b) : a2mix_leave(b);
+  return mix_wanted(b) ? mix_enter(b) : mix_leave(b);
 }
 
 // ---- stream slots (include/nam_hip.h: nam_hip_batch_restart_streams, _get / _set_stream_state) ----
@@ -1096,12 +1156,12 @@ static int restart_streams_in_groups(nam_hip_batch* b, const std::vector<int>& i
 int restart_streams(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
 {
   NAM_HIP_CHECK(quiesce(b));
-  // (an A2 container at mixed sizes: every stream back in its own group's rows, the restart as ever, the batch resident again)
-  if (const int rc = a2mix_leave(b))
+  // (a container at mixed sizes: every stream back in its own group's rows, the restart as ever, the batch resident again)
+  if (const int rc = mix_leave(b))
     return rc;
   if (const int rc = restart_streams_in_groups(b, ids, prewarm))
     return rc;
-  return a2mix_sync(b);
+  return mix_sync(b);
 }
 static int restart_streams_in_groups(nam_hip_batch* b, const std::vector<int>& ids, bool prewarm)
 {
@@ -1217,21 +1277,18 @@ int get_stream_state(nam_hip_batch* b, int stream, void* buf)
   std::vector<float> payload(bytes / sizeof(float));
   if (b->mix.resident && w != b->model->full_width)
   {
-    // the stream lives zero-padded in the largest submodel's rows (A2Mix): its blob is its own group's row, as ever — this one
+    // the stream lives zero-padded in the largest submodel's rows (SizeMix): its blob is its own group's row, as ever — this one
     // stream's rings are copied there first (the padded copy stays the live one; no other stream is touched)
     DeviceBuf<int> d_one;
     NAM_HIP_CHECK(upload(d_one, &stream, 1));
-    WidthGroup& full = b->groups[(size_t)b->model->full_width];
     const double t0 = stats_on() ? stat_now_us() : 0.0;
-    const hipError_t e = launch_a2_transcode(b->mix.d_rings[(size_t)w].get(), (int)b->model->transcode[(size_t)w].rings.size(), full.d_state.get(),
-                                             full.state_stride, g.d_state.get(), g.state_stride, d_one.get(), 1, false, b->stream.get());
+    const int rm = mix_move(b, (size_t)w, d_one.get(), 1, false);
     const hipError_t es = hipStreamSynchronize(b->stream.get()); // (before `d_one` goes)
-    NAM_HIP_CHECK(e);
+    if (rm != NAM_HIP_OK)
+      return rm;
     NAM_HIP_CHECK(es);
-    b->mix.n_transcodes++;
-    b->mix.n_streams_moved++;
     if (stats_on())
-      b->mix.t_transcode_us += stat_now_us() - t0;
+      b->mix.t_move_us += stat_now_us() - t0;
   }
   if (q.arch == ARCH_LINEAR)
   {
@@ -1261,12 +1318,12 @@ static int set_stream_state_in_groups(nam_hip_batch* b, int stream, const void* 
 int set_stream_state(nam_hip_batch* b, int stream, const void* buf, int64_t size)
 {
   NAM_HIP_CHECK(quiesce(b));
-  // (an A2 container at mixed sizes: the blob is written into the stream's own group's row with every stream back in its own; what
+  // (a container at mixed sizes: the blob is written into the stream's own group's row with every stream back in its own; what
   // the batch is afterwards — the blob may have changed the stream's size — decides where the streams live from here on)
-  if (const int rc = a2mix_leave(b))
+  if (const int rc = mix_leave(b))
     return rc;
   const int rc = set_stream_state_in_groups(b, stream, buf, size);
-  const int rs = a2mix_sync(b); // (also behind a refusal: the batch goes back to where it was)
+  const int rs = mix_sync(b); // (also behind a refusal: the batch goes back to where it was)
   return rc != NAM_HIP_OK ? rc : rs;
 }
 static int set_stream_state_in_groups(nam_hip_batch* b, int stream, const void* buf, int64_t size)
@@ -1435,6 +1492,19 @@ int build_model(std::shared_ptr<ModelSpec> spec, nam_hip_model** out)
     {
       m->padded = std::move(padded);
       m->transcode = std::move(transcode);
+      m->mix_family = MIX_A2;
+    }
+    else if (full.a1.valid && full.a1.il_ok && full.a1.p2_ok)
+    {
+      // ... or on the official WaveNet topology (standard, lite, feather): the submodels as they are planned — zero-padded to
+      // 16 / 8 in the padded ring layout — are members of one BANK_A1_IL bank, or the container has no residency. Asked of
+      // the bank's own rules (api_bank.cpp), once, here.
+      const std::string why = container_a1_difference(*m);
+      if (why.empty())
+        m->mix_family = MIX_A1;
+      m->mix_note = why.empty() ? "a1_mixed_session=1 (every submodel is the official topology at padded 16 / 8 channels: a batch at mixed "
+                                  "sizes runs persistent mode as one session of nam_a1_q_kernel)"
+                                : "a1_mixed_session=0 (" + why + ": a batch at mixed sizes runs a launch per size and no session)";
     }
   }
   *out = m.release();

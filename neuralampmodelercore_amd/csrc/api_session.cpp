@@ -24,10 +24,10 @@ int persist_kind(const nam_hip_batch* b)
     return PERSIST_NONE;
   if (g.plan->arch == ARCH_LINEAR) // no recurrence, nothing to keep resident: a Linear batch launches per call (Linear, follow-up)
     return PERSIST_NONE;
-  // an A2 container at mixed sizes whose narrow streams live zero-padded next to the largest submodel's (A2Mix; a2mix_wanted has
-  // asked what PERSIST_KQ asks below, of every stream): one group, one launch of nam_kq_kernel, one command ring
+  // a container at mixed sizes whose narrow streams live zero-padded next to the largest submodel's (SizeMix; mix_wanted has asked
+  // what its family's session asks below, of every stream): one group, one launch of the family's kernel, one command ring
   if (b->mix.resident)
-    return PERSIST_KQ;
+    return mix_rules(b).persist;
   const int cus = std::max(b->n_cus, 1);
   {
     // nam_wn_reg_kernel serves every width group with one launch: a mixed-width batch is one session. Its workgroups
@@ -46,20 +46,7 @@ int persist_kind(const nam_hip_batch* b)
   if ((int)g.streams.size() != b->n_streams || g.d_map)
     return PERSIST_NONE;
   if (g.plan->arch == ARCH_WAVENET)
-  {
-    // One workgroup per stream holding most of a CU's LDS: `cus` of them are on the chip at once. More streams than
-    // that still make a session — the workgroups never wait for a command, so the resident ones drain the ring and
-    // leave, the next ones start behind them and consume the same commands (every workgroup resumes from its own
-    // count) — in as many turns as it takes; bounded so that the completion words stay a short scan for the host.
-    const int wg_limit = kPersistTurns * cus;
-    if (g.plan->a1.valid && g.plan->a1.il_ok && g.plan->a1.p2_ok && b->n_streams <= wg_limit
-        && (b->kernel == NAM_HIP_KERNEL_AUTO || b->kernel == NAM_HIP_KERNEL_A1_IL))
-      return PERSIST_A1_P2;
-    if (!b->no_pipe && g.plan->a1.valid && kq_runs(b, *g.plan) && !g.plan->a1.ws_ok && b->n_streams <= wg_limit
-        && pick_kernel(b, g) == NAM_HIP_KERNEL_A1_MFMA)
-      return PERSIST_KQ;
-    return PERSIST_NONE;
-  }
+    return wavenet_persist_kind(b, g);
   if (g.plan->arch == ARCH_LSTM && b->kernel == NAM_HIP_KERNEL_AUTO)
   {
     const LSTMPlan& L = g.plan->lstm;
@@ -68,6 +55,22 @@ int persist_kind(const nam_hip_batch* b)
     if (lstm_wide_eligible(L) && b->n_streams <= 4 * cus) // one wavefront per SIMD
       return PERSIST_LSTM_WIDE;
   }
+  return PERSIST_NONE;
+}
+
+int wavenet_persist_kind(const nam_hip_batch* b, const WidthGroup& g)
+{
+  // One workgroup per stream holding most of a CU's LDS: `cus` of them are on the chip at once. More streams than
+  // that still make a session — the workgroups never wait for a command, so the resident ones drain the ring and
+  // leave, the next ones start behind them and consume the same commands (every workgroup resumes from its own
+  // count) — in as many turns as it takes; bounded so that the completion words stay a short scan for the host.
+  const int wg_limit = kPersistTurns * std::max(b->n_cus, 1);
+  if (g.plan->a1.valid && g.plan->a1.il_ok && g.plan->a1.p2_ok && b->n_streams <= wg_limit
+      && (b->kernel == NAM_HIP_KERNEL_AUTO || b->kernel == NAM_HIP_KERNEL_A1_IL))
+    return PERSIST_A1_P2;
+  if (!b->no_pipe && g.plan->a1.valid && kq_runs(b, *g.plan) && !g.plan->a1.ws_ok && b->n_streams <= wg_limit
+      && pick_kernel(b, g) == NAM_HIP_KERNEL_A1_MFMA)
+    return PERSIST_KQ;
   return PERSIST_NONE;
 }
 
@@ -389,9 +392,13 @@ static int persist_prepare_alloc(nam_hip_batch* b)
   // a session of the headline kernel may start its low-latency sibling later (short_bursts): its code object is loaded now,
   // not at the switch (~1.6 ms on first use) — both output forms, the window is not known yet
   const WidthGroup& g0 = b->groups[b->model->full_width];
+  // (a container with the A1 residency runs the plain form while its streams are at one size and the bank form while they are mixed)
+  const bool both_forms = b->model->mix_family == MIX_A1 && !b->bank;
   if (g0.plan->arch == ARCH_WAVENET && g0.plan->a1.valid && g0.plan->a1.p2_ok && q_runs(b, *g0.plan))
     for (int oh = 0; oh < 2; oh++)
-      NAM_HIP_CHECK(preload_a1_p4_session(g0.plan->a1.p2_c0, g0.plan->a1.p2_c1, g0.plan->a1.arr[0].act, oh != 0, (bool)g0.d_bank_member));
+      for (int bank = 0; bank < 2; bank++)
+        if (both_forms || (bank != 0) == (bool)g0.d_bank_member)
+          NAM_HIP_CHECK(preload_a1_p4_session(g0.plan->a1.p2_c0, g0.plan->a1.p2_c1, g0.plan->a1.arr[0].act, oh != 0, bank != 0));
   return NAM_HIP_OK;
 }
 

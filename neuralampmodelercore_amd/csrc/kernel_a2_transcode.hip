@@ -3,8 +3,12 @@
 // of the other). One workgroup per (ring, stream); a thread moves one float of the padded side at a time, channels fastest, so the
 // padded rows are whole 32-byte accesses and the narrow side is read / written in its groups of up to four channels. It moves
 // data and does no arithmetic: to the padded side the channels the narrow model does not have become +0, the other way they are
-// dropped; the ring's write position goes along. Runs inside control calls only (api_launch.cpp: a2mix_enter / a2mix_leave, the
+// dropped; the ring's write position goes along. Runs inside control calls only (api_launch.cpp: mix_enter / mix_leave, the
 // stream slots), on the batch's stream, with the batch quiesced.
+// Behind it nam_state_rows_copy_kernel, the mover of a residency whose two sides keep ONE layout (the official WaveNet topology's
+// lite and feather submodels next to the standard one: api_internal.h, MIX_A1): whole state rows, bit for bit.
+#include <algorithm>
+
 #include "device_common.h"
 #include "kernels.h"
 
@@ -56,6 +60,33 @@ hipError_t launch_a2_transcode(const A2XcRing* rings, int n_rings, float* a2_sta
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(nam_a2_transcode_kernel, dim3((unsigned)n_rings, (unsigned)n_streams), dim3(256), 0, stream, rings, a2_state, a2_stride,
                      wr_state, wr_stride, streams, to_padded ? 1 : 0);
+  return hipGetLastError();
+}
+
+// Rows `streams[k]` of `src` into the same rows of `dst`, `floats` floats each; one workgroup column per stream (blockIdx.y), the
+// row's floats spread over blockIdx.x x 256 threads. Moves data and does no arithmetic.
+__global__ __launch_bounds__(256) void nam_state_rows_copy_kernel(float* __restrict__ dst, long dst_stride, const float* __restrict__ src,
+                                                                  long src_stride, const int* __restrict__ streams, int floats)
+{
+  const int stream = streams ? streams[blockIdx.y] : (int)blockIdx.y;
+  float* const D = dst + (size_t)stream * (size_t)dst_stride;
+  const float* const S = src + (size_t)stream * (size_t)src_stride;
+  for (int i = (int)(blockIdx.x * 256 + threadIdx.x); i < floats; i += (int)(gridDim.x * 256))
+    D[i] = S[i];
+}
+
+// `streams`: n_streams stream indices in device memory (nullptr: streams 0 .. n_streams - 1), each below the row count of both
+// allocations; `floats` <= both strides (the caller's check: api_launch.cpp, mix_move)
+hipError_t launch_state_rows_copy(float* dst, long dst_stride, const float* src, long src_stride, const int* streams, int n_streams, int floats,
+                                  hipStream_t stream)
+{
+  if (n_streams <= 0 || floats <= 0)
+    return hipSuccess;
+  if (!dst || !src || dst == src || n_streams > 65535 || floats > dst_stride || floats > src_stride)
+    return hipErrorInvalidValue;
+  const unsigned per_row = (unsigned)std::min((floats + 255) / 256, 64); // (up to 64 workgroups a row; a thread then takes every 16,384th float)
+  hipLaunchKernelGGL(nam_state_rows_copy_kernel, dim3(per_row, (unsigned)n_streams), dim3(256), 0, stream, dst, dst_stride, src, src_stride, streams,
+                     floats);
   return hipGetLastError();
 }
 } // namespace namhip

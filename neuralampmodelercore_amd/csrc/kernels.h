@@ -383,6 +383,10 @@ hipError_t launch_fill_state_bank(float* state, long state_stride, const int* st
 // (`a2_state`), ring by ring of the device table `rings` (a2_transcode.h); a plain copy, zeros into the padded channels
 hipError_t launch_a2_transcode(const A2XcRing* rings, int n_rings, float* a2_state, long a2_stride, float* wr_state, long wr_stride,
                                const int* streams, int n_streams, bool to_padded, hipStream_t stream);
+// nam_state_rows_copy_kernel (kernel_a2_transcode.hip): the state rows of the streams `streams` (device memory; nullptr = 0 ..
+// n_streams - 1) from `src` to `dst`, `floats` floats a row, bit for bit — two allocations that keep one layout
+hipError_t launch_state_rows_copy(float* dst, long dst_stride, const float* src, long src_stride, const int* streams, int n_streams, int floats,
+                                  hipStream_t stream);
 // One stream's columns [col0, col0 + n_cols) of a Linear batch's history ring `hist` = [hist_frames][cols_pad] at position `pos`
 // (the row the next frame goes to: the oldest). `rows` = [hist_frames][n_cols] in device memory, oldest frame first
 // (stream_state.h: ring_row); unused by LINEAR_COLS_ZERO. No other column is read or written.

@@ -190,6 +190,8 @@ int64_t nam_hip_model_get_string(const nam_hip_model* model, int field, char* bu
                   + (p.wr.ok ? std::string(" wn_reg=1") : " wn_reg=0 (" + p.wr.why + ")")
                   + (p.wr.jit_failed.empty() ? std::string() : " wn_reg_jit=failed (" + p.wr.jit_failed + ")");
       }
+      if (!model->mix_note.empty()) // (a container on the official WaveNet topology: whether it has the mixed-size residency)
+        text += " | container: " + model->mix_note;
       if (lin_container_model(*model)) // (the plans above are the submodels' own: as one-model batches run them)
         text += " | container: kernel=nam_linear_pairs_kernel, one ring for every stream, ring_frames="
                 + std::to_string(lin_container_hist_frames(*model, 0));
@@ -433,9 +435,9 @@ void nam_hip_batch_destroy(nam_hip_batch* batch)
                  batch->ps.n_starts, batch->ps.n_launches, batch->ps.n_flush_relaunches, batch->ps.n_host_doorbells, batch->ps.n_stream_doorbells);
   if (stats_on() && batch->ps.n_starts)
     std::fprintf(stderr, "nam_hip session launches: %llu publish every command, %llu of them linger\n", batch->ps.n_publishing, batch->ps.n_lingering);
-  if (stats_on() && batch->mix.n_transcodes)
-    std::fprintf(stderr, "nam_hip A2 mixed sizes: %llu launches of nam_a2_transcode_kernel moved %llu stream states, %.1f us of control calls in all\n",
-                 batch->mix.n_transcodes, batch->mix.n_streams_moved, batch->mix.t_transcode_us);
+  if (stats_on() && batch->mix.n_moves)
+    std::fprintf(stderr, "nam_hip %s mixed sizes: %llu launches of %s moved %llu stream states, %.1f us of control calls in all\n",
+                 mix_rules(batch).name, batch->mix.n_moves, mix_rules(batch).mover, batch->mix.n_streams_moved, batch->mix.t_move_us);
   if (stats_on() && batch->ps.n_waits)
   {
     std::fprintf(stderr, "nam_hip tickets: %llu waits, %.1f looks at the completion word each\n", batch->ps.n_waits, (double)batch->ps.n_polls / batch->ps.n_waits);
@@ -453,7 +455,7 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
     return fail(NAM_HIP_ERR_INVALID_ARGUMENT, "nam_hip_batch_reset: null batch");
   NAM_HIP_CHECK(hipSetDevice(batch->device));
   NAM_HIP_CHECK(quiesce(batch)); // launches still running on a caller-supplied stream must not race with the zeroing
-  batch->mix.resident = false; // (an A2 container at mixed sizes: every stream of every group is reset in its own group's rows, as ever — nothing to move back)
+  batch->mix.resident = false; // (a container at mixed sizes: every stream of every group is reset in its own group's rows, as ever — nothing to move back)
   batch->was_reset = true;
   batch->reset_with_prewarm = prewarm != 0;
   if (batch->lin.on) // zero history, as a Linear batch's; the streams keep their submodels
@@ -471,7 +473,7 @@ int nam_hip_batch_reset(nam_hip_batch* batch, int prewarm)
       return rc;
   }
   NAM_HIP_CHECK(hipStreamSynchronize(batch->stream.get()));
-  if (const int rc = a2mix_sync(batch)) // (... and its narrow streams' fresh state moves next to the largest submodel's again)
+  if (const int rc = mix_sync(batch)) // (... and its narrow streams' fresh state moves next to the largest submodel's again)
     return rc;
   if (batch->ps.enabled && persist_eligible(batch)) // (a session's window-independent resources: see nam_hip_batch_set_persistent)
   {
@@ -553,17 +555,17 @@ int nam_hip_batch_set_slimmable_size(nam_hip_batch* batch, const int* stream_ids
   NAM_HIP_CHECK(quiesce(batch));
   if (batch->lin.on) // the moved streams' columns of the one ring become zero: a freshly reset submodel
     return lin_container_move(batch, moved, w, true);
-  // an A2 container in persistent mode (A2Mix): a change that mixes or un-mixes the batch moves the OTHER streams' state between
+  // a container with a mixed-size residency in persistent mode (SizeMix): a change that mixes or un-mixes the batch moves the OTHER streams' state between
   // the two layouts — a copy, so they go on as if nothing had happened; the named streams get their fresh state in their new
   // group's own rows first, as ever
-  if (const int rc = a2mix_leave(batch))
+  if (const int rc = mix_leave(batch))
     return rc;
   if (const int rc = move_streams_to_width(batch, moved, w))
     return rc;
   // fresh sub-model state for the streams that moved: Reset (+ prewarm) as in slimmable.cpp:433-447
   if (const int rc = reset_moved_streams(batch, batch->groups[w], moved, false))
     return rc;
-  if (const int rc = a2mix_sync(batch))
+  if (const int rc = mix_sync(batch))
     return rc;
   if (batch->mix.resident) // (a batch that has just become one session: its ring and words, outside the audio path)
     return persist_prepare(batch);
@@ -606,8 +608,8 @@ int nam_hip_batch_process_device(nam_hip_batch* batch, const float* d_in, float*
   }
   if (batch->lin.on) // one launch for every stream, whichever submodel each is on
     return lin_container_launch(batch, d_in, d_out, n_frames, (long)frame_stride, s);
-  if (batch->mix.resident) // an A2 container at mixed sizes, a call outside the session (a ragged length): every stream's rings are in
-                           // the largest submodel's rows — one launch of its kernels over all of them, as an all-Full batch falls back
+  if (batch->mix.resident) // a container at mixed sizes, a call outside the session (a ragged length): every stream's rings are in
+                           // the largest submodel's rows — one launch of its kernels' bank form over all of them
     return launch_group(batch, batch->groups[(size_t)batch->model->full_width], nullptr, batch->n_streams, d_in, d_out, n_frames, (long)frame_stride, s,
                         LaunchContext());
   for (auto& g : batch->groups)
@@ -834,9 +836,9 @@ int nam_hip_batch_set_persistent(nam_hip_batch* batch, int enable)
       return rc;
   }
   batch->ps.enabled = enable != 0; // (persist_eligible / persist_kind look at it)
-  // an A2 container at mixed sizes: on, its narrow streams move next to the largest submodel's (one session of nam_kq_kernel); off,
+  // a container at mixed sizes (SizeMix): on, its narrow streams move next to the largest submodel's (one session); off,
   // they move back to their own groups' rows and the batch launches per size again
-  if (const int rc = a2mix_sync(batch))
+  if (const int rc = mix_sync(batch))
   {
     batch->ps.enabled = false;
     return rc;
@@ -885,12 +887,12 @@ int nam_hip_batch_set_kernel(nam_hip_batch* batch, int kernel)
   }
   if (batch->mix.resident)
   {
-    // an A2 container at mixed sizes: the choice is made on the batch as it is outside persistent mode (every stream in its own
+    // a container at mixed sizes: the choice is made on the batch as it is outside persistent mode (every stream in its own
     // group's rows), and whatever it turns out to be decides where the streams live afterwards
-    if (const int rc = a2mix_leave(batch))
+    if (const int rc = mix_leave(batch))
       return rc;
     const int rc = nam_hip_batch_set_kernel(batch, kernel);
-    const int rs = a2mix_sync(batch);
+    const int rs = mix_sync(batch);
     return rc != NAM_HIP_OK ? rc : rs;
   }
   if (batch->model->spec->arch == ARCH_LINEAR || batch->lin.on) // one device engine (include/nam_hip.h): nothing to choose
@@ -1011,7 +1013,7 @@ const char* nam_hip_batch_kernel_name_for(const nam_hip_batch* batch, int n_fram
     return "nam_linear_pairs_kernel";
   // the group with the most streams (a uniform batch has exactly one populated group)
   const WidthGroup* best = &batch->groups[batch->model->full_width];
-  // (an A2 container at mixed sizes in persistent mode is ONE group, the largest submodel's, whatever the sizes' shares: A2Mix)
+  // (a container at mixed sizes in persistent mode is ONE group, the largest submodel's, whatever the sizes' shares: SizeMix)
   for (const auto& g : batch->groups)
     if (g.streams.size() > best->streams.size() && !batch->mix.resident)
       best = &g;
